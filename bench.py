@@ -5,7 +5,10 @@ Headline workload (BASELINE.json configs[1]): synthetic graph of the public WN18
 train triples -> 173 670 directed edges + N self loops per layer), 2 layers 100 -> 200 -> 200, eval mode. A "step" is
 one encoder forward over the whole graph: one fused launch per layer (aggregation + dense step + BN + tanh + relation
 projection), replayed from a hipGraph. Inputs (tables, CSR, weights) are resident in HBM before the timed region.
-The same run also reports, in sub-objects of the ONE JSON line printed by rank 0:
+A plain run sets up, warms up, times the K steps and prints the ONE JSON line (rank 0); `--dump-outputs DIR` also
+writes what the last timed step returned as DIR/all_ent.npy [N, O] and DIR/all_rel.npy [2R, O] (float32; 33 MB on the
+WN18RR shape), from inputs that are the same in every run with the same arguments.
+With `--full` the same run also reports, in sub-objects of that line:
   kernels / roofline   per-launch device time (HIP events on the launch stream) priced against BOTH roofs (SURVEY §8d
                        bytes / 8 TB/s, and the dense step's flops / MFMA peak), PMC traffic from profiles/;
   fb15k237             the same step on the FB15k-237 shape (BASELINE configs[2]) with its own kernels and CPU baseline;
@@ -14,9 +17,9 @@ The same run also reports, in sub-objects of the ONE JSON line printed by rank 0
                        over all ranks (RCCL) next to the same evaluation on ONE rank, so the N-GPU gain reads off one line;
   cpu_baseline         the oracle on this box's host cores (N = 1 only).
 
-`python bench.py --gpus N --steps K --warmup W`. For N > 1 either run it under torch.distributed.run (one rank per
-GPU) or plainly: without WORLD_SIZE in the environment it starts the N ranks itself (a torch.distributed.run child,
-before this process touches the GPU) and relays their output.
+`python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]`. For N > 1 either run it under
+torch.distributed.run (one rank per GPU) or plainly: without WORLD_SIZE in the environment it starts the N ranks itself
+(a torch.distributed.run child, before this process touches the GPU) and relays their output.
 """
 import argparse
 import hashlib
@@ -124,7 +127,8 @@ def make_model(pkg, shape, dev, layers, seed, zipf, D=100, O=200):
 def timed_steps(model, graph, steps, warmup, barrier, ramp_s=0.4):
     """W untimed warm-up steps, then exactly K timed ones between two barriers. Before the warm-up the same step runs
     untimed for `ramp_s` seconds: a fresh process otherwise measures the clock ramp and first-touch page faults of a
-    0.2 ms step instead of its steady state (--steps 20 --warmup 5 read 16 % slower than --steps 200)."""
+    0.2 ms step instead of its steady state (--steps 20 --warmup 5 read 16 % slower than --steps 200).
+    Returns the seconds of the K timed steps and what the last of them returned."""
     def step():
         with torch.no_grad():
             return model.encode(graph)
@@ -139,9 +143,9 @@ def timed_steps(model, graph, steps, warmup, barrier, ramp_s=0.4):
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = step()
     barrier()
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, out
 
 
 def main():
@@ -152,11 +156,16 @@ def main():
     ap.add_argument('--shape', default='wn18rr', choices=sorted(SHAPES))
     ap.add_argument('--layers', type=int, default=2)
     ap.add_argument('--zipf', type=float, default=0.0, help='tail endpoints ~ Zipf(a) instead of uniform (hub-heavy profile)')
+    ap.add_argument('--full', action='store_true', help='also measure every section besides the headline: kernels / roofline, '
+                    'train, eval, fb15k237, scale, cpu_baseline (the last four each have a --no-* option)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the last timed step\'s outputs as DIR/<name>.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-eval', action='store_true')
     ap.add_argument('--no-fb', action='store_true', help='skip the FB15k-237-shape sub-objects (configs[2], configs[3])')
     ap.add_argument('--no-scale', action='store_true', help='skip the "scale" object (partitioned encoder, configs[4] slice)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(args))                         # nothing above has initialised the GPU in this process
@@ -192,11 +201,14 @@ def main():
     D, O = 100, 200
     # every rank works on its own graph of the same shape (seed = rank): per-GPU work fixed -> weak scaling
     model, graph, params, edge_index, edge_attr = make_model(pkg, shape, dev, args.layers, rank, args.zipf)
-    elapsed = timed_steps(model, graph, args.steps, args.warmup, barrier)
+    elapsed, out = timed_steps(model, graph, args.steps, args.warmup, barrier)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    del out
 
     edges_per_step = args.layers * (2 * E + N)               # per rank
     value = world * edges_per_step * args.steps / elapsed
@@ -214,77 +226,85 @@ def main():
                                   'the RCCL exchange of the sharded scoring pass is timed in "eval"' % world},
     }
 
-    if rank == 0:
-        result.update(kernel_breakdown(pkg, model, graph, args.steps, shape, args.shape, args.layers, D, O))
-        result['train'] = guarded(lambda: train_breakdown(pkg, model, graph, shape, D, O))
-    if not args.no_eval:                                    # every rank takes part (collectives when W > 1)
-        if rank != 0:                                       # the sharded pass needs ONE graph on all ranks: rank 0's
-            del model, graph
-            model, graph, params, edge_index, edge_attr = make_model(pkg, shape, dev, args.layers, 0, args.zipf)
-        ev = eval_wallclock(pkg, model, graph, params, shape, dev, edge_index, edge_attr, world, rank)
+    if args.full:                                           # every section besides the headline (off by default)
         if rank == 0:
-            result['eval'] = ev
-    scale = {}
-    if not args.no_scale:                                   # every rank takes part
-        if rank != 0 and args.no_eval:                      # (the partitioned encoder needs ONE graph on all ranks: rank 0's)
-            del model, graph
-            model, graph, params, edge_index, edge_attr = make_model(pkg, shape, dev, args.layers, 0, args.zipf)
-        scale[args.shape] = guarded(lambda: encode_sharded_timing(pkg, model, graph, shape, dev, world, rank, dist, O))
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
-        result['cpu_baseline'] = cpu_baseline(model, edge_index, edge_attr, args.shape, args.layers, N, R, E, D, O, 20.0)
-        result['config']['gpu_over_cpu'] = value / result['cpu_baseline']['value']
+            result.update(kernel_breakdown(pkg, model, graph, args.steps, shape, args.shape, args.layers, D, O))
+            result['train'] = guarded(lambda: train_breakdown(pkg, model, graph, shape, D, O))
+        if not args.no_eval:                                    # every rank takes part (collectives when W > 1)
+            if rank != 0:                                       # the sharded pass needs ONE graph on all ranks: rank 0's
+                del model, graph
+                model, graph, params, edge_index, edge_attr = make_model(pkg, shape, dev, args.layers, 0, args.zipf)
+            ev = eval_wallclock(pkg, model, graph, params, shape, dev, edge_index, edge_attr, world, rank)
+            if rank == 0:
+                result['eval'] = ev
+        scale = {}
+        if not args.no_scale:                                   # every rank takes part
+            if rank != 0 and args.no_eval:                      # (the partitioned encoder needs ONE graph on all ranks: rank 0's)
+                del model, graph
+                model, graph, params, edge_index, edge_attr = make_model(pkg, shape, dev, args.layers, 0, args.zipf)
+            scale[args.shape] = guarded(lambda: encode_sharded_timing(pkg, model, graph, shape, dev, world, rank, dist, O))
+        if rank == 0 and not args.no_cpu_baseline and world == 1:
+            result['cpu_baseline'] = cpu_baseline(model, edge_index, edge_attr, args.shape, args.layers, N, R, E, D, O, 20.0)
+            result['config']['gpu_over_cpu'] = value / result['cpu_baseline']['value']
 
-    if rank == 0:
-        real = real_dataset_sections(pkg, args, dev, D, O)
-        if real:
-            result['real_datasets'] = real
-    if not args.no_fb and args.shape == 'wn18rr':
-        del model, graph
-        torch.cuda.empty_cache()
-        fb = fb_sections(pkg, args, dev, world, rank, dist, barrier, D, O)
         if rank == 0:
-            result['fb15k237'] = fb['step']
-            if 'eval' in fb:
-                result.setdefault('eval', {})['fb15k237'] = fb['eval']
-        if 'scale' in fb:
-            scale['fb15k237'] = fb['scale']
-    if not args.no_scale:
-        torch.cuda.empty_cache()
-        c5 = guarded(lambda: config5_slice(pkg, dev, world, rank, dist))
-        if dist is not None:          # outside the guarded body: every rank reaches this collective whatever happened inside
-            tt = torch.tensor([c5.get('layer_ms', -1.0)], dtype=torch.float64, device=dev)
-            lo = tt.clone()
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            dist.all_reduce(lo, op=dist.ReduceOp.MIN)
-            c5['layer_ms_max_over_ranks'] = float(tt.item())
-            if float(lo.item()) < 0:
-                c5['error_on_some_rank'] = True
-        else:
-            c5['layer_ms_max_over_ranks'] = c5.get('layer_ms')
-        scale['config5_slice'] = c5
-        if rank == 0:
-            scale['note'] = ('SURVEY 8(e) measured: "encode_sharded_s" = the destination-partitioned 2-layer encoder (each rank its '
-                             'work-balanced destination range and table shard, all-gather of every layer output included), same '
-                             'graph on all ranks: strong scaling against "one_rank_s" (rank 0 alone, same process, no '
-                             'collective); "config5_slice" = one rank\'s 1/8 of a 2M-entity / 20M-triple / dim-512 layer '
-                             '(BASELINE configs[4] scaled to what one box builds in seconds), every rank its own slice')
-            result['scale'] = scale
-    if rank == 0 and world > 1:
-        # What `value` is for N > 1: N independent replicas of the step (no data-path collective: linear by construction,
-        # "scaling": "replicas"). The quantities that DO exchange data over RCCL are lifted to the top level: strong-scaling
-        # speed-ups of the destination-partitioned encoder and of the entity-sharded evaluation (north_star's ">= 6x at 8 GPUs"
-        # is the last one) against rank 0 alone in the same run.
-        result['partitioned'] = {
-            'encoder_speedup_vs_one_rank': {k: v.get('speedup_vs_one_rank') for k, v in scale.items() if isinstance(v, dict) and 'speedup_vs_one_rank' in v},
-            'fb15k237_sharded_scoring_speedup_vs_one_rank': result.get('eval', {}).get('fb15k237', {}).get('speedup_vs_one_rank'),
-            'note': 'strong scaling, same graph on all ranks, collectives included; the headline "value" is replicas',
-        }
+            real = real_dataset_sections(pkg, args, dev, D, O)
+            if real:
+                result['real_datasets'] = real
+        if not args.no_fb and args.shape == 'wn18rr':
+            del model, graph
+            torch.cuda.empty_cache()
+            fb = fb_sections(pkg, args, dev, world, rank, dist, barrier, D, O)
+            if rank == 0:
+                result['fb15k237'] = fb['step']
+                if 'eval' in fb:
+                    result.setdefault('eval', {})['fb15k237'] = fb['eval']
+            if 'scale' in fb:
+                scale['fb15k237'] = fb['scale']
+        if not args.no_scale:
+            torch.cuda.empty_cache()
+            c5 = guarded(lambda: config5_slice(pkg, dev, world, rank, dist))
+            if dist is not None:          # outside the guarded body: every rank reaches this collective whatever happened inside
+                tt = torch.tensor([c5.get('layer_ms', -1.0)], dtype=torch.float64, device=dev)
+                lo = tt.clone()
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+                c5['layer_ms_max_over_ranks'] = float(tt.item())
+                if float(lo.item()) < 0:
+                    c5['error_on_some_rank'] = True
+            else:
+                c5['layer_ms_max_over_ranks'] = c5.get('layer_ms')
+            scale['config5_slice'] = c5
+            if rank == 0:
+                scale['note'] = ('SURVEY 8(e) measured: "encode_sharded_s" = the destination-partitioned 2-layer encoder (each rank its '
+                                 'work-balanced destination range and table shard, all-gather of every layer output included), same '
+                                 'graph on all ranks: strong scaling against "one_rank_s" (rank 0 alone, same process, no '
+                                 'collective); "config5_slice" = one rank\'s 1/8 of a 2M-entity / 20M-triple / dim-512 layer '
+                                 '(BASELINE configs[4] scaled to what one box builds in seconds), every rank its own slice')
+                result['scale'] = scale
+        if rank == 0 and world > 1:
+            # What `value` is for N > 1: N independent replicas of the step (no data-path collective: linear by construction,
+            # "scaling": "replicas"). The quantities that DO exchange data over RCCL are lifted to the top level: strong-scaling
+            # speed-ups of the destination-partitioned encoder and of the entity-sharded evaluation (north_star's ">= 6x at 8 GPUs"
+            # is the last one) against rank 0 alone in the same run.
+            result['partitioned'] = {
+                'encoder_speedup_vs_one_rank': {k: v.get('speedup_vs_one_rank') for k, v in scale.items() if isinstance(v, dict) and 'speedup_vs_one_rank' in v},
+                'fb15k237_sharded_scoring_speedup_vs_one_rank': result.get('eval', {}).get('fb15k237', {}).get('speedup_vs_one_rank'),
+                'note': 'strong scaling, same graph on all ranks, collectives included; the headline "value" is replicas',
+            }
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
         sys.stdout.flush()
         print(json.dumps(result), flush=True)
+
+
+def dump_outputs(d, out):
+    """The timed step's result as the caller of model.encode receives it: entity and relation embeddings."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in zip(('all_ent', 'all_rel'), out):
+        np.save(os.path.join(d, name + '.npy'), t.detach().float().cpu().numpy())
 
 
 def real_dataset_sections(pkg, args, dev, D, O):
@@ -304,7 +324,7 @@ def real_dataset_sections(pkg, args, dev, D, O):
         torch.manual_seed(0)
         model = pkg.MGCN(dl.num_entity, dl.num_relation, dl.num_edge, params).to(dev).eval()
         steps = max(args.steps, 20)
-        elapsed = timed_steps(model, dl.graph, steps, args.warmup, torch.cuda.synchronize, ramp_s=0.2)
+        elapsed, _ = timed_steps(model, dl.graph, steps, args.warmup, torch.cuda.synchronize, ramp_s=0.2)
         eps = args.layers * (2 * dl.num_edge + dl.num_entity)
         out[name] = {'N': dl.num_entity, 'R': dl.num_relation, 'E': dl.num_edge, 'ms_per_step': 1e3 * elapsed / steps,
                      'value': eps * steps / elapsed, 'unit': 'edges/s'}
@@ -433,7 +453,7 @@ def fb_sections(pkg, args, dev, world, rank, dist, barrier, D, O):
     model, graph, params, edge_index, edge_attr = make_model(pkg, shape, dev, args.layers, 0, zipf)
     out = {}
     steps = max(args.steps, 20)
-    elapsed = timed_steps(model, graph, steps, args.warmup, barrier, ramp_s=0.2)
+    elapsed, _ = timed_steps(model, graph, steps, args.warmup, barrier, ramp_s=0.2)
     if rank == 0:
         eps = args.layers * (2 * E + N)
         step = {'workload': 'fb15k237-shape synthetic graph (N=%d, R=%d, E=%d, Zipf(%.1f) tails, hubs split), %d-layer '

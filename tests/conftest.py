@@ -1,3 +1,4 @@
+import glob
 import importlib
 import os
 import sys
@@ -31,10 +32,20 @@ def oracle():
     return importlib.import_module('oracle.mgcn_oracle')
 
 
+class _Arrays(dict):
+    @property
+    def files(self):                     # the names, as np.load's NpzFile lists them
+        return list(self)
+
+
 class Golden(object):
     def __init__(self, name):
         self.name = name
-        self.z = np.load(os.path.join(GOLDEN, name + '.npz'))
+        # a case is stored as name.npz plus parts name.1.npz, name.2.npz, ... so that every fixture file stays under 1 MiB
+        self.z = _Arrays()
+        for path in [os.path.join(GOLDEN, name + '.npz')] + sorted(glob.glob(os.path.join(GOLDEN, name + '.*.npz'))):
+            with np.load(path) as z:
+                self.z.update((k, z[k]) for k in z.files)
         import json
         self.hp = json.loads(str(self.z['params_json']))
 

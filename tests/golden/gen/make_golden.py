@@ -18,6 +18,7 @@ outputs) and the Toy data files (fixture data the reference ships: data/Toy/*.tx
 
 Usage:  python tests/golden/gen/make_golden.py        (rewrites tests/golden/*.npz, data/*)
 """
+import glob
 import json
 import os
 import shutil
@@ -279,6 +280,28 @@ def run_case(root, name, params_over, scale_tables=1.0, full_model=True, seed=20
     return out
 
 
+PART_BYTES = 1000000      # raw array bytes per fixture file: every committed file stays under 1 MiB
+
+
+def split_into_parts(name):
+    """Store case `name` as name.npz, name.1.npz, name.2.npz, ... of at most PART_BYTES of arrays each (an array larger
+    than that gets a file of its own); tests/conftest.py merges the parts."""
+    path = os.path.join(GOLDEN, name + '.npz')
+    with np.load(path) as z:
+        arrays = {k: z[k] for k in z.files}
+    for old in glob.glob(os.path.join(GOLDEN, name + '.*.npz')):
+        os.remove(old)
+    parts, size = [{}], 0
+    for k, a in arrays.items():
+        if parts[-1] and size + a.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += a.nbytes
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(GOLDEN, name + ('.npz' if i == 0 else '.%d.npz' % i)), **part)
+
+
 def main():
     root = tempfile.mkdtemp(prefix='mgcn_golden_')
     data_out = os.path.join(GOLDEN, 'data')
@@ -314,6 +337,8 @@ def main():
         run_case(root, 'syn_b', dict(gcn_in_dim=20, gcn_out_dim=40, k_w=5, k_h=8, num_filter=8, kernel_size=3),
                  scale_tables=5.0)
         run_case(root, 'syn_c', dict(), full_model=False)
+        for name in ('toy_small', 'toy_d100', 'syn_a', 'syn_b', 'syn_c'):
+            split_into_parts(name)
 
         # untrained Toy, seed 2020, default dims, reference evaluate('test')
         os.chdir(root)

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_fb
 rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o t -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-eval --no-fb --no-scale --shape fb15k237 --zipf 1.1 > "$OUT/bench.json" 2> "$OUT/trace.log"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o t -- python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-eval --no-fb --no-scale --shape fb15k237 --zipf 1.1 > "$OUT/bench.json" 2> "$OUT/trace.log"
 find "$OUT" -name "*kernel_trace.csv" -delete
 python3 - <<'PY'
 import csv, glob

@@ -62,7 +62,7 @@ def main():
     fetch_scale = 512.0 * 1024 / max(cal_f) if cal_f else 2.0
     assert 0.9 < write_scale < 1.1 and 1.8 < fetch_scale < 2.2, (copy_name, max(cal_w), cal_f[:3])
     res = {'source': 'tools/profile_round.sh: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) '
-                     'on `python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-eval --no-fb --no-scale [--shape fb15k237 --zipf 1.1]`',
+                     'on `python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-eval --no-fb --no-scale [--shape fb15k237 --zipf 1.1]`',
            'calibration': {'copy_kernel': copy_name[:60], 'copy_512MiB_FETCH_SIZE_KiB': max(cal_f) if cal_f else None, 'copy_512MiB_WRITE_SIZE_KiB': max(cal_w) if cal_w else None,
                            'fetch_scale': fetch_scale, 'write_scale': write_scale,
                            'note': 'counters are KiB; FETCH_SIZE counts half of a wide streaming read on gfx950 (MI355X_MICROARCH.md, HBM)'},
