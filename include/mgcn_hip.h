@@ -368,6 +368,43 @@ int mgcn_label_rows(int32_t batch, const int64_t *qkey_dev, int64_t num_keys, co
                     const int64_t *ptr_dev, const int32_t *tails_dev, int64_t ent_row0, int64_t n_local, float hot,
                     float cold, float *out_dev, int64_t ldo, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (7) Filtered top-k link prediction: the k most likely tails of each query (h, r, ?), the job of model.py:177-179
+ * that the reference leaves to torch.topk over the [B, N] block. Head prediction is the inverse-relation query
+ * (t, r + R, ?), as the loader builds it (data_loader.py:80-96).
+ * mgcn_score_topk, for x [B, O] against the shard ent [n_local, O] / bias [n_local] whose rows are global ids
+ * [ent_row0, ent_row0 + n_local):
+ *   score  the f32 value mgcn_score_fwd produces for (b, n), bit for bit (the shard is scored through that launch, in
+ *          chunks of at most 2^18 rows into the workspace, so both arithmetic paths of (5) apply as there);
+ *   filter entity n is excluded when bit (n & 31) of mask[b, n >> 5] is set (the bits of mgcn_score_rank, built by
+ *          mgcn_filter_mask; ldm words per row); mask_dev == NULL excludes nothing;
+ *   order  score descending, then global id ascending (compared as f32 values: -0 == +0): the order of a stable
+ *          descending sort over the ids in ascending order, the tie rule of the rank counts (rank = 1 + gt + tl);
+ *   output out_score [B, ldo >= k] f32 and out_id [B, ldi >= k] int64 in that order; a row with fewer than k unfiltered
+ *          entities is padded at its end with score -inf and id -1.
+ * The result depends on nothing but the scores: not on the chunking, the launch geometry, the arrival order of the
+ * (integer) LDS atomics, or the sharding. Selection: every chunk is cut into segments of 4096 columns; one workgroup per
+ * (query, segment) keeps the segment's k best (radix select on an order-preserving 32-bit key with the id below it,
+ * bitonic sort of at most 1024 pairs in LDS), and one workgroup per query folds the segments' lists and the running
+ * list of the chunks before (the kernel of mgcn_topk_merge). A shard of one segment takes the single launch.
+ * Limits: 1 <= k <= 1024; batch, n_local, dim as mgcn_score_fwd; ent_row0 + n_local <= 2^31 - 1 (ids are int32 on
+ * the device). workspace_dev: mgcn_score_topk_workspace(batch, n_local, k) bytes, 16-byte aligned; with
+ * C = min(n_local, 2^18) rows per chunk and S = ceil(C / 4096) segments, it is
+ *   align256(4 B round4(C)) + align256(4 B (S + 1) k) + 8 B (S + 1) k   (align256: up to a multiple of 256)
+ * which does not grow with n_local past 2^18 rows (0 is returned for arguments outside the limits).
+ * mgcn_topk_merge: the top-k, in the order above, of `lists` candidate lists of k per query: list l of query b is
+ * in_score / in_id [b * ld_in + l * k, + k); entries with id < 0 are padding and are skipped, the others have distinct
+ * ids in [0, 2^31) (the lists need not be sorted). out [B, k] contiguous, padded as above; it must not overlap the input.
+ * Merging the lists of the shards of a table equals mgcn_score_topk over the whole table (dist.sharded_topk).
+ */
+size_t mgcn_score_topk_workspace(int32_t batch, int64_t n_local, int32_t k);
+int mgcn_score_topk(int32_t batch, int64_t n_local, int64_t ent_row0, int32_t dim, const float *x_dev, int64_t ldx,
+                    const float *ent_dev, int64_t lde, const float *bias_dev, const uint32_t *mask_dev, int64_t ldm,
+                    int32_t k, float *out_score_dev, int64_t ldo, int64_t *out_id_dev, int64_t ldi, void *workspace_dev,
+                    size_t workspace_bytes, void *stream);
+int mgcn_topk_merge(int32_t batch, int32_t lists, const float *in_score_dev, const int64_t *in_id_dev, int64_t ld_in,
+                    int32_t k, float *out_score_dev, int64_t *out_id_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,10 @@ _SIGNATURES = {
     'mgcn_score_bce_fwd': (ctypes.c_int, [_i32, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _f32, _f32, _f32, _ptr,
                                           _i64, _ptr, _ptr]),
     'mgcn_label_rows': (ctypes.c_int, [_i32, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _f32, _f32, _ptr, _i64, _ptr]),
+    'mgcn_score_topk_workspace': (ctypes.c_size_t, [_i32, _i64, _i32]),
+    'mgcn_score_topk': (ctypes.c_int, [_i32, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _i64,
+                                       _ptr, _i64, _ptr, ctypes.c_size_t, _ptr]),
+    'mgcn_topk_merge': (ctypes.c_int, [_i32, _i32, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _ptr]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
     'mgcn_ingest_count': (_i64, [_ptr, _i32]),
@@ -566,6 +570,54 @@ def score_rank(x, ent, bias, obj, target, label=None, ent_row0=0, counts=None, m
                                  _dev(mask, torch.int32, 'mask', True), mask.size(1) if mask is not None else 0,
                                  _dev(counts, torch.int64, 'counts'), _stream(x)), 'mgcn_score_rank')
     return counts
+
+
+TOPK_MAX = 1024
+
+
+def _check_k(k, what):
+    if not 1 <= int(k) <= TOPK_MAX:
+        raise NativeError('%s: k = %d outside [1, %d]' % (what, int(k), TOPK_MAX))
+    return int(k)
+
+
+def score_topk(x, ent, bias, k, mask=None, ent_row0=0):
+    """(7) The k best entities of this shard per query: (scores [B, k] f32, ids [B, k] int64 global ids), score
+    descending then id ascending, each score the f32 value of score_fwd; entities whose bit is set in the bit-packed
+    `mask` [B, >= ceil(n/32)] int32 of filter_mask() are excluded; a row with fewer than k entities left ends in
+    (-inf, -1) padding (see mgcn_score_topk)."""
+    B, n, O = _score_args(x, ent, bias)
+    k = _check_k(k, 'score_topk')
+    if mask is not None and (mask.dim() != 2 or mask.size(0) != B or mask.size(1) < (n + 31) // 32 or not mask.is_contiguous()):
+        raise NativeError('score_topk: mask must be contiguous (%d, >= %d)' % (B, (n + 31) // 32))
+    _same_device(x, ent, bias, mask)
+    scores = torch.empty((B, k), dtype=torch.float32, device=x.device)
+    ids = torch.empty((B, k), dtype=torch.int64, device=x.device)
+    nbytes = lib().mgcn_score_topk_workspace(B, n, k)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)    # the caching allocator's memory
+    _check(lib().mgcn_score_topk(B, n, int(ent_row0), O, _dev(x, torch.float32, 'x'), _ld(x),
+                                 _dev(ent, torch.float32, 'ent'), _ld(ent), _dev(bias, torch.float32, 'bias'),
+                                 _dev(mask, torch.int32, 'mask', True), mask.size(1) if mask is not None else 0, k,
+                                 _dev(scores, torch.float32, 'scores'), k, _dev(ids, torch.int64, 'ids'), k,
+                                 _dev(ws, torch.uint8, 'workspace'), nbytes, _stream(x)), 'mgcn_score_topk')
+    return scores, ids
+
+
+def topk_merge(scores, ids, k):
+    """(7) The top-k of candidate lists laid side by side: scores [B, L] f32, ids [B, L] int64 with L a multiple of k
+    (L / k lists of k, id -1 = padding) -> (scores [B, k], ids [B, k]) in the order of score_topk (see mgcn_topk_merge)."""
+    k = _check_k(k, 'topk_merge')
+    _same_device(scores, ids)
+    if scores.dim() != 2 or ids.shape != scores.shape or scores.size(1) % k != 0:
+        raise NativeError('topk_merge: scores %s / ids %s must be equal [B, lists * %d]' % (tuple(scores.shape), tuple(ids.shape), k))
+    B, lists = scores.size(0), scores.size(1) // k
+    scores, ids = scores.contiguous(), ids.contiguous()
+    out_s = torch.empty((B, k), dtype=torch.float32, device=scores.device)
+    out_i = torch.empty((B, k), dtype=torch.int64, device=scores.device)
+    _check(lib().mgcn_topk_merge(B, lists, _dev(scores, torch.float32, 'scores'), _dev(ids, torch.int64, 'ids'),
+                                 scores.size(1), k, _dev(out_s, torch.float32, 'out scores'),
+                                 _dev(out_i, torch.int64, 'out ids'), _stream(scores)), 'mgcn_topk_merge')
+    return out_s, out_i
 
 
 def filter_mask(qkey, keys, ptr, tails, n_local, ent_row0=0, out=None):

@@ -111,6 +111,41 @@ def sharded_rank_counts(x, qkey, obj, ent_shard, bias_shard, row0, filt, group=N
     return counts[rank * B:(rank + 1) * B], target[rank * B:(rank + 1) * B]
 
 
+def _topk_all(x, qkey, ent_shard, bias_shard, row0, k, filt, group, kernels):
+    """sharded_topk for every rank's queries: (scores [W*B, k], ids [W*B, k]) in rank order, the same on every rank."""
+    world = dist.get_world_size(group) if (group is not None or dist.is_initialized()) else 1
+    if world > 1:
+        x_all = _gather(x, group, world)
+        key_all = _gather(qkey, group, world) if filt is not None else None
+    else:
+        x_all, key_all = x.contiguous(), qkey
+    mask = kernels.filter_mask(key_all, filt.keys, filt.ptr, filt.tails, ent_shard.size(0), ent_row0=row0) \
+        if filt is not None else None
+    scores, ids = kernels.score_topk(x_all, ent_shard, bias_shard, k, mask=mask, ent_row0=row0)
+    if world == 1:
+        return scores, ids
+    total = x_all.size(0)
+    # every rank's [W*B, k] lists -> [W*B, W*k]: query b's candidates from every shard side by side, then one merge
+    s_all, i_all = _gather(scores, group, world), _gather(ids, group, world)
+    s_all = s_all.view(world, total, k).transpose(0, 1).reshape(total, world * k)
+    i_all = i_all.view(world, total, k).transpose(0, 1).reshape(total, world * k)
+    return kernels.topk_merge(s_all, i_all, k)
+
+
+def sharded_topk(x, qkey, ent_shard, bias_shard, row0, k, filt=None, group=None, kernels=_native):
+    """Filtered top-k of this rank's B queries against the WHOLE entity table, which is sharded by rows (the counterpart
+    of sharded_rank_counts): x [B, O] query embeddings (ConvE trunk output), qkey [B] filter keys (filt.query_keys;
+    ignored without `filt`), ent_shard / bias_shard the rows [row0, row0 + n_local). The exchange: one all-gather of x
+    and the keys, the local top-k over the shard with global ids, one all-gather of the [W*B, k] candidate lists, and
+    a merge. Returns (scores [B, k], ids [B, k]) equal to the unsharded result (the order is total). All ranks pass the
+    same B and k, and all or none pass `filt`."""
+    world = dist.get_world_size(group) if (group is not None or dist.is_initialized()) else 1
+    rank = dist.get_rank(group) if world > 1 else 0
+    B = x.size(0)
+    scores, ids = _topk_all(x, qkey, ent_shard, bias_shard, row0, k, filt, group, kernels)
+    return scores[rank * B:(rank + 1) * B], ids[rank * B:(rank + 1) * B]
+
+
 def xavier_rows(edge_ids, num_rows, dim, seed, device, chunk=1 << 16):
     """Rows `edge_ids` (reference edge ids, int64) of a [num_rows, dim] xavier-uniform table (utils.get_param's
     initialiser, utils.py:113-118) that is DEFINED chunk-wise: rows [c * chunk, (c + 1) * chunk) come from a generator
@@ -334,3 +369,35 @@ def evaluate_sharded(model, graph, queries, filt, batch_size=None, group=None, t
     for k in (1, 3, 10):
         res['hits@%d' % k] = sums[2 + k] / count
     return res
+
+
+@torch.no_grad()
+def predict_topk_sharded(model, graph, queries, k, filt=None, group=None, trunk_chunk=2048, shard_encoder=False):
+    """Filtered top-k tails of `queries` ([Q, 2] int64: subject, relation id; heads through the inverse relation r + R)
+    with the entity table sharded over the group, batched as evaluate_sharded: rank r takes the query range
+    [c_r, c_{r+1}) padded to a common length, the ConvE trunk runs over it in chunks of `trunk_chunk`, and the exchange
+    happens once (sharded_topk). `filt`: a FilterIndex on the device, or None for unfiltered lists. Returns
+    (ids [Q, k] int64, scores [Q, k] f32) for ALL queries on every rank, equal to model.predict_topk at world size 1."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if world > 1 else 0
+    model.eval()
+    all_ent, all_rel = encode_sharded(model, graph, group) if shard_encoder else model.encode(graph)
+    N = all_ent.size(0)
+    b = shard_bounds(N, world)
+    ent_shard = all_ent[b[rank]:b[rank + 1]].contiguous()
+    bias_shard = model.conv2.bias[b[rank]:b[rank + 1]].contiguous()
+    dev = all_ent.device
+    Q = queries.size(0)
+    per = (Q + world - 1) // world
+    lo, hi = min(rank * per, Q), min((rank + 1) * per, Q)
+    q = torch.zeros((per, 2), dtype=torch.int64, device=dev)   # padding rows are harmless queries, dropped below
+    q[:hi - lo] = queries[lo:hi, :2].to(dev)
+    sub, rel = q[:, 0], q[:, 1]
+    x = torch.cat([model.conv2.trunk(all_ent.index_select(0, sub[i:i + trunk_chunk]),
+                                     all_rel.index_select(0, rel[i:i + trunk_chunk]))
+                   for i in range(0, per, trunk_chunk)], dim=0) if per > 0 else all_ent.new_zeros((0, all_ent.size(1)))
+    keys = filt.query_keys(sub, rel) if filt is not None else sub
+    if per == 0:
+        return (torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=torch.float32, device=dev))
+    scores, ids = _topk_all(x, keys, ent_shard, bias_shard, b[rank], k, filt, group, _native)
+    return ids[:Q], scores[:Q]

@@ -601,3 +601,27 @@ class MGCN(nn.Module):
             mask = _native.filter_mask(f.query_keys(src, rel), f.keys, f.ptr, f.tails, ent.size(0))
             counts = _native.score_rank(x, ent, self.conv2.bias, obj, target, mask=mask)
         return counts, target
+
+    @torch.no_grad()
+    def predict_topk(self, src, rel, data, k=10, filter_index=None):
+        """Link prediction: the k most likely tails of the queries (src, rel, ?) as (ids [B, k] int64, scores [B, k] f32),
+        score descending and, among equal scores, lower entity id first (the tie rule of rank_counts). The scores are
+        those of forward(src, rel, data), bit for bit. `filter_index` (a dist.FilterIndex, e.g. DataLoader.filter_index()
+        or train_index(), on the device) excludes the known tails of each (src, rel); a row with fewer than k entities
+        left ends in id -1 / score -inf. Heads are predicted with the inverse-relation query: the heads of (?, r, t)
+        are the tails of (t, r + R), R = number of relations, as DataLoader.eval_queries builds them. Runs the model in
+        eval mode (restored afterwards) through encode(), so the cached encoder and its hipGraph replay apply."""
+        was_training = self.training
+        self.eval()
+        try:
+            all_ent, all_rel = self.encode(data)
+            x = self.conv2.trunk(torch.index_select(all_ent, 0, src), torch.index_select(all_rel, 0, rel))
+            ent = all_ent.contiguous()
+            mask = None
+            if filter_index is not None:
+                f = filter_index
+                mask = _native.filter_mask(f.query_keys(src, rel), f.keys, f.ptr, f.tails, ent.size(0))
+            scores, ids = _native.score_topk(x, ent, self.conv2.bias, k, mask=mask)
+        finally:
+            self.train(was_training)
+        return ids, scores
