@@ -182,6 +182,34 @@ int mgcn_aggregate_bwd(int64_t num_nodes, int64_t num_edges_half, int32_t dim, i
                        float *workspace_dev, size_t workspace_bytes, void *stream);
 size_t mgcn_aggregate_bwd_workspace(int64_t num_edges_half, int32_t dim, int32_t num_rel_rows, int64_t num_hub_chunks);
 
+/* (3s) Aggregation backward of ONE destination range [node_begin, node_end) from its table shard — one rank's share of the
+ * training step of the destination partition (kgc-gcn_amd/dist.py train_step_sharded). The shard is the table of (2):
+ * rows_in in-half rows, then rows_out out-half rows, then rows_hub hub rows, row r of a region at slot r + ee_sub_{region}.
+ * g_dev holds the gradient of the range's rows only (row 0 = node_begin, first 2D columns used). Outputs:
+ *   gee [rows, D]   = (3)'s gee of the shard's slots, in shard order (bit-identical to (3)'s rows of those slots);
+ *   grel [num_rel_rows, D] = (3)'s sum restricted to the shard's slots (a partial: the ranks' grel add up to (3)'s);
+ *   gx [N, D] (optional) = for every node, (3)'s by-source sum restricted to the shard's slots (zero rows where the shard has
+ *                          none; a partial: the ranks' gx add up to (3)'s).
+ * Index lists (built once per graph and range, kgc-gcn_amd/graph.py GraphCSR.shard_backward_index; they only cover the shard's
+ * rows, no rank walks the whole graph):
+ *   type_ptr [num_rel_rows + 1], type_rows [rows]: the shard's rows grouped by relation row, ascending (slot order);
+ *   src_ptr [2N + 1], src_rows [rows]: entries [src_ptr[2s + h], src_ptr[2s + h + 1]) = the rows whose slot lies in half h and
+ *     leaves node s, ordered by the slot of the reverse edge (the order in which (3) walks s's destination runs of half 1 - h);
+ *   src_chunks [num_hub_chunks][4]: for every hub chunk c of the graph (include (1); hubinfo of the whole graph), {first, end)
+ *     entries of src_rows whose reverse slot lies in chunk c, first chunk of its hub, chunk count of its hub}.
+ * grel uses (3)'s one-pass gee + by-type chunk sums over type_rows and its final fold; gx walks src_rows per (node, half) and takes
+ * a hub's chunk sums through (3)'s fold. Sums in fixed orders, no float atomics. With the whole graph as the range (one rank)
+ * every output is bit-identical to (3)'s. workspace: mgcn_aggregate_bwd_shard_workspace bytes, 16-byte aligned. */
+size_t mgcn_aggregate_bwd_shard_workspace(int64_t shard_rows, int32_t dim, int32_t num_rel_rows, int64_t num_hub_chunks);
+int mgcn_aggregate_bwd_shard(int64_t num_nodes, int64_t num_edges_half, int32_t dim, int32_t num_rel_rows,
+                             const mgcn_edge_rec *rec_dev, const int32_t *slot_dst_dev, int64_t node_begin, int64_t node_end,
+                             int64_t rows_in, int64_t rows_out, int64_t rows_hub, int64_t ee_sub_in, int64_t ee_sub_out,
+                             int64_t ee_sub_hub, const int32_t *src_ptr_dev, const int32_t *src_rows_dev,
+                             const int32_t *hubinfo_dev, const int32_t *src_chunks_dev, int64_t num_hub_chunks,
+                             const int32_t *type_ptr_dev, const int32_t *type_rows_dev, const float *x_dev, int64_t ldx,
+                             const float *rel_dev, const float *ee_dev, const float *g_dev, int64_t ldg, float *gx_dev,
+                             float *gee_dev, float *grel_dev, float *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * (4) Dense step + epilogue (f32 MFMA, exact f32). Replaces model.py:116 (moved after the sum) and
  * model.py:103-106 in eval mode:
@@ -290,6 +318,33 @@ int mgcn_bn_tanh_train_bwd(int64_t num_rows, int32_t dim_out, const float *z_dev
                            const float *save_mean_dev, const float *save_rstd_dev, const float *gamma_dev, float *gz_dev,
                            float *gu_dev, float *ggamma_dev, float *gbeta_dev, float *workspace_dev, size_t workspace_bytes,
                            void *stream);
+
+/* (4s) (4t) split into stages around an exchange, for the destination partition's training step: each rank holds num_rows rows of
+ * the layer and reduces them in the same fixed 128-row blocks as (4t); between the stages the caller gathers every rank's per-block
+ * partials ([ceil(num_rows / 128), O] each) and passes them all, rank after rank, as num_blocks rows; total_rows = the rows of all
+ * ranks. The folds add the blocks in the order given, so every rank computes the same statistics; when every rank's first row is a
+ * multiple of 128 (always with one rank) they are bit-identical to (4t)'s.
+ *   stage_sum:    z (as (4t)) and its per-block column sums -> part [nblk, O];
+ *   stage_center: mean = (sum of the blocks) / total_rows, then the per-block sums of (z - mean)^2 -> part [nblk, O];
+ *   stage_finish: rstd and the running statistics from the blocks of stage_center, then y = tanh(BN(z));
+ *   bwd_stage_sums:  per-block sums of g_pre = gy * (1 - y^2) and of g_pre * xhat -> g_part, gx_part [nblk, O];
+ *   bwd_stage_apply: gbeta / ggamma = the folds of all ranks' blocks, then gz and gu = gz / 3 for the rank's rows.
+ * num_rows may be 0 (a rank without rows contributes no blocks). */
+int mgcn_bn_train_stage_sum(int64_t num_rows, int32_t dim_out, const float *u_in_dev, const float *u_out_dev,
+                            const float *u_loop_dev, int64_t ldu, const float *bias_dev, float *z_dev, float *part_dev, void *stream);
+int mgcn_bn_train_stage_center(int64_t num_rows, int32_t dim_out, const float *z_dev, const float *sum_parts_dev, int64_t num_blocks,
+                               int64_t total_rows, float *mean_dev, float *part_dev, void *stream);
+int mgcn_bn_train_stage_finish(int64_t num_rows, int32_t dim_out, const float *z_dev, const float *sq_parts_dev, int64_t num_blocks,
+                               int64_t total_rows, const float *mean_dev, const float *gamma_dev, const float *beta_dev,
+                               float *running_mean_dev, float *running_var_dev, float momentum, float eps, float *rstd_dev,
+                               float *y_dev, void *stream);
+int mgcn_bn_train_bwd_stage_sums(int64_t num_rows, int32_t dim_out, const float *z_dev, const float *y_dev, const float *gy_dev,
+                                 const float *save_mean_dev, const float *save_rstd_dev, float *g_part_dev, float *gx_part_dev,
+                                 void *stream);
+int mgcn_bn_train_bwd_stage_apply(int64_t num_rows, int32_t dim_out, const float *z_dev, const float *y_dev, const float *gy_dev,
+                                  const float *save_mean_dev, const float *save_rstd_dev, const float *gamma_dev,
+                                  const float *g_parts_dev, const float *gx_parts_dev, int64_t num_blocks, int64_t total_rows,
+                                  float *gz_dev, float *gu_dev, float *ggamma_dev, float *gbeta_dev, void *stream);
 
 /* C[M, N] = A^T B for A [K, M] (lda), B [K, N] (ldb): the weight gradient of model.py:116, dW = aggregate^T g (K = number of
  * nodes). Split over K (fixed ranges, partial products added in range order: reproducible), exact-f32 MFMA. M <= 208, N <= 256,

@@ -27,6 +27,14 @@ _SIGNATURES = {
     'mgcn_aggregate_bwd': (ctypes.c_int, [_i64, _i64, _i32, _i32] + [_ptr] * 6 + [_i64, _ptr, _ptr] +
                            [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_aggregate_bwd_workspace': (ctypes.c_size_t, [_i64, _i32, _i32, _i64]),
+    'mgcn_aggregate_bwd_shard': (ctypes.c_int, [_i64, _i64, _i32, _i32, _ptr, _ptr] + [_i64] * 8 + [_ptr] * 4 + [_i64, _ptr, _ptr,
+                                                _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
+    'mgcn_aggregate_bwd_shard_workspace': (ctypes.c_size_t, [_i64, _i32, _i32, _i64]),
+    'mgcn_bn_train_stage_sum': (ctypes.c_int, [_i64, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
+    'mgcn_bn_train_stage_center': (ctypes.c_int, [_i64, _i32, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr]),
+    'mgcn_bn_train_stage_finish': (ctypes.c_int, [_i64, _i32, _ptr, _ptr, _i64, _i64] + [_ptr] * 5 + [_f32, _f32, _ptr, _ptr, _ptr]),
+    'mgcn_bn_train_bwd_stage_sums': (ctypes.c_int, [_i64, _i32] + [_ptr] * 8),
+    'mgcn_bn_train_bwd_stage_apply': (ctypes.c_int, [_i64, _i32] + [_ptr] * 8 + [_i64, _i64] + [_ptr] * 5),
     'mgcn_dense_bn_tanh_fwd': (ctypes.c_int, [_i64, _i32, _i32, _ptr, _i64] + [_ptr] * 6 + [_f32, _ptr, _i64, _ptr]),
     'mgcn_layer_fwd_fused': (ctypes.c_int, [_i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
                                             _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i64, _i64, _i64,
@@ -287,6 +295,49 @@ def aggregate_bwd(csr, x, rel, ee, g, want_gx=True, want_gee=True, want_grel=Tru
     return gx, gee, grel
 
 
+def aggregate_bwd_shard(csr, x, rel, ee, g, node_range, want_gx=True):
+    """(3s) aggregate_bwd for the destinations [n0, n1) of one rank from its table shard `ee` (slot order, the rows of
+    GraphCSR.edge_table_shard); `g` [n1 - n0, >= 2D] holds the gradient of those rows only. Returns (gx [N, D] partial or None,
+    gee [shard rows, D] complete, grel [num_rel_rows, D] partial): summed over the ranks of a partition, gx / grel are
+    aggregate_bwd's (bit-identical with one range covering the graph)."""
+    N, E, D = csr.num_nodes, csr.num_edges_half, x.size(1)
+    n0, n1 = int(node_range[0]), int(node_range[1])
+    _same_device(csr.rowptr, x, rel, ee, g)
+    if not csr.has_backward:
+        raise NativeError('aggregate_bwd_shard: graph was prepared without the backward indices')
+    if want_gx and not csr.mirrored:
+        raise NativeError('aggregate_bwd_shard: the edge list is not mirror-symmetric: no gradient w.r.t. the layer input')
+    if not 0 <= n0 <= n1 <= N:
+        raise NativeError('aggregate_bwd_shard: node range (%d, %d) outside [0, %d]' % (n0, n1, N))
+    if x.size(0) != N or tuple(rel.shape) != (csr.num_rel_rows, D) or not rel.is_contiguous():
+        raise NativeError('aggregate_bwd_shard: x / rel do not match the graph')
+    rows = csr.shard_slot_counts(n0, n1)
+    if ee is None or tuple(ee.shape) != (sum(rows), D) or not ee.is_contiguous():
+        raise NativeError('aggregate_bwd_shard: per-edge shard %s does not match destinations [%d, %d) (%d rows)'
+                          % (None if ee is None else tuple(ee.shape), n0, n1, sum(rows)))
+    if g.dim() != 2 or g.size(0) != n1 - n0 or g.size(1) < 2 * D:
+        raise NativeError('aggregate_bwd_shard: g %s must be [%d, >= %d]' % (tuple(g.shape), n1 - n0, 2 * D))
+    idx = csr.shard_backward_index(n0, n1)
+    sub = csr.shard_ee_sub(n0, n1)
+    gx = torch.empty((N, D), dtype=torch.float32, device=x.device) if want_gx else None
+    gee = torch.empty((sum(rows), D), dtype=torch.float32, device=x.device)
+    grel = torch.empty((csr.num_rel_rows, D), dtype=torch.float32, device=x.device)
+    hubs = csr.num_chunks > 0
+    ws_bytes = lib().mgcn_aggregate_bwd_shard_workspace(sum(rows), D, csr.num_rel_rows, csr.num_chunks)
+    ws = torch.empty(max(ws_bytes // 4, 4), dtype=torch.float32, device=x.device)
+    nz = lambda t, dtype, what: _dev(t, dtype, what) if t.numel() > 0 else None     # (an empty shard: nothing is read or written)
+    _check(lib().mgcn_aggregate_bwd_shard(
+        N, E, D, csr.num_rel_rows, _dev(csr.rec, torch.int32, 'rec'), _dev(csr.slot_dst, torch.int32, 'slot_dst'), n0, n1,
+        rows[0], rows[1], rows[2], sub[0], sub[1], sub[2], _dev(idx['src_ptr'], torch.int32, 'src_ptr'),
+        nz(idx['src_rows'], torch.int32, 'src_rows'), _dev(csr.hubinfo, torch.int32, 'hubinfo') if hubs else None,
+        _dev(idx['src_chunks'], torch.int32, 'src_chunks') if hubs else None, csr.num_chunks,
+        _dev(idx['type_ptr'], torch.int32, 'type_ptr'), nz(idx['type_rows'], torch.int32, 'type_rows'), _dev(x, torch.float32, 'x'), _ld(x),
+        _dev(rel, torch.float32, 'rel'), nz(ee, torch.float32, 'ee'), nz(g, torch.float32, 'g'), _ld(g) if g.numel() > 0 else 2 * D,
+        _dev(gx, torch.float32, 'gx', True), nz(gee, torch.float32, 'gee'), _dev(grel, torch.float32, 'grel'), _dev(ws, torch.float32, 'ws'),
+        ws_bytes, _stream(x)), 'mgcn_aggregate_bwd_shard')
+    return gx, gee, grel
+
+
 def dense_bn_tanh_fwd(a, w_cat, bias, bn_mean, bn_var, bn_gamma, bn_beta, eps, out):
     """(4) out = tanh(BN_eval((A @ w_cat) / 3 + bias)), w_cat [3D, O] = W_in, W_out, W_loop stacked by rows."""
     N, O = a.size(0), w_cat.size(1)
@@ -517,6 +568,105 @@ def bn_tanh_train_bwd(z, y, gy, mean, rstd, gamma):
     return gz, gu, gg, gb
 
 
+BN_BLOCK = 128       # rows per partial-sum block of the training epilogue (csrc/train_layer.hip)
+
+
+def bn_blocks(rows):
+    return (int(rows) + BN_BLOCK - 1) // BN_BLOCK
+
+
+def _bn_parts(parts, O, what):
+    if parts.dim() != 2 or parts.size(0) < 1 or parts.size(1) != O or not parts.is_contiguous():
+        raise NativeError('%s: block partials must be contiguous [blocks >= 1, %d]' % (what, O))
+    return parts.size(0)
+
+
+def bn_train_stage_sum(u_in, u_out, u_loop, bias):
+    """(4s) stage 1: z = (u_in + u_out + u_loop) / 3 (+ bias) of this rank's rows and its per-block column sums [bn_blocks(n), O]."""
+    n, O = u_in.shape
+    _same_device(u_in, u_out, u_loop, bias)
+    for t in (u_in, u_out, u_loop):
+        if tuple(t.shape) != (n, O) or (n > 0 and (t.stride(1) != 1 or t.stride(0) != u_in.stride(0))):
+            raise NativeError('bn_train_stage_sum: the three products must be [N, O] with the same row stride')
+    if bias is not None and bias.numel() != O:
+        raise NativeError('bn_train_stage_sum: bias must have %d elements' % O)
+    z = torch.empty((n, O), dtype=torch.float32, device=u_in.device)
+    part = torch.empty((bn_blocks(n), O), dtype=torch.float32, device=u_in.device)
+    if n > 0:
+        _check(lib().mgcn_bn_train_stage_sum(n, O, _dev(u_in, torch.float32, 'u_in'), _dev(u_out, torch.float32, 'u_out'),
+                                             _dev(u_loop, torch.float32, 'u_loop'), u_in.stride(0), _dev(bias, torch.float32, 'bias', True),
+                                             _dev(z, torch.float32, 'z'), _dev(part, torch.float32, 'part'), _stream(u_in)),
+               'mgcn_bn_train_stage_sum')
+    return z, part
+
+
+def bn_train_stage_center(z, sum_parts, total_rows):
+    """(4s) stage 2: mean [O] from ALL ranks' stage-1 blocks (rank, then block order) and this rank's blocks of (z - mean)^2."""
+    n, O = z.shape
+    _same_device(z, sum_parts)
+    nb = _bn_parts(sum_parts, O, 'bn_train_stage_center')
+    mean = torch.empty(O, dtype=torch.float32, device=z.device)
+    part = torch.empty((bn_blocks(n), O), dtype=torch.float32, device=z.device)
+    _check(lib().mgcn_bn_train_stage_center(n, O, _dev(z, torch.float32, 'z', n == 0), _dev(sum_parts, torch.float32, 'sum_parts'), nb,
+                                            int(total_rows), _dev(mean, torch.float32, 'mean'),
+                                            _dev(part, torch.float32, 'part') if n > 0 else None, _stream(sum_parts)),
+           'mgcn_bn_train_stage_center')
+    return mean, part
+
+
+def bn_train_stage_finish(z, sq_parts, total_rows, mean, gamma, beta, running_mean, running_var, momentum, eps):
+    """(4s) stage 3: rstd [O] (and the running statistics, in place) from ALL ranks' stage-2 blocks, then y = tanh(BN(z))."""
+    n, O = z.shape
+    _same_device(z, sq_parts, mean, gamma, beta, running_mean, running_var)
+    nb = _bn_parts(sq_parts, O, 'bn_train_stage_finish')
+    for v in (mean, gamma, beta) + tuple(t for t in (running_mean, running_var) if t is not None):
+        if v.numel() != O or not v.is_contiguous():
+            raise NativeError('bn_train_stage_finish: per-column vectors must be contiguous with %d elements' % O)
+    y = torch.empty_like(z)
+    rstd = torch.empty(O, dtype=torch.float32, device=z.device)
+    _check(lib().mgcn_bn_train_stage_finish(
+        n, O, _dev(z, torch.float32, 'z', n == 0), _dev(sq_parts, torch.float32, 'sq_parts'), nb, int(total_rows),
+        _dev(mean, torch.float32, 'mean'), _dev(gamma, torch.float32, 'gamma'), _dev(beta, torch.float32, 'beta'),
+        _dev(running_mean, torch.float32, 'running_mean', True), _dev(running_var, torch.float32, 'running_var', True),
+        float(momentum), float(eps), _dev(rstd, torch.float32, 'rstd'), _dev(y, torch.float32, 'y') if n > 0 else None,
+        _stream(sq_parts)), 'mgcn_bn_train_stage_finish')
+    return y, rstd
+
+
+def bn_train_bwd_stage_sums(z, y, gy, mean, rstd):
+    """(4s) backward stage 1: this rank's per-block sums of g_pre and g_pre * xhat, as one [2, bn_blocks(n), O] tensor."""
+    n, O = z.shape
+    _same_device(z, y, gy, mean, rstd)
+    gy = gy.contiguous()
+    part = torch.empty((2, bn_blocks(n), O), dtype=torch.float32, device=z.device)
+    if n > 0:
+        _check(lib().mgcn_bn_train_bwd_stage_sums(n, O, _dev(z, torch.float32, 'z'), _dev(y, torch.float32, 'y'),
+                                                  _dev(gy, torch.float32, 'gy'), _dev(mean, torch.float32, 'mean'),
+                                                  _dev(rstd, torch.float32, 'rstd'), _dev(part[0], torch.float32, 'g_part'),
+                                                  _dev(part[1], torch.float32, 'gx_part'), _stream(z)), 'mgcn_bn_train_bwd_stage_sums')
+    return part
+
+
+def bn_train_bwd_stage_apply(z, y, gy, mean, rstd, gamma, g_parts, gx_parts, total_rows):
+    """(4s) backward stage 2: (gz, gu = gz / 3, ggamma, gbeta) with ggamma / gbeta folded from ALL ranks' blocks."""
+    n, O = z.shape
+    _same_device(z, y, gy, mean, rstd, gamma, g_parts, gx_parts)
+    nb = _bn_parts(g_parts, O, 'bn_train_bwd_stage_apply')
+    if _bn_parts(gx_parts, O, 'bn_train_bwd_stage_apply') != nb:
+        raise NativeError('bn_train_bwd_stage_apply: g / gx partials differ in blocks')
+    gy = gy.contiguous()
+    gz, gu = torch.empty_like(z), torch.empty_like(z)
+    gg, gb = torch.empty_like(mean), torch.empty_like(mean)
+    live = n > 0
+    _check(lib().mgcn_bn_train_bwd_stage_apply(
+        n, O, _dev(z, torch.float32, 'z', not live), _dev(y, torch.float32, 'y', not live), _dev(gy, torch.float32, 'gy', not live),
+        _dev(mean, torch.float32, 'mean'), _dev(rstd, torch.float32, 'rstd'), _dev(gamma, torch.float32, 'gamma'),
+        _dev(g_parts, torch.float32, 'g_parts'), _dev(gx_parts, torch.float32, 'gx_parts'), nb, int(total_rows),
+        _dev(gz, torch.float32, 'gz') if live else None, _dev(gu, torch.float32, 'gu') if live else None,
+        _dev(gg, torch.float32, 'ggamma'), _dev(gb, torch.float32, 'gbeta'), _stream(mean)), 'mgcn_bn_train_bwd_stage_apply')
+    return gz, gu, gg, gb
+
+
 def _score_args(x, ent, bias):
     _same_device(x, ent, bias)
     if x.dim() != 2 or ent.dim() != 2 or x.size(1) != ent.size(1) or bias.numel() != ent.size(0):
@@ -651,16 +801,18 @@ def score_bce_supported(x, ent):
             and x.data_ptr() % 16 == 0 and ent.data_ptr() % 16 == 0)
 
 
-def score_bce_fwd(x, ent, bias, mask, hot, cold):
+def score_bce_fwd(x, ent, bias, mask, hot, cold, num_entities=None):
     """(N3) One launch: returns (loss [] f32, G [n, B] f32 = d loss / d logits, entity-major) for the mean BCE of
-    sigmoid(x @ ent^T + bias) against targets `hot` at the mask's bits, `cold` elsewhere (see mgcn_score_bce_fwd)."""
+    sigmoid(x @ ent^T + bias) against targets `hot` at the mask's bits, `cold` elsewhere (see mgcn_score_bce_fwd).
+    `num_entities`: the mean's count of entities when `ent` is one rank's row shard of a larger table (default: its rows);
+    the ranks' losses and gradients then add up to the whole table's."""
     B, n, O = _score_args(x, ent, bias)
     if mask.dim() != 2 or mask.size(0) != B or mask.size(1) < (n + 31) // 32 or not mask.is_contiguous():
         raise NativeError('score_bce_fwd: mask must be contiguous (%d, >= %d)' % (B, (n + 31) // 32))
     _same_device(x, ent, bias, mask)
     g = torch.empty((n, B), dtype=torch.float32, device=x.device)
     parts = torch.empty(int(lib().mgcn_score_bce_partials(B, n)), dtype=torch.float32, device=x.device)
-    inv = 1.0 / (float(B) * float(n))
+    inv = 1.0 / (float(B) * float(n if num_entities is None else int(num_entities)))
     _check(lib().mgcn_score_bce_fwd(B, n, O, _dev(x, torch.float32, 'x'), _ld(x), _dev(ent, torch.float32, 'ent'), _ld(ent),
                                     _dev(bias, torch.float32, 'bias'), _dev(mask, torch.int32, 'mask'), mask.size(1),
                                     float(hot), float(cold), inv, _dev(g, torch.float32, 'grad_logit'), g.stride(0),

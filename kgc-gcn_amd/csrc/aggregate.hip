@@ -388,7 +388,19 @@ struct BwdArgs {
   float *gx, *gee, *grel, *ws;
   int64_t ldx, ldg;
   int32_t n, e, d, rel_rows, nchunks_type;
+  // destination-range backward (mgcn_aggregate_bwd_shard) only: the table shard's rows, g's rows, the shard's own lists
+  int64_t sub[3];              // slot of shard row r = r + sub[region]; region: in-half rows, out-half rows, hub rows
+  int64_t rows_in, rows_inout; // first out-half row, first hub row
+  int64_t g_row0;              // g holds destinations [g_row0, ...)
+  int64_t list_len;            // entries of the by-type list (= rows of the shard)
+  const int32_t *src_ptr;      // [2N + 1] by-source list: entries [src_ptr[2 s + h], src_ptr[2 s + h + 1]) = slots of half h leaving s
+  const int32_t *src_rows;     // [rows] shard rows grouped by source
 };
+
+// Slot of row r of a destination range's table shard (in-half run, out-half run, hub run: include/mgcn_hip.h (2)).
+__device__ __forceinline__ int shard_slot(const BwdArgs &p, int64_t r) {
+  return int(r + (r < p.rows_in ? p.sub[0] : (r < p.rows_inout ? p.sub[1] : p.sub[2])));
+}
 
 constexpr int kTypeChunk = 16;  // slots per partial sum of the by-type reduction (short chunks = many lane groups in flight)
 
@@ -607,8 +619,10 @@ __global__ __launch_bounds__(256) void agg_bwd_grel_partial_kernel(BwdArgs p, in
 // flight together (the unfused stage 1 walked its 16 slots as 16 chains of three dependent round trips). Per slot
 // P = (g[dst, half] * norm) * x[src]; gee[slot] = P * rel[type] (agg_bwd_gee_kernel's value, bit for bit) and the chunk's partial
 // sum takes P * ee[slot] in entry order (agg_bwd_grel_partial_kernel's sum, bit for bit).
-template <int VEC, int CPL>
-__global__ __launch_bounds__(256) void agg_bwd_gee_grel_kernel(BwdArgs p, int gs_log2) {
+// SHARD (mgcn_aggregate_bwd_shard): the entries are rows of a destination range's table shard (typeslots / typeptr = the shard's
+// by-type list), ee / gee are indexed by that row, the slot is the row's slot and g holds the range's rows only.
+template <int VEC, int CPL, bool SHARD>
+__device__ __forceinline__ void gee_grel_pass(const BwdArgs &p, int gs_log2) {
   using V = Vec<VEC>;
   using T = typename V::type;
   constexpr int U = CPL == 1 ? 4 : (CPL == 2 ? 2 : 1);
@@ -617,19 +631,22 @@ __global__ __launch_bounds__(256) void agg_bwd_gee_grel_kernel(BwdArgs p, int gs
   const int64_t chunk = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> gs_log2;
   if (chunk >= p.nchunks_type) return;
   const int nchunk = p.d / VEC;
-  const int64_t e2 = 2 * int64_t(p.e);
+  const int64_t e2 = SHARD ? p.list_len : 2 * int64_t(p.e);
   const int64_t lo = chunk * kTypeChunk;
   const int64_t hi = (lo + kTypeChunk < e2) ? lo + kTypeChunk : e2;
   T acc[CPL];
 #pragma unroll
   for (int c = 0; c < CPL; ++c) acc[c] = V::zero();
-  int cur_type = p.rec[p.typeslots[lo]].y;
+  int cur_type = p.rec[SHARD ? shard_slot(p, p.typeslots[lo]) : p.typeslots[lo]].y;
   int64_t out_row = (p.typeptr[cur_type] == lo) ? int64_t(p.nchunks_type) + cur_type : chunk;
   for (int64_t i = lo; i < hi; i += U) {
-    int slot[U], sd[U];
+    int slot[U], row[U], sd[U];
     int4 r[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) slot[u] = p.typeslots[(i + u < hi) ? i + u : hi - 1];   // (clamped: no branch around a load)
+    for (int u = 0; u < U; ++u) {
+      row[u] = p.typeslots[(i + u < hi) ? i + u : hi - 1];   // (clamped: no branch around a load)
+      slot[u] = SHARD ? shard_slot(p, row[u]) : row[u];
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       r[u] = p.rec[slot[u]];
@@ -638,9 +655,9 @@ __global__ __launch_bounds__(256) void agg_bwd_gee_grel_kernel(BwdArgs p, int gs
     T gv[U][CPL], xv[U][CPL], ev[U][CPL], rv[U][CPL];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const float *gr = p.g + int64_t(sd[u] & 0x7fffffff) * p.ldg + ((sd[u] >> 31) & 1) * p.d;
+      const float *gr = p.g + (int64_t(sd[u] & 0x7fffffff) - (SHARD ? p.g_row0 : 0)) * p.ldg + ((sd[u] >> 31) & 1) * p.d;
       const float *xr = p.x + int64_t(r[u].x) * p.ldx;
-      const float *er = p.ee + int64_t(slot[u]) * p.d;
+      const float *er = p.ee + int64_t(row[u]) * p.d;
       const float *rr = p.rel + int64_t(r[u].y) * p.d;
 #pragma unroll
       for (int c = 0; c < CPL; ++c) {
@@ -670,7 +687,7 @@ __global__ __launch_bounds__(256) void agg_bwd_gee_grel_kernel(BwdArgs p, int gs
           const int ch = lig + c * gs;
           if (ch < nchunk) {
             const T pm = V::mul(V::muls(gv[u][c], w), xv[u][c]);
-            V::store(p.gee + int64_t(slot[u]) * p.d + ch * VEC, V::mul(pm, rv[u][c]));
+            V::store(p.gee + int64_t(row[u]) * p.d + ch * VEC, V::mul(pm, rv[u][c]));
             acc[c] = V::add(acc[c], V::mul(pm, ev[u][c]));
           }
         }
@@ -681,6 +698,126 @@ __global__ __launch_bounds__(256) void agg_bwd_gee_grel_kernel(BwdArgs p, int gs
   for (int c = 0; c < CPL; ++c) {
     const int ch = lig + c * gs;
     if (ch < nchunk) V::store(p.ws + out_row * p.d + ch * VEC, acc[c]);
+  }
+}
+
+template <int VEC, int CPL>
+__global__ __launch_bounds__(256) void agg_bwd_gee_grel_kernel(BwdArgs p, int gs_log2) {
+  gee_grel_pass<VEC, CPL, false>(p, gs_log2);
+}
+
+template <int VEC, int CPL>
+__global__ __launch_bounds__(256) void agg_bwd_shard_gee_grel_kernel(BwdArgs p, int gs_log2) {
+  gee_grel_pass<VEC, CPL, true>(p, gs_log2);
+}
+
+// By-source sums of a destination range (mgcn_aggregate_bwd_shard): entries [beg, end) of the shard's by-source list, each a row r
+// of the table shard with slot q; contribution ((g[dst_q, half_q] * norm_q) * rel[type_q]) * ee[r] — gx_walk's product, added in
+// list order (which is gx_walk's order: the list of (source, half) follows the reverse slots of the other half's run).
+template <int VEC, int CPL, int U>
+__device__ __forceinline__ void gx_list_walk(const BwdArgs &p, int beg, int end, int lig, int gs, typename Vec<VEC>::type (&acc)[CPL]) {
+  using V = Vec<VEC>;
+  using T = typename V::type;
+  const int nchunk = p.d / VEC;
+  for (int s = beg; s < end; s += U) {
+    int row[U], sd[U];
+    int4 rq[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (s + u < end) row[u] = p.src_rows[s + u];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (s + u < end) {
+        const int q = shard_slot(p, row[u]);
+        rq[u] = p.rec[q];
+        sd[u] = p.slot_dst[q];
+      }
+    T gv[U][CPL], rv[U][CPL], ev[U][CPL];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (s + u >= end) continue;
+      const float *gr = p.g + (int64_t(sd[u] & 0x7fffffff) - p.g_row0) * p.ldg + ((sd[u] >> 31) & 1) * p.d;
+      const float *rr = p.rel + int64_t(rq[u].y) * p.d;
+      const float *er = p.ee + int64_t(row[u]) * p.d;
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        const int ch = lig + c * gs;
+        if (ch < nchunk) {
+          gv[u][c] = V::load(gr + ch * VEC);
+          rv[u][c] = V::load(rr + ch * VEC);
+          ev[u][c] = V::load(er + ch * VEC);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (s + u >= end) continue;
+      const float w = __int_as_float(rq[u].z);
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        const int ch = lig + c * gs;
+        if (ch < nchunk) acc[c] = V::add(acc[c], V::mul(V::mul(V::muls(gv[u][c], w), rv[u][c]), ev[u][c]));
+      }
+    }
+  }
+}
+
+// gx partial of a destination range: every node (zero when the shard has no slot leaving it), half 0 then half 1; a (node, half)
+// whose reverse run is a hub takes the folded chunk sums of agg_bwd_shard_gx_hub_kernel instead — gx_node's order.
+template <int VEC, int CPL>
+__global__ __launch_bounds__(256) void agg_bwd_shard_gx_kernel(BwdArgs p, int gs_log2) {
+  using V = Vec<VEC>;
+  using T = typename V::type;
+  const int gs = 1 << gs_log2;
+  const int lig = threadIdx.x & (gs - 1);
+  const int64_t node = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> gs_log2;
+  if (node >= p.n) return;
+  const int nchunk = p.d / VEC;
+  T acc[CPL];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) acc[c] = V::zero();
+  for (int hq = 0; hq < 2; ++hq) {
+    if (p.hubinfo) {
+      const int2 hi = p.hubinfo[int64_t(1 - hq) * p.n + node];
+      if (hi.y > 0) {
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+          const int ch = lig + c * gs;
+          if (ch < nchunk) acc[c] = V::add(acc[c], V::load(p.hub_ws + int64_t(hi.x) * p.d + ch * VEC));
+        }
+        continue;
+      }
+    }
+    gx_list_walk<VEC, CPL, (CPL == 1 ? 2 : 1)>(p, p.src_ptr[2 * node + hq], p.src_ptr[2 * node + hq + 1], lig, gs, acc);
+  }
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) {
+    const int ch = lig + c * gs;
+    if (ch < nchunk) V::store(p.gx + node * p.d + ch * VEC, acc[c]);
+  }
+}
+
+// Hub pre-pass of the range's gx: one lane group per hub chunk of the graph; chunks[c] = {list begin, list end, first chunk of its
+// hub, chunks of its hub} holds the shard's slots whose reverse lies in chunk c (an empty range on ranks that own none of them),
+// so the fold (agg_hub_fold_kernel) adds the same rows in the same tree as the whole graph's.
+template <int VEC, int CPL>
+__global__ __launch_bounds__(256) void agg_bwd_shard_gx_hub_kernel(BwdArgs p, int gs_log2) {
+  using V = Vec<VEC>;
+  using T = typename V::type;
+  const int gs = 1 << gs_log2;
+  const int lig = threadIdx.x & (gs - 1);
+  const int64_t chunk = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> gs_log2;
+  if (chunk >= p.nchunks_hub) return;
+  const int nchunk = p.d / VEC;
+  const int4 range = p.chunks[chunk];
+  T acc[CPL];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) acc[c] = V::zero();
+  gx_list_walk<VEC, CPL, (CPL == 1 ? 4 : (CPL == 2 ? 2 : 1))>(p, range.x, range.y, lig, gs, acc);
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) {
+    const int ch = lig + c * gs;
+    if (ch < nchunk) V::store(p.hub_ws + chunk * p.d + ch * VEC, acc[c]);
   }
 }
 
@@ -956,6 +1093,27 @@ extern "C" int mgcn_aggregate_fwd(int64_t num_nodes, int64_t num_edges_half, int
   return MGCN_OK;
 }
 
+static void launch_grel_final(const Geometry &g, const BwdArgs &p, int32_t num_rel_rows, int32_t dim, hipStream_t st) {
+  const size_t lds = size_t(256 >> g.gs_log2) * size_t(dim) * sizeof(float);
+#define MGCN_GRELF_CASE(V_, C_) hipLaunchKernelGGL((agg_bwd_grel_final_kernel<V_, C_>), dim3(unsigned(num_rel_rows)), dim3(256), lds, st, p, g.gs_log2)
+  if (g.vec == 4) {
+    switch (g.cpl) {
+      case 1: MGCN_GRELF_CASE(4, 1); break;
+      case 2: MGCN_GRELF_CASE(4, 2); break;
+      case 4: MGCN_GRELF_CASE(4, 4); break;
+      default: MGCN_GRELF_CASE(4, 8); break;
+    }
+  } else {
+    switch (g.cpl) {
+      case 1: MGCN_GRELF_CASE(1, 1); break;
+      case 2: MGCN_GRELF_CASE(1, 2); break;
+      case 4: MGCN_GRELF_CASE(1, 4); break;
+      default: MGCN_GRELF_CASE(1, 8); break;
+    }
+  }
+#undef MGCN_GRELF_CASE
+}
+
 extern "C" size_t mgcn_aggregate_bwd_workspace(int64_t num_edges_half, int32_t dim, int32_t num_rel_rows,
                                                int64_t num_hub_chunks) {
   const int64_t nchunks = (2 * num_edges_half + kTypeChunk - 1) / kTypeChunk;
@@ -1045,28 +1203,93 @@ extern "C" int mgcn_aggregate_bwd(int64_t num_nodes, int64_t num_edges_half, int
       }
       MGCN_CHECK_LAUNCH("agg_bwd_grel_partial_kernel");
     }
-    {
-      const size_t lds = size_t(256 >> g.gs_log2) * size_t(dim) * sizeof(float);
-      hipStream_t st = static_cast<hipStream_t>(stream);
-#define MGCN_GRELF_CASE(V_, C_) hipLaunchKernelGGL((agg_bwd_grel_final_kernel<V_, C_>), dim3(unsigned(num_rel_rows)), dim3(256), lds, st, p, g.gs_log2)
-      if (g.vec == 4) {
-        switch (g.cpl) {
-          case 1: MGCN_GRELF_CASE(4, 1); break;
-          case 2: MGCN_GRELF_CASE(4, 2); break;
-          case 4: MGCN_GRELF_CASE(4, 4); break;
-          default: MGCN_GRELF_CASE(4, 8); break;
-        }
-      } else {
-        switch (g.cpl) {
-          case 1: MGCN_GRELF_CASE(1, 1); break;
-          case 2: MGCN_GRELF_CASE(1, 2); break;
-          case 4: MGCN_GRELF_CASE(1, 4); break;
-          default: MGCN_GRELF_CASE(1, 8); break;
-        }
-      }
-#undef MGCN_GRELF_CASE
-    }
+    launch_grel_final(g, p, num_rel_rows, dim, static_cast<hipStream_t>(stream));
     MGCN_CHECK_LAUNCH("agg_bwd_grel_final_kernel");
+  }
+  return MGCN_OK;
+}
+
+extern "C" size_t mgcn_aggregate_bwd_shard_workspace(int64_t shard_rows, int32_t dim, int32_t num_rel_rows, int64_t num_hub_chunks) {
+  const int64_t nchunks = (shard_rows + kTypeChunk - 1) / kTypeChunk;
+  return size_t(nchunks + num_rel_rows + (num_hub_chunks > 0 ? num_hub_chunks : 0)) * size_t(dim) * sizeof(float);
+}
+
+extern "C" int mgcn_aggregate_bwd_shard(int64_t num_nodes, int64_t num_edges_half, int32_t dim, int32_t num_rel_rows,
+                                        const mgcn_edge_rec *rec_dev, const int32_t *slot_dst_dev, int64_t node_begin,
+                                        int64_t node_end, int64_t rows_in, int64_t rows_out, int64_t rows_hub, int64_t ee_sub_in,
+                                        int64_t ee_sub_out, int64_t ee_sub_hub, const int32_t *src_ptr_dev,
+                                        const int32_t *src_rows_dev, const int32_t *hubinfo_dev, const int32_t *src_chunks_dev,
+                                        int64_t num_hub_chunks, const int32_t *type_ptr_dev, const int32_t *type_rows_dev,
+                                        const float *x_dev, int64_t ldx, const float *rel_dev, const float *ee_dev,
+                                        const float *g_dev, int64_t ldg, float *gx_dev, float *gee_dev, float *grel_dev,
+                                        float *workspace_dev, size_t workspace_bytes, void *stream) {
+  MGCN_REQUIRE(num_nodes >= 0 && num_edges_half >= 0 && dim > 0 && num_rel_rows > 0, "aggregate_bwd_shard: bad sizes");
+  MGCN_REQUIRE(num_nodes < (int64_t(1) << 31) - 1 && 2 * num_edges_half < (int64_t(1) << 31) - 1,
+               "aggregate_bwd_shard: sizes exceed int32");
+  MGCN_REQUIRE(node_begin >= 0 && node_begin <= node_end && node_end <= num_nodes, "aggregate_bwd_shard: bad node range");
+  const int64_t rows = rows_in + rows_out + rows_hub;
+  MGCN_REQUIRE(rows_in >= 0 && rows_out >= 0 && rows_hub >= 0 && rows <= 2 * num_edges_half, "aggregate_bwd_shard: bad shard rows");
+  MGCN_REQUIRE(x_dev && rel_dev && grel_dev && type_ptr_dev, "aggregate_bwd_shard: null pointer");
+  MGCN_REQUIRE(rows == 0 || (rec_dev && slot_dst_dev && ee_dev && g_dev && gee_dev && type_rows_dev), "aggregate_bwd_shard: null slot arrays");
+  MGCN_REQUIRE(!gx_dev || (src_ptr_dev && (rows == 0 || src_rows_dev)), "aggregate_bwd_shard: gx needs the by-source list");
+  MGCN_REQUIRE(ldx >= dim && ldg >= 2 * int64_t(dim), "aggregate_bwd_shard: ldx/ldg too small");
+  MGCN_REQUIRE(num_hub_chunks >= 0 && num_hub_chunks < (int64_t(1) << 31) &&
+                   (num_hub_chunks == 0 || !gx_dev || (hubinfo_dev && src_chunks_dev)),
+               "aggregate_bwd_shard: hub chunks need hubinfo / the shard's chunk lists");
+  const size_t ws_need = mgcn_aggregate_bwd_shard_workspace(rows, dim, num_rel_rows, num_hub_chunks);
+  MGCN_REQUIRE(workspace_dev && workspace_bytes >= ws_need, "aggregate_bwd_shard: workspace too small (%zu bytes needed)", ws_need);
+  const bool aligned = mgcn::aligned16(x_dev) && mgcn::aligned16(rel_dev) && (!g_dev || mgcn::aligned16(g_dev)) &&
+                       (!ee_dev || mgcn::aligned16(ee_dev)) && (!gx_dev || mgcn::aligned16(gx_dev)) && (!gee_dev || mgcn::aligned16(gee_dev)) &&
+                       mgcn::aligned16(grel_dev) && mgcn::aligned16(workspace_dev) && ldx % 4 == 0 && ldg % 4 == 0;
+  Geometry g;
+  if (!pick_geometry(dim, aligned, &g)) return mgcn::fail(MGCN_EUNSUPPORTED, "aggregate_bwd_shard: dim %d too wide", dim);
+  BwdArgs p = {};
+  p.rec = reinterpret_cast<const int4 *>(rec_dev);
+  p.slot_dst = slot_dst_dev;
+  p.hubinfo = num_hub_chunks > 0 ? reinterpret_cast<const int2 *>(hubinfo_dev) : nullptr;
+  p.chunks = reinterpret_cast<const int4 *>(src_chunks_dev);
+  p.nchunks_hub = int32_t(num_hub_chunks);
+  p.typeptr = type_ptr_dev;
+  p.typeslots = type_rows_dev;
+  p.x = x_dev;
+  p.rel = rel_dev;
+  p.ee = ee_dev;
+  p.g = g_dev;
+  p.gx = gx_dev;
+  p.gee = gee_dev;
+  p.grel = grel_dev;
+  p.ws = workspace_dev;
+  p.ldx = ldx;
+  p.ldg = ldg;
+  p.n = int32_t(num_nodes);
+  p.e = int32_t(num_edges_half);
+  p.d = dim;
+  p.rel_rows = num_rel_rows;
+  p.nchunks_type = int32_t((rows + kTypeChunk - 1) / kTypeChunk);
+  p.hub_ws = workspace_dev + (int64_t(p.nchunks_type) + num_rel_rows) * dim;
+  p.sub[0] = ee_sub_in; p.sub[1] = ee_sub_out; p.sub[2] = ee_sub_hub;
+  p.rows_in = rows_in;
+  p.rows_inout = rows_in + rows_out;
+  p.g_row0 = node_begin;
+  p.list_len = rows;
+  p.src_ptr = src_ptr_dev;
+  p.src_rows = src_rows_dev;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (rows > 0) {   // gee and the grel chunk sums: one pass over the shard's slots in type order
+    MGCN_LAUNCH_GEOM(agg_bwd_shard_gee_grel_kernel, p, p.nchunks_type, g, stream);
+    MGCN_CHECK_LAUNCH("agg_bwd_shard_gee_grel_kernel");
+  }
+  launch_grel_final(g, p, num_rel_rows, dim, st);   // (an empty shard: zero rows)
+  MGCN_CHECK_LAUNCH("agg_bwd_grel_final_kernel");
+  if (gx_dev && num_nodes > 0) {
+    if (num_hub_chunks > 0) {
+      MGCN_LAUNCH_GEOM(agg_bwd_shard_gx_hub_kernel, p, num_hub_chunks, g, stream);
+      MGCN_CHECK_LAUNCH("agg_bwd_shard_gx_hub_kernel");
+      launch_fold(g, p.chunks, p.hub_ws, 0, dim, num_hub_chunks, st);
+      MGCN_CHECK_LAUNCH("agg_hub_fold_kernel");
+    }
+    MGCN_LAUNCH_GEOM(agg_bwd_shard_gx_kernel, p, num_nodes, g, stream);
+    MGCN_CHECK_LAUNCH("agg_bwd_shard_gx_kernel");
   }
   return MGCN_OK;
 }

@@ -256,3 +256,96 @@ extern "C" int mgcn_matmul_tn_f32(int64_t k, int32_t m, int32_t n, const float *
   MGCN_CHECK_LAUNCH("matmul_tn_f32");
   return MGCN_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// (4s) The same epilogue split into stages for a destination partition: every rank reduces ITS rows in the same 128-row blocks and
+// the caller exchanges the per-block partials between the stages; the folds then run over all ranks' blocks in the order given
+// (rank, then block), so the statistics are the same on every rank — and equal to the unsplit entry points' when every rank's
+// first row is a multiple of 128 (the blocks are then the same blocks).
+// ---------------------------------------------------------------------------------------------
+extern "C" int mgcn_bn_train_stage_sum(int64_t num_rows, int32_t dim_out, const float *u_in_dev, const float *u_out_dev,
+                                       const float *u_loop_dev, int64_t ldu, const float *bias_dev, float *z_dev, float *part_dev,
+                                       void *stream) {
+  MGCN_REQUIRE(num_rows >= 0 && dim_out > 0 && ldu >= dim_out, "bn_train_stage_sum: bad sizes");
+  if (num_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(u_in_dev && u_out_dev && u_loop_dev && z_dev && part_dev, "bn_train_stage_sum: null pointer");
+  const int nblk = int((num_rows + RB - 1) / RB);
+  hipLaunchKernelGGL(combine_sum_kernel, dim3(nblk), dim3(TPB), 0, static_cast<hipStream_t>(stream), u_in_dev, u_out_dev, u_loop_dev, ldu,
+                     bias_dev, z_dev, part_dev, num_rows, dim_out);
+  MGCN_CHECK_LAUNCH("bn_train_stage_sum");
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_bn_train_stage_center(int64_t num_rows, int32_t dim_out, const float *z_dev, const float *sum_parts_dev,
+                                          int64_t num_blocks, int64_t total_rows, float *mean_dev, float *part_dev, void *stream) {
+  MGCN_REQUIRE(num_rows >= 0 && dim_out > 0 && total_rows >= num_rows && total_rows > 0 && num_blocks > 0 && num_blocks < (int64_t(1) << 31),
+               "bn_train_stage_center: bad sizes");
+  MGCN_REQUIRE(sum_parts_dev && mean_dev && (num_rows == 0 || (z_dev && part_dev)), "bn_train_stage_center: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const unsigned cg = unsigned((dim_out + TPB - 1) / TPB);
+  hipLaunchKernelGGL(fold_kernel, dim3(cg), dim3(TPB), 0, st, sum_parts_dev, int(num_blocks), dim_out, 1.0f / float(total_rows), mean_dev);
+  if (num_rows > 0) {
+    const int nblk = int((num_rows + RB - 1) / RB);
+    hipLaunchKernelGGL((partial_kernel<0>), dim3(nblk), dim3(TPB), 0, st, z_dev, nullptr, nullptr, mean_dev, nullptr, part_dev, nullptr,
+                       num_rows, dim_out);
+  }
+  MGCN_CHECK_LAUNCH("bn_train_stage_center");
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_bn_train_stage_finish(int64_t num_rows, int32_t dim_out, const float *z_dev, const float *sq_parts_dev,
+                                          int64_t num_blocks, int64_t total_rows, const float *mean_dev, const float *gamma_dev,
+                                          const float *beta_dev, float *running_mean_dev, float *running_var_dev, float momentum,
+                                          float eps, float *rstd_dev, float *y_dev, void *stream) {
+  MGCN_REQUIRE(num_rows >= 0 && dim_out > 0 && total_rows >= num_rows && total_rows > 0 && num_blocks > 0 && num_blocks < (int64_t(1) << 31),
+               "bn_train_stage_finish: bad sizes");
+  MGCN_REQUIRE(sq_parts_dev && mean_dev && gamma_dev && beta_dev && rstd_dev && (num_rows == 0 || (z_dev && y_dev)),
+               "bn_train_stage_finish: null pointer");
+  MGCN_REQUIRE((running_mean_dev != nullptr) == (running_var_dev != nullptr), "bn_train_stage_finish: bad arguments");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const unsigned cg = unsigned((dim_out + TPB - 1) / TPB);
+  hipLaunchKernelGGL(stats_finish_kernel, dim3(cg), dim3(TPB), 0, st, sq_parts_dev, int(num_blocks), dim_out, total_rows, eps, momentum,
+                     mean_dev, rstd_dev, running_mean_dev, running_var_dev);
+  const int64_t total = num_rows * dim_out;
+  if (total > 0)
+    hipLaunchKernelGGL(apply_fwd_kernel, dim3(unsigned((total + TPB - 1) / TPB)), dim3(TPB), 0, st, z_dev, mean_dev, rstd_dev, gamma_dev,
+                       beta_dev, y_dev, total, dim_out);
+  MGCN_CHECK_LAUNCH("bn_train_stage_finish");
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_bn_train_bwd_stage_sums(int64_t num_rows, int32_t dim_out, const float *z_dev, const float *y_dev,
+                                            const float *gy_dev, const float *save_mean_dev, const float *save_rstd_dev,
+                                            float *g_part_dev, float *gx_part_dev, void *stream) {
+  MGCN_REQUIRE(num_rows >= 0 && dim_out > 0, "bn_train_bwd_stage_sums: bad sizes");
+  if (num_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(z_dev && y_dev && gy_dev && save_mean_dev && save_rstd_dev && g_part_dev && gx_part_dev,
+               "bn_train_bwd_stage_sums: null pointer");
+  const int nblk = int((num_rows + RB - 1) / RB);
+  hipLaunchKernelGGL((partial_kernel<1>), dim3(nblk), dim3(TPB), 0, static_cast<hipStream_t>(stream), z_dev, y_dev, gy_dev,
+                     save_mean_dev, save_rstd_dev, g_part_dev, gx_part_dev, num_rows, dim_out);
+  MGCN_CHECK_LAUNCH("bn_train_bwd_stage_sums");
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_bn_train_bwd_stage_apply(int64_t num_rows, int32_t dim_out, const float *z_dev, const float *y_dev,
+                                             const float *gy_dev, const float *save_mean_dev, const float *save_rstd_dev,
+                                             const float *gamma_dev, const float *g_parts_dev, const float *gx_parts_dev,
+                                             int64_t num_blocks, int64_t total_rows, float *gz_dev, float *gu_dev, float *ggamma_dev,
+                                             float *gbeta_dev, void *stream) {
+  MGCN_REQUIRE(num_rows >= 0 && dim_out > 0 && total_rows >= num_rows && total_rows > 0 && num_blocks > 0 && num_blocks < (int64_t(1) << 31),
+               "bn_train_bwd_stage_apply: bad sizes");
+  MGCN_REQUIRE(save_mean_dev && save_rstd_dev && gamma_dev && g_parts_dev && gx_parts_dev && ggamma_dev && gbeta_dev &&
+                   (num_rows == 0 || (z_dev && y_dev && gy_dev && gz_dev && gu_dev)),
+               "bn_train_bwd_stage_apply: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const unsigned cg = unsigned((dim_out + TPB - 1) / TPB);
+  hipLaunchKernelGGL(fold_kernel, dim3(cg), dim3(TPB), 0, st, g_parts_dev, int(num_blocks), dim_out, 1.0f, gbeta_dev);     // d beta
+  hipLaunchKernelGGL(fold_kernel, dim3(cg), dim3(TPB), 0, st, gx_parts_dev, int(num_blocks), dim_out, 1.0f, ggamma_dev);   // d gamma
+  const int64_t total = num_rows * dim_out;
+  if (total > 0)
+    hipLaunchKernelGGL(apply_bwd_kernel, dim3(unsigned((total + TPB - 1) / TPB)), dim3(TPB), 0, st, z_dev, y_dev, gy_dev, save_mean_dev,
+                       save_rstd_dev, gamma_dev, gbeta_dev, ggamma_dev, gz_dev, gu_dev, total, dim_out, 1.0f / float(total_rows));
+  MGCN_CHECK_LAUNCH("bn_train_bwd_stage_apply");
+  return MGCN_OK;
+}

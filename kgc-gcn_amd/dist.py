@@ -48,16 +48,22 @@ class FilterIndex(object):
         return sub.to(torch.int64) * self.num_rel_ids + rel.to(torch.int64)
 
 
-_INTO_TENSOR = {}
+_INTO_TENSOR = {}      # (backend, device type) -> the probe's answer
+_PROBED = set()        # (group name, its global ranks, device type) whose members have run the probe (a name and a member list,
+                       # not the object: holding a group would keep it from being destroyed with its process group)
 
 
 def _into_tensor_ok(group, like):
-    """Whether the group's backend has all_gather_into_tensor — decided ONCE per (backend, device type) by a one-element probe
-    that every rank of the group runs at the same point (the first exchange), never by catching an error of a real
-    collective: a rank whose collective fails for its own reasons (an RCCL error, a size mismatch) must raise, not
-    quietly switch to another collective than its peers are in."""
+    """Whether the group's backend has all_gather_into_tensor — decided by a one-element probe that EVERY process group runs
+    once per device type, at its first exchange (all its members reach that point together), never by catching an error of a
+    real collective: a rank whose collective fails for its own reasons (an RCCL error, a size mismatch) must raise, not
+    quietly switch to another collective than its peers are in. Per group, not per backend: members of a sub-group that probed
+    first would otherwise skip the probe that the other ranks run on a larger group, and the ranks would be in different
+    collectives."""
+    group = dist.group.WORLD if group is None else group
     key = (dist.get_backend(group), like.device.type)
-    if key not in _INTO_TENSOR:
+    ident = (getattr(group, 'group_name', ''), tuple(dist.get_process_group_ranks(group)), key[1])
+    if ident not in _PROBED:
         ok = hasattr(dist, 'all_gather_into_tensor')
         if ok:
             world = dist.get_world_size(group)
@@ -66,6 +72,7 @@ def _into_tensor_ok(group, like):
             except (RuntimeError, NotImplementedError):   # a capability of the backend: the same answer on every rank
                 ok = False
         _INTO_TENSOR[key] = ok
+        _PROBED.add(ident)
     return _INTO_TENSOR[key]
 
 
@@ -401,3 +408,439 @@ def predict_topk_sharded(model, graph, queries, k, filt=None, group=None, trunk_
         return (torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=torch.float32, device=dev))
     scores, ids = _topk_all(x, keys, ent_shard, bias_shard, b[rank], k, filt, group, _native)
     return ids[:Q], scores[:Q]
+
+
+# ------------------------------------------------------------------------------------------------
+# Training step of the destination partition: rank r owns destinations [n0, n1) = balanced_bounds(W)[r:r + 2], their
+# shard of every per-edge table and the matching entity rows of the scorer; everything else is replicated.
+# ------------------------------------------------------------------------------------------------
+class _Exchange(object):
+    """The collectives of one sharded step: bounds, this rank's rows, and the group (None = one rank, no collective)."""
+
+    def __init__(self, bounds, rank, group, world):
+        self.b, self.rank, self.group, self.world = bounds, rank, group, world
+        self.n0, self.n1 = bounds[rank], bounds[rank + 1]
+        self.rows = [bounds[r + 1] - bounds[r] for r in range(world)]
+        self.chunk = max(self.rows)
+        self.total = bounds[-1]
+
+    def gather_rows(self, y):
+        """[N, O]: every rank's rows in rank order (equal padded chunks, one all-gather)."""
+        if self.world == 1:
+            return y
+        pad = y.new_zeros((self.chunk, y.size(1)))
+        pad[:y.size(0)] = y
+        full = y.new_empty((self.world * self.chunk, y.size(1)))
+        _gather_into(full, pad, self.group)
+        if all(n == self.chunk for n in self.rows[:-1]):
+            return full[:self.total]
+        return torch.cat([full[r * self.chunk:r * self.chunk + self.rows[r]] for r in range(self.world)], dim=0)
+
+    def gather_blocks(self, part):
+        """Every rank's BN block partials ([blocks_r, O] or [2, blocks_r, O]) concatenated along the blocks in rank order: the
+        order in which the stages fold them."""
+        if self.world == 1:
+            return part
+        nb = [_native.bn_blocks(n) for n in self.rows]
+        width = max(nb)
+        stacked = part.dim() == 3
+        p = part.permute(1, 0, 2) if stacked else part                     # blocks first
+        pad = p.new_zeros((width,) + tuple(p.shape[1:]))
+        pad[:p.size(0)] = p
+        full = pad.new_empty((self.world * width,) + tuple(pad.shape[1:]))
+        _gather_into(full, pad, self.group)
+        out = torch.cat([full[r * width:r * width + nb[r]] for r in range(self.world) if nb[r] > 0], dim=0)
+        return (out.permute(1, 0, 2) if stacked else out).contiguous()
+
+    def all_reduce(self, t):
+        if self.world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t
+
+
+def _mm(a, b):
+    return _native.matmul(a, b) if a.size(0) > 0 else a.new_zeros((0, b.size(1)))
+
+
+def _mm_tn(a, b):
+    return _native.matmul_tn(a, b) if a.size(0) > 0 else a.new_zeros((a.size(1), b.size(1)))
+
+
+class _ShardAggregateFn(torch.autograd.Function):
+    """In / out aggregates [n1 - n0, 2D] of this rank's destinations from its table shard; backward by mgcn_aggregate_bwd_shard
+    (gee complete, grel and gx partial: the ranks' sums add up)."""
+
+    @staticmethod
+    def forward(ctx, x, rels, ee_shard, csr, n0, n1):
+        out = torch.empty((n1 - n0, 2 * x.size(1)), dtype=torch.float32, device=x.device)
+        if n1 > n0:
+            _native.aggregate_fwd(csr, x, rels, ee_shard, True, None, out, node_range=(n0, n1), ee_sub=csr.shard_ee_sub(n0, n1),
+                                  out_row0=n0)
+        ctx.save_for_backward(x, rels, ee_shard)
+        ctx.csr, ctx.range = csr, (n0, n1)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, rels, ee = ctx.saved_tensors
+        gx, gee, grel = _native.aggregate_bwd_shard(ctx.csr, x, rels, ee, g.contiguous(), ctx.range, want_gx=ctx.needs_input_grad[0])
+        return gx, grel, gee, None, None, None
+
+
+class _ShardLayerTrainFn(torch.autograd.Function):
+    """model._LayerTrainFn on this rank's rows with GLOBAL batch statistics: the BN reductions run in the split stages of
+    csrc/train_layer.hip (4s) and every rank's per-block partials are all-gathered between them (forward: column sums, then
+    centred sums; backward: the g_pre / g_pre * xhat sums). Dropout keep-masks are the rank's own for its rows."""
+
+    @staticmethod
+    def forward(ctx, agg, a_loop, w_in, w_out, w_loop, bias, gamma, beta, running_mean, running_var, momentum, eps, p_drop, ex):
+        d = w_in.size(0)
+        u_in, u_out = _mm(agg[:, :d], w_in.contiguous()), _mm(agg[:, d:], w_out.contiguous())
+        u_loop = _mm(a_loop.contiguous(), w_loop.contiguous())
+        m_in = m_out = None
+        ctx.inv_keep = 1.0
+        if p_drop >= 1.0:
+            m_in = torch.zeros(u_in.shape, dtype=torch.bool, device=u_in.device)
+            m_out, ctx.inv_keep = m_in, 0.0
+            u_in, u_out = torch.zeros_like(u_in), torch.zeros_like(u_out)
+        elif p_drop > 0:
+            keep = 1.0 - p_drop
+            ctx.inv_keep = 1.0 / keep
+            m_in = torch.empty_like(u_in).bernoulli_(keep).bool()
+            m_out = torch.empty_like(u_out).bernoulli_(keep).bool()
+            u_in, u_out = (u_in * m_in).mul_(ctx.inv_keep), (u_out * m_out).mul_(ctx.inv_keep)
+        z, part = _native.bn_train_stage_sum(u_in, u_out, u_loop, bias)
+        mean, part = _native.bn_train_stage_center(z, ex.gather_blocks(part), ex.total)
+        y, rstd = _native.bn_train_stage_finish(z, ex.gather_blocks(part), ex.total, mean, gamma, beta, running_mean, running_var,
+                                                momentum, eps)
+        ctx.save_for_backward(agg, a_loop, w_in, w_out, w_loop, gamma, z, y, mean, rstd, m_in, m_out)
+        ctx.has_bias, ctx.ex = bias is not None, ex
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        agg, a_loop, w_in, w_out, w_loop, gamma, z, y, mean, rstd, m_in, m_out = ctx.saved_tensors
+        d = w_in.size(0)
+        gy = gy.contiguous()
+        parts = ctx.ex.gather_blocks(_native.bn_train_bwd_stage_sums(z, y, gy, mean, rstd))
+        gz, gu, ggamma, gbeta = _native.bn_train_bwd_stage_apply(z, y, gy, mean, rstd, gamma, parts[0], parts[1], ctx.ex.total)
+        g_in = (gu * m_in).mul_(ctx.inv_keep) if m_in is not None else gu
+        g_out = (gu * m_out).mul_(ctx.inv_keep) if m_out is not None else gu
+        need = ctx.needs_input_grad
+        g_agg = g_loop = g_win = g_wout = g_wloop = None
+        if need[0]:
+            g_agg = torch.cat([_mm(g_in, w_in.t().contiguous()), _mm(g_out, w_out.t().contiguous())], dim=1)
+        if need[1]:
+            g_loop = _mm(gu, w_loop.t().contiguous())
+        if need[2]:
+            g_win = _mm_tn(agg[:, :d], g_in)
+        if need[3]:
+            g_wout = _mm_tn(agg[:, d:], g_out)
+        if need[4]:
+            g_wloop = _mm_tn(a_loop.contiguous(), gu)
+        g_bias = gz.sum(0) if (ctx.has_bias and need[5]) else None
+        return g_agg, g_loop, g_win, g_wout, g_wloop, g_bias, ggamma, gbeta, None, None, None, None, None, None
+
+
+class _GatherRowsFn(torch.autograd.Function):
+    """Layer output rows -> [N, O] on every rank. Backward: the rank's rows of the incoming gradient, all-reduced first when it
+    holds partials (`reduce`: a layer the next layer reads, whose gx is a partial [N, O] on every rank)."""
+
+    @staticmethod
+    def forward(ctx, y, ex, reduce):
+        ctx.ex, ctx.reduce = ex, reduce
+        return ex.gather_rows(y.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        ex = ctx.ex
+        g = g.contiguous()
+        if ctx.reduce:
+            # in place, without the [N, O] copy a clone costs (20 GB at configs[4]): `g` is the gradient autograd accumulated for
+            # the gathered output, and this node is its only reader — the output has no other grad_fn consumer of it and no hook
+            ex.all_reduce(g)
+        return g[ex.n0:ex.n1].contiguous(), None, None
+
+
+class _AllReduceGradFn(torch.autograd.Function):
+    """Identity; the gradient is summed over the ranks (d x_trunk = sum_r G_r^T ent_r: each rank scores its own entities)."""
+
+    @staticmethod
+    def forward(ctx, x, ex):
+        ctx.ex = ex
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        # cloned ([B, O]: small): `g` may be the very tensor the scorer's backward returned for other uses
+        return ctx.ex.all_reduce(g.contiguous().clone()), None
+
+
+class _RankZeroGradFn(torch.autograd.Function):
+    """Identity; only rank 0 passes the gradient on: a gradient that every rank computes in full (a replicated computation on
+    complete inputs) joins partial ones, and the sum over the ranks must count it once."""
+
+    @staticmethod
+    def forward(ctx, x, ex):
+        ctx.ex = ex
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g if ctx.ex.rank == 0 else torch.zeros_like(g)), None
+
+
+class _ScoreBCEShardFn(torch.autograd.Function):
+    """model._ScoreBCEFn on this rank's entity rows: the mean runs over B x the GLOBAL entity count, so the ranks' losses and
+    gradients add up to the whole table's."""
+
+    @staticmethod
+    def forward(ctx, x, ent, bias, mask, hot, cold, num_entities):
+        loss, g = _native.score_bce_fwd(x, ent, bias, mask, hot, cold, num_entities=num_entities)
+        ctx.save_for_backward(x, ent, g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        from .model import _ScoreBCEFn
+        return _ScoreBCEFn.backward(ctx, gl) + (None,)
+
+
+def _dropout(x, p, generator):
+    """F.dropout with the keep-mask drawn from `generator`."""
+    if p <= 0:
+        return x
+    if p >= 1:
+        return x * 0.0
+    keep = 1.0 - p
+    return x * torch.empty_like(x).bernoulli_(keep, generator=generator) * (1.0 / keep)
+
+
+def _trunk(conv2, src_emb, rel_emb, generator):
+    """ConvE.trunk with its two dropouts drawn from `generator` (None: torch's default generator, as ConvE.trunk)."""
+    import torch.nn.functional as F
+    if generator is None or not conv2.training:
+        return conv2.trunk(src_emb, rel_emb)
+    p = conv2.params
+    o = p.gcn_out_dim
+    stack = torch.cat([src_emb.view(-1, 1, o), rel_emb.view(-1, 1, o)], dim=1)
+    stack = stack.transpose(2, 1).reshape(-1, 1, 2 * p.k_w, p.k_h)
+    x = _dropout(F.relu(conv2.bn1(conv2.conv_e(conv2.bn0(stack)))), conv2.feature_drop.p, generator)
+    x = _dropout(conv2.fc(x.view(-1, conv2.flat_sz)), conv2.hidden_drop.p, generator)
+    return F.relu(conv2.bn2(x)).contiguous()
+
+
+def _agreed_seed(group, device):
+    """A fresh random 62-bit seed that every rank of `group` agrees on: rank 0 draws it from its default generator (which
+    advances, so every call gives a new seed) and broadcasts it. A collective: every rank calls it at the same point."""
+    t = torch.randint(0, 1 << 62, (1,), dtype=torch.int64).to(device)
+    dist.broadcast(t, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    return int(t.item())
+
+
+def _world_rank(group):
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    return world, (dist.get_rank(group) if world > 1 else 0)
+
+
+def _sharded_setup(model, graph, group, what):
+    """(csr, exchange) for this rank, or NativeError for a model / graph the sharded step cannot train."""
+    world, rank = _world_rank(group)
+    csr = graph.csr(model.relation_embedding.size(0) + 1)
+    b = csr.balanced_bounds(world)
+    n0, n1 = b[rank], b[rank + 1]
+    ent_identity, edge_identity = model._graph_facts(graph)
+    if not (ent_identity and edge_identity):
+        raise _native.NativeError('%s: the graph\'s entity and edge ids must be the identity (data_loader.py:113,147-149 builds '
+                                  'them so): the table shards are laid out by edge position' % what)
+    if model._edge_shard is None:
+        if world > 1:
+            raise _native.NativeError('%s: the model holds whole per-edge tables; at %d ranks fill a model built with '
+                                      'params.edge_table_rows through dist.shard_model_tables for destinations [%d, %d)'
+                                      % (what, world, n0, n1))
+        model._use_slot_order(csr)           # one rank: the whole slot-ordered table is the shard of [0, N)
+    elif model._edge_shard[0] is not csr or model._edge_shard[1:] != (n0, n1):
+        raise _native.NativeError('%s: the model holds the table shard of destinations %s, this rank owns (%d, %d)'
+                                  % (what, model._edge_shard[1:], n0, n1))
+    if not csr.mirrored:
+        raise _native.NativeError('%s: the edge list is not mirror-symmetric' % what)
+    return csr, _Exchange(b, rank, group, world)
+
+
+def _complete_params(model):
+    """Replicated parameters whose gradient every rank computes in full: the ConvE trunk, the encoder's BN affine pair (global
+    statistics) and the last layer's relation projection (fed by the trunk alone). All others are partial sums over the ranks."""
+    layers = [model.conv1] + list(model.conv1_extra)
+    ps = [p for n, p in model.conv2.named_parameters() if n != 'bias']
+    for layer in layers:
+        ps += [layer.ent_bn.weight, layer.ent_bn.bias]
+    ps.append(layers[-1].rels_weight)
+    return {id(p) for p in ps}
+
+
+def _trunk_statistics(model):
+    """The ConvE trunk's BN running statistics: every rank updates them from its own (replicated) trunk forward, which MIOpen
+    does not promise to reduce in the same order on every rank."""
+    return [b for b in model.conv2.buffers() if b.is_floating_point()]
+
+
+def _bucket_grads(model):
+    """Point the .grad of every replicated parameter at a view of ONE zeroed flat buffer before the backward: autograd then
+    accumulates into the views in place, and the bucket is reduced without staging a copy of d entity_embedding [N, D]. A tail
+    of the buffer carries the trunk's running statistics. Returns (buffer, [(parameter, view)]). The per-edge table shards keep
+    their own, local gradients."""
+    shard = {id(p) for _, p in model._edge_tables()}
+    params = [p for p in model.parameters() if id(p) not in shard and p.requires_grad]
+    tail = sum(b.numel() for b in _trunk_statistics(model))
+    flat = torch.zeros(sum(p.numel() for p in params) + tail, dtype=torch.float32, device=model.entity_embedding.device)
+    views, off = [], 0
+    for p in params:
+        v = flat[off:off + p.numel()].view_as(p)
+        p.grad = v
+        views.append((p, v))
+        off += p.numel()
+    return flat, views
+
+
+def _reduce_bucket(model, ex, flat, views):
+    """One all-reduce of the flat bucket: partial sums from every rank, complete gradients and the trunk's running statistics
+    from rank 0 only (each counted once, and every rank ends with the same bits whatever the determinism of the replicated
+    computation)."""
+    complete = _complete_params(model)
+    for p, v in views:
+        if p.grad is not v:              # (autograd replaced the view instead of accumulating into it: move the values in)
+            v.copy_(p.grad)
+            p.grad = v
+        if id(p) in complete and ex.rank != 0:
+            v.zero_()
+    stats = _trunk_statistics(model)
+    off = flat.numel() - sum(b.numel() for b in stats)
+    if ex.rank == 0 and stats:
+        flat[off:] = torch.cat([b.reshape(-1) for b in stats])
+    ex.all_reduce(flat)
+    for b in stats:
+        b.copy_(flat[off:off + b.numel()].view_as(b))
+        off += b.numel()
+
+
+def clip_grad_norm_sharded(model, max_norm, group=None):
+    """torch.nn.utils.clip_grad_norm_ over the model's parameters with the GLOBAL norm: the per-parameter norms in parameter
+    order (torch._foreach_norm, as torch), the table shards' norms replaced by their norm over all ranks (all-reduced squares),
+    then the norm of those norms. With one rank this is clip_grad_norm_'s value bit for bit. Returns the total norm."""
+    world, _ = _world_rank(group)
+    params = [p for p in model.parameters() if p.grad is not None]
+    if not params:
+        return torch.tensor(0.0)
+    norms = list(torch._foreach_norm([p.grad for p in params], 2.0))
+    if world > 1:
+        shard = {id(p) for _, p in model._edge_tables()}
+        idx = [i for i, p in enumerate(params) if id(p) in shard]
+        if idx:
+            sq = torch.stack([norms[i] for i in idx]) ** 2
+            dist.all_reduce(sq, op=dist.ReduceOp.SUM, group=group)
+            for j, i in enumerate(idx):
+                norms[i] = sq[j].sqrt()
+    total = torch.linalg.vector_norm(torch.stack(norms), 2.0)
+    torch.nn.utils.clip_grads_with_norm_(params, max_norm, total)
+    return total
+
+
+def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0, clip=None, group=None, generator=None):
+    """One training step (main.py:59-70: forward, BCE against the train index's targets, backward, clipping, optimizer) of the
+    destination-partitioned model: rank r owns destinations [n0, n1) = graph.csr(...).balanced_bounds(W)[r:r + 2], the table
+    shards of `dist.shard_model_tables` for that range (a whole-table model only at W = 1) and entity rows [n0, n1) of the
+    scorer; `entity_embedding`, `relation_embedding`, the layer weights, BN and ConvE are replicated. Every rank passes the same
+    batch (src, rel [B]), `index` = DataLoader.train_index() on the device, and the same optimizer type over model.parameters().
+    Data flow: per layer the rank aggregates its destinations, runs the training-mode products and epilogue with
+    GLOBAL batch statistics, applies its own dropout masks to its rows and all-gathers the rows; every rank runs the ConvE trunk
+    on the whole batch and scores its own entities (global mean); the backward reduces each gradient once — the trunk's input
+    gradient and every inner layer output's by all-reduce inside the backward, all replicated parameters in one flat bucket
+    after it; the table shards' gradients stay local. The trunk's dropout masks must be the same on every rank: they come from
+    `generator` (a torch.Generator on the device, seeded identically on every rank) or, without one at W > 1, from a per-step
+    generator seeded from a fresh seed the group agrees on. With one rank the step computes what forward_loss + backward +
+    clip_grad_norm_ + step compute, bit for bit (dropout 0). Returns the global loss (0-dim tensor, detached)."""
+    import torch.nn.functional as F
+    csr, ex = _sharded_setup(model, graph, group, 'train_step_sharded')
+    n0, n1, W = ex.n0, ex.n1, ex.world
+    model.train()
+    optimizer.zero_grad()
+    layers = [model.conv1] + list(model.conv1_extra)
+    tables = [model.edge_embeddings] + list(model.edge_embeddings_extra)
+    for layer in layers:
+        bn = layer.ent_bn
+        if not (bn.track_running_stats and bn.momentum is not None and bn.affine and
+                _native.matmul_tn_supported(layer.in_channels, layer.out_channels)):
+            raise _native.NativeError('train_step_sharded: layer %s is outside the HIP training path' % (layer,))
+    x, rel_e = model.entity_embedding, model.relation_embedding
+    for li, (layer, table) in enumerate(zip(layers, tables)):
+        last = li == len(layers) - 1
+        bn = layer.ent_bn
+        rels = torch.cat([rel_e, layer.loop_rel], dim=0)
+        agg = _ShardAggregateFn.apply(x, rels, table, csr, n0, n1)
+        x_own = x if (n0, n1) == (0, x.size(0)) else x[n0:n1]
+        a_loop = (x_own * rels[-1]) * layer.loop_edge
+        y = _ShardLayerTrainFn.apply(agg, a_loop, layer.in_weight, layer.out_weight, layer.loop_weight, layer.bias, bn.weight,
+                                     bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, layer.drop.p, ex)
+        with torch.no_grad():
+            bn.num_batches_tracked += 1
+        rel_e = torch.matmul(_RankZeroGradFn.apply(rels, ex) if (last and W > 1) else rels, layer.rels_weight)[:-1]
+        y = F.dropout(y, p=model.params.gcn_drop, training=True)
+        x = _GatherRowsFn.apply(y, ex, not last) if W > 1 else y
+    ent = y.contiguous()
+    if W > 1 and generator is None and (model.conv2.feature_drop.p > 0 or model.conv2.hidden_drop.p > 0):
+        generator = torch.Generator(device=ent.device)
+        generator.manual_seed(_agreed_seed(group, ent.device))
+    xt = _trunk(model.conv2, torch.index_select(x, 0, src), torch.index_select(rel_e, 0, rel), generator)
+    if W > 1:
+        xt = _AllReduceGradFn.apply(xt, ex)
+    bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]
+    N = ex.total
+    keys = index.query_keys(src, rel)
+    if _native.score_bce_supported(xt, ent) and n1 > n0:
+        hot, cold = _native.smoothed_targets(lbl_smooth, N)
+        mask = _native.filter_mask(keys, index.keys, index.ptr, index.tails, n1 - n0, ent_row0=n0)
+        loss = _ScoreBCEShardFn.apply(xt, ent, bias, mask, hot, cold, N)
+    elif n1 == n0:      # a rank without entity rows scores nothing, but takes part in the backward's collectives
+        loss = (xt * 0.0).sum()
+    else:               # batch sizes the fused launch does not take: the scores of the rank's entities, then the BCE
+        from .model import _ScoreFn
+        labels = _native.label_rows(keys, index.keys, index.ptr, index.tails, n1 - n0, lbl_smooth=lbl_smooth, num_entities=N,
+                                    ent_row0=n0)
+        scores = _ScoreFn.apply(xt, ent, bias)
+        # one rank: forward_loss's own form (BCELoss's mean); several: the rank's sum over the global count, the ranks' parts add up
+        loss = model.loss_fn(scores, labels) if W == 1 else \
+            F.binary_cross_entropy(scores, labels, reduction='sum') * (1.0 / (xt.size(0) * N))
+    bucket = _bucket_grads(model) if W > 1 else None
+    loss.backward()
+    if W > 1:
+        _reduce_bucket(model, ex, *bucket)
+    if clip is not None:
+        clip_grad_norm_sharded(model, clip, group)
+    optimizer.step()
+    loss = loss.detach().clone()
+    return ex.all_reduce(loss)
+
+
+def train_epoch_sharded(model, queries, index, graph, optimizer, params, batch_size, generator=None, group=None):
+    """One epoch of train_step_sharded, as harness.train_device_labels: `queries` [Q, 2] int64 (DataLoader.train_queries()),
+    `index` = DataLoader.train_index() on the device, shuffled with `generator` — which must be seeded identically on every rank
+    so that every rank takes the same batches. Without one every call draws a new order: at W = 1 from torch's default
+    generator (as harness.train_device_labels, which one epoch then equals bit for bit at dropout 0), at W > 1 from a fresh seed
+    that rank 0 draws and broadcasts. Clips at params.clip_grad, smooths with params.lbl_smooth. Returns the mean of the steps'
+    global losses."""
+    from .utils import RunningAverage
+    world, _ = _world_rank(group)
+    dev = model.entity_embedding.device
+    if generator is None and world > 1:
+        generator = torch.Generator()
+        generator.manual_seed(_agreed_seed(group, dev))
+    model.train()
+    loss_avg = RunningAverage()
+    queries = queries.to(dev)
+    order = torch.randperm(queries.size(0), generator=generator).to(dev)
+    for i in range(0, queries.size(0), batch_size):
+        q = queries.index_select(0, order[i:i + batch_size])
+        loss = train_step_sharded(model, graph, q[:, 0], q[:, 1], index, optimizer, lbl_smooth=params.lbl_smooth,
+                                  clip=params.clip_grad, group=group)
+        loss_avg.update(loss.item())
+    return loss_avg()

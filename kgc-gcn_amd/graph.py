@@ -158,6 +158,46 @@ class GraphCSR(object):
         (i0, i1), (o0, o1), (h0, h1) = self._shard_bounds(n0, n1)
         return i0, o0 - (i1 - i0), h0 - (i1 - i0) - (o1 - o0)
 
+    def shard_backward_index(self, n0, n1):
+        """Index lists of the aggregation backward of destinations [n0, n1) from their table shard (include/mgcn_hip.h (3s)),
+        built once per range from the shard's own slots (never the whole graph's) with stable device sorts, and cached:
+          type_ptr [R + 1], type_rows: the shard's rows grouped by relation-table row, each group in ascending slot order;
+          src_ptr [2N + 1], src_rows: the rows grouped by (source s, half h) — group 2s + h —, each group ordered by the slot of
+            the reverse edge: the order in which the whole graph's backward walks s's destination runs, so that one range
+            covering the graph reproduces its sums bit for bit;
+          src_chunks [hub chunks, 4]: per hub chunk of the graph, the entries of src_rows whose reverse slot lies in it, then
+            the chunk's hub (first chunk, chunk count)."""
+        key = ('bwd', int(n0), int(n1))
+        cache = self.__dict__.setdefault('_shard_cache', {})
+        if key not in cache:
+            (i0, i1), (o0, o1), (h0, h1) = self._shard_bounds(n0, n1)
+            dev, i32 = self.rec.device, torch.int32
+            slots = torch.cat([torch.arange(i0, i1), torch.arange(o0, o1), torch.arange(h0, h1)]).to(dev)   # slot of row r
+            e2, N = 2 * self.num_edges_half, self.num_nodes
+            rec = self.rec.index_select(0, slots).to(torch.int64)
+            half = (self.slot_dst.index_select(0, slots).to(torch.int64) >> 31) & 1
+            typ = rec[:, 1]
+            type_rows = torch.sort(typ, stable=True).indices
+            counts = torch.bincount(typ, minlength=self.num_rel_rows)
+            type_ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)])
+            group = rec[:, 0] * 2 + half
+            skey = group * e2 + self.mirror.index_select(0, slots).to(torch.int64)     # (source, half, reverse slot)
+            skey_sorted, src_rows = torch.sort(skey)
+            counts = torch.bincount(group, minlength=2 * N)
+            src_ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)])
+            src_chunks = torch.zeros((max(self.num_chunks, 1), 4), dtype=torch.int64, device=dev)
+            if self.num_chunks:
+                ch = self.chunks[:self.num_chunks].to(torch.int64)
+                sd = self.slot_dst.index_select(0, ch[:, 0]).to(torch.int64)
+                # the chunk's slots enter hub d in half h: their reverses leave d in half 1 - h
+                base = ((sd & 0x7fffffff) * 2 + (1 - ((sd >> 31) & 1))) * e2
+                src_chunks[:self.num_chunks, 0] = torch.searchsorted(skey_sorted, base + ch[:, 0])
+                src_chunks[:self.num_chunks, 1] = torch.searchsorted(skey_sorted, base + ch[:, 1])
+                src_chunks[:self.num_chunks, 2:] = ch[:, 2:]
+            cache[key] = dict(type_ptr=type_ptr.to(i32), type_rows=type_rows.to(i32), src_ptr=src_ptr.to(i32),
+                              src_rows=src_rows.to(i32), src_chunks=src_chunks.to(i32).contiguous())
+        return cache[key]
+
     def edge_table_shard(self, table_slot_order, n0, n1):
         """Rows of a slot-ordered per-edge table that destinations [n0, n1) need: their in-half slots, their out-half
         slots, then the slots of their hubs (each a contiguous run). 1/W of the table per rank for a balanced partition."""
