@@ -232,7 +232,8 @@ int mgcn_dense_bn_tanh_fwd(int64_t num_nodes, int32_t dim_in, int32_t dim_out, c
  *       (or 64) destinations, stages of 128 input columns per mode, two LDS images, one workgroup barrier per stage;
  *   generation 3, otherwise (dim_in <= 1024, dim_out <= 512), and generation 2's shapes when the caller brings row bounds
  *       for a launch short of two tiles per CU  csrc/layer_fused3.hip: one contiguous run of rows per workgroup in tiles of
- *       48-80, stages of 128 or 256 columns, a ring of f32 staging buffers coupled by LDS counters, 13 or 32 column tiles.
+ *       48-80, stages of 128 input columns (256 through `tune` only), a ring of f32 staging buffers coupled by LDS counters,
+ *       13 or 32 column tiles.
  *       Generations 2 and 3 run the same arithmetic (k order, products, and for dim_out > 128 the weight packing): rows
  *       are bit-identical between them;
  *   generation 4, dim_in <= 256 and dim_out <= 208, ONLY through `tune`  csrc/layer_fused4.hip (round 4's experiment: all
@@ -274,7 +275,8 @@ int mgcn_dense_bn_tanh_fwd(int64_t num_nodes, int32_t dim_in, int32_t dim_out, c
  * tune: 0 = automatic. For A/B runs only (never needed for correctness): bits 0-3 row tiles per tile (3..5); bits 4-7
  * generation 3: staging buffers (1..4), generation 4: slots per gather batch (2 / 4 / 8); bits 8-9 relation table in LDS
  * (1 = never); bits 10-11 force a generation (1 = generation 4, 2, 3; wp_dev must then come from mgcn_pack_weights_gen for
- * it); bits 12-13 generation 3: input columns per slot walk (1 = 128, 2 = 256).
+ * it); bits 12-13 generation 3: input columns per slot walk (0 or 1 = 128, 2 = 256), generation 4: phase groups of its
+ * stagger (1 = none, 0 or 2 = two, 3 = four).
  * status_dev (optional, one zero-initialised uint32 in device memory): generation 3 couples its roles through LDS counters
  * with BOUNDED spins; a spin that runs out (a wave parked for ~0.1 s by a debugger, a preemption, or a protocol error)
  * lets its wave go on, the rows of that tile are then garbage, and bit 0 of *status_dev is set: callers check the word at

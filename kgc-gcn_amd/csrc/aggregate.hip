@@ -1189,19 +1189,21 @@ extern "C" int mgcn_aggregate_bwd(int64_t num_nodes, int64_t num_edges_half, int
     }
     if (num_edges_half < 4 * num_nodes) {   // 42.5 vs 55 us on the WN18RR shape
       MGCN_LAUNCH_GEOM(agg_bwd_gx_short_kernel, p, num_nodes, g, stream);
+      MGCN_CHECK_LAUNCH("agg_bwd_gx_short_kernel");
     } else {
       MGCN_LAUNCH_GEOM(agg_bwd_gx_kernel, p, num_nodes, g, stream);
+      MGCN_CHECK_LAUNCH("agg_bwd_gx_kernel");
     }
-    MGCN_CHECK_LAUNCH("agg_bwd_gx_kernel");
   }
   if (grel_dev) {
     if (p.nchunks_type > 0) {
       if (fused_gee_grel) {
         MGCN_LAUNCH_GEOM(agg_bwd_gee_grel_kernel, p, p.nchunks_type, g, stream);
+        MGCN_CHECK_LAUNCH("agg_bwd_gee_grel_kernel");
       } else {
         MGCN_LAUNCH_GEOM(agg_bwd_grel_partial_kernel, p, p.nchunks_type, g, stream);
+        MGCN_CHECK_LAUNCH("agg_bwd_grel_partial_kernel");
       }
-      MGCN_CHECK_LAUNCH("agg_bwd_grel_partial_kernel");
     }
     launch_grel_final(g, p, num_rel_rows, dim, static_cast<hipStream_t>(stream));
     MGCN_CHECK_LAUNCH("agg_bwd_grel_final_kernel");

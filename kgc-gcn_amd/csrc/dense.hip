@@ -25,13 +25,12 @@
 
 #include <cstdlib>
 
-#include "mgcn_common.h"
+#include "fused_common.h"   // split3p: the one exact bf16 split of the library
 
 namespace {
 
 enum { EPI_NONE = 0, EPI_BN_TANH = 1, EPI_SIGMOID = 2, EPI_TARGET = 3, EPI_RANK = 4, EPI_BCE = 5 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct TileArgs {
   const float *a;        // [M, K], row stride lda (EPI_TARGET: row i is a[(obj[i]-row0)*lda])
@@ -491,22 +490,13 @@ __global__ __launch_bounds__(THREADS, min_waves(EPI, NT)) void tile_kernel(TileA
 // row tiles: 32 bytes of the entity row per lane and k-block straight from global (the next k-block's in flight),
 // split in registers (18 VALU per 8 values), 4 column tiles x 6 MFMAs.
 typedef __bf16 bf16x8s __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2s __attribute__((ext_vector_type(2)));
-typedef float f32x2s __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split3p_(float v0, float v1, uint32_t &h, uint32_t &m, uint32_t &l) {
-  h = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2s{v0, v1}, bf16x2s));
-  const float r0 = v0 - __uint_as_float(h << 16), r1 = v1 - __uint_as_float(h & 0xffff0000u);
-  m = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2s{r0, r1}, bf16x2s));
-  const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-  l = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2s{s0, s1}, bf16x2s));
-}
 __device__ __forceinline__ void split8_(const float4 &lo, const float4 &hi, u32x4s &h, u32x4s &m, u32x4s &l) {
   uint32_t a, b, c;
-  split3p_(lo.x, lo.y, a, b, c); h[0] = a; m[0] = b; l[0] = c;
-  split3p_(lo.z, lo.w, a, b, c); h[1] = a; m[1] = b; l[1] = c;
-  split3p_(hi.x, hi.y, a, b, c); h[2] = a; m[2] = b; l[2] = c;
-  split3p_(hi.z, hi.w, a, b, c); h[3] = a; m[3] = b; l[3] = c;
+  split3p(lo.x, lo.y, a, b, c); h[0] = a; m[0] = b; l[0] = c;
+  split3p(lo.z, lo.w, a, b, c); h[1] = a; m[1] = b; l[1] = c;
+  split3p(hi.x, hi.y, a, b, c); h[2] = a; m[2] = b; l[2] = c;
+  split3p(hi.z, hi.w, a, b, c); h[3] = a; m[3] = b; l[3] = c;
 }
 constexpr int SS_NQT = 4, SS_BQ = SS_NQT * 16, SS_MAX_KB = 11, SS_THREADS = 512;   // 64 queries per strip, K <= 352
 

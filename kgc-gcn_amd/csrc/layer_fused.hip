@@ -5,7 +5,7 @@
 
 #include <cstdlib>
 
-#include "mgcn_common.h"
+#include "fused_common.h"
 
 
 namespace {
@@ -63,10 +63,7 @@ extern "C" int mgcn_pack_weights(int32_t dim_in, int32_t dim_out, const float *w
 // 64 rows on 256 CUs, the heaviest tile 1.15x the mean) and the two packings coincide (O > 128).
 extern "C" int mgcn_fused_kernel_generation(int32_t dim_in, int32_t dim_out, int64_t num_rows, int32_t with_row_bounds) {
   if (!lockstep_shape(dim_in, dim_out)) return 3;
-  int cus = 256, dev = 0;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  const bool few_tiles = (num_rows + 79) / 80 < 2 * int64_t(cus);
+  const bool few_tiles = (num_rows + 79) / 80 < 2 * int64_t(mgcn::cu_count());
   return (with_row_bounds && few_tiles && dim_out > 128) ? 3 : 2;
 }
 
@@ -120,23 +117,12 @@ extern "C" int mgcn_layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, i
                dim_in, dim_out);
   MGCN_REQUIRE(num_row_bounds >= 0 && num_row_bounds <= 4096 && (num_row_bounds == 0 || row_bounds_dev),
                "layer_fwd_fused: bad row bounds");
-  if (gen == 4)
-    return mgcn::fused4_launch(num_nodes, dim_in, dim_out, num_rel_rows, rowptr_dev, rec_dev, x_dev, ldx, rel_dev,
-                               loop_rel_dev, ee_dev, loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev, bn_gamma_dev,
-                               bn_beta_dev, bn_eps, out_dev, ldo, node_begin, node_end, ee_sub_in, ee_sub_out,
-                               num_chunks > 0 ? hubinfo_dev : nullptr, chunk_begin, partial_dev,
-                               want_rel ? rels_weight_dev : nullptr, want_rel ? rel_out_dev : nullptr, row_bounds_dev,
-                               num_row_bounds, tune, stream);
-  if (gen == 2)
-    return mgcn::fused2_launch(num_nodes, dim_in, dim_out, num_rel_rows, rowptr_dev, rec_dev, x_dev, ldx, rel_dev,
-                               loop_rel_dev, ee_dev, loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev, bn_gamma_dev,
-                               bn_beta_dev, bn_eps, out_dev, ldo, node_begin, node_end, ee_sub_in, ee_sub_out,
-                               num_chunks > 0 ? hubinfo_dev : nullptr, chunk_begin, partial_dev,
-                               want_rel ? rels_weight_dev : nullptr, want_rel ? rel_out_dev : nullptr, stream);
-  return mgcn::fused3_launch(num_nodes, dim_in, dim_out, num_rel_rows, rowptr_dev, rec_dev, x_dev, ldx, rel_dev,
-                               loop_rel_dev, ee_dev, loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev, bn_gamma_dev,
-                               bn_beta_dev, bn_eps, out_dev, ldo, node_begin, node_end, ee_sub_in, ee_sub_out,
-                               num_chunks > 0 ? hubinfo_dev : nullptr, chunk_begin, partial_dev,
-                               want_rel ? rels_weight_dev : nullptr, want_rel ? rel_out_dev : nullptr, row_bounds_dev,
-                               num_row_bounds, tune, status_dev, stream);
+  const mgcn::FusedLaunch a = {num_nodes, dim_in, dim_out, num_rel_rows, rowptr_dev, rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev,
+                               loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev, bn_gamma_dev, bn_beta_dev, bn_eps, out_dev, ldo,
+                               node_begin, node_end, ee_sub_in, ee_sub_out, num_chunks > 0 ? hubinfo_dev : nullptr, chunk_begin,
+                               partial_dev, want_rel ? rels_weight_dev : nullptr, want_rel ? rel_out_dev : nullptr, row_bounds_dev,
+                               num_row_bounds, tune, status_dev, stream};
+  if (gen == 4) return mgcn::fused4_launch(a);
+  if (gen == 2) return mgcn::fused2_launch(a);
+  return mgcn::fused3_launch(a);
 }

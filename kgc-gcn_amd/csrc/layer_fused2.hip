@@ -11,7 +11,7 @@
 //              hi.hi, hi.mid, mid.hi, hi.lo, lo.hi, mid.mid (everything down to 2^-16 of |a||w|; what is dropped is
 //              below 2^-24, the rounding of one f32 product), f32 accumulation: f32-faithful at 6/16 of the f32
 //              MFMA's issue time. A wave owns NT/8 column tiles x ALL row tiles of the block tile, so a weight
-//              fragment (three bf16 pieces, pre-split and pre-packed by pack2_kernel, read straight from L2) feeds
+//              fragment (three bf16 pieces, pre-split and pre-packed by pack_kernel<ModeWeights>, read straight from L2) feeds
 //              6 * NRT MFMAs; the operands are swapped (W as the A operand) so that a lane ends up with four
 //              consecutive output columns of one row: the epilogue (/3, bias, BN eval, tanh: model.py:103-106)
 //              runs on the accumulators and stores 16 bytes per lane.
@@ -24,32 +24,13 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "mgcn_common.h"
+#include "fused_common.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int T2 = 1024;   // 8 MFMA waves + 8 gather waves: two of each per SIMD, 128 VGPRs per wave
 
-struct Args2 {
-  const int32_t *rowptr;
-  const int4 *rec;
-  const float *x, *rel, *loop_rel, *ee, *loop_edge;
-  const u32x4 *wp;        // packed weights [G][NT][3][64] (8 bf16 per lane)
-  const float *bias, *bn_mean, *bn_var, *bn_gamma, *bn_beta;
-  float *out;
-  int64_t ldx, ldo;
-  int32_t n, d, o, rel_rows;
-  int32_t node0, node1;   // destinations [node0, node1) are this launch's share; out row 0 = node0
-  int32_t ee_sub[2];      // slot-order per-edge table shard: row of (absolute) slot s of half h = s - ee_sub[h]
-  const int2 *hubinfo;    // [2][N] (first chunk, chunk count) or null
-  const float *partial;   // folded hub totals (pre-pass), row (first chunk - chunk0)
-  int32_t chunk0;
-  const float *rw;        // relation projection: rels_weight [D, O] (model.py:107) or null
-  float *rel_out;         // [rel_rows - 1, O]
+struct Args2 : LayerArgs {   // wp: [G][NT][3][64]
   int32_t nch, nkb_last, kbm, G;   // 128-column chunks per mode, k-blocks of the last chunk, k-blocks per mode / tile
   float bn_eps;
 #ifdef MGCN_DIAG
@@ -67,51 +48,6 @@ struct Args2 {
 #define MGCN_ABLATE(bit) 0
 #define MGCN_STAMP(role, idx) do {} while (0)
 #endif
-
-__device__ __forceinline__ float tanh2_(float v) {   // as layer_fused.hip: exp2 + rcp, 7 VALU per value
-  const float t = __builtin_amdgcn_exp2f(fabsf(v) * -2.885390081777927f);
-  return copysignf((1.0f - t) * __builtin_amdgcn_rcpf(1.0f + t), v);
-}
-
-// Exact three-way split of two f32 values into bf16 pieces, packed {even, odd}: hi = bf16(v) (round to nearest even),
-// mid = bf16(v - hi), lo = v - hi - mid; every difference is exact, so hi + mid + lo == v bit for bit for finite v (see
-// layer_fused3.hip: the same split, the same six products).
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split3p(float v0, float v1, uint32_t &h, uint32_t &m, uint32_t &l) {
-  h = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{v0, v1}, bf16x2));            // v_cvt_pk_bf16_f32
-  const float r0 = v0 - __uint_as_float(h << 16), r1 = v1 - __uint_as_float(h & 0xffff0000u);
-  m = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
-  const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-  l = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{s0, s1}, bf16x2));
-}
-
-// wp[((g * NT + ct) * 3 + piece) * 64 + lane] = 8 bf16: W[mode * D + chunk * 128 + 8 * (4 kb + (lane >> 4)) + i]
-// [16 ct + (lane & 15)], i = 0..7, zero outside; g = mode * kbm + 4 * chunk + kb.
-__global__ __launch_bounds__(256) void pack2_kernel(const float *__restrict__ w, u32x4 *__restrict__ wp, int d, int o,
-                                                    int kbm, int nt, int total) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int lane = idx & 63, piece = (idx >> 6) % 3, ct = ((idx >> 6) / 3) % nt, g = (idx >> 6) / (3 * nt);
-  const int mode = g / kbm, kbi = g - mode * kbm, chunk = kbi >> 2, kb = kbi & 3;
-  const int col = ct * 16 + (lane & 15), k0 = chunk * 128 + 8 * (4 * kb + (lane >> 4));
-  uint32_t bits[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float v[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int k = k0 + 2 * i + j;
-      v[j] = (k < d && col < o) ? w[(int64_t(mode) * d + k) * o + col] : 0.f;
-    }
-    uint32_t h, m, l;
-    split3p(v[0], v[1], h, m, l);
-    bits[i] = piece == 0 ? h : piece == 1 ? m : l;
-  }
-  wp[idx] = u32x4{bits[0], bits[1], bits[2], bits[3]};
-}
-
-__device__ __forceinline__ float4 f4mul2(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 
 // LDS: [2 stage images][epilogue vectors 2 x 208 floats][relation table, when RELLDS]
 constexpr int EPI_FLOATS = 2 * 208;
@@ -178,20 +114,12 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
     // row, raised with the tile's slot count so that no group gets more than 31 rows). A stage ends when its slowest
     // group ends: with 5 rows each the slowest of 16 groups carried ~1.6x the mean slots, by work ~1.15x. Every row's
     // slots are still summed by ONE group in slot order, so sums do not depend on the partition.
-    // Per group, lane l holds the tile's row pointers l, l + 32, l + 64 (clamped to BM); both the pointers and the
-    // group's first slot records are fetched one (tile, mode) ahead, so a stage starts straight at its row loads.
-    struct RowPtrs { int a, b, c; };
+    // Both the row pointers and the group's first slot records are fetched one (tile, mode) ahead, so a stage starts straight
+    // at its row loads.
+    // (rp_get, partition and rec_chunk below are layer_fused3.hip's with nr = BM: kept per kernel, because as functions of
+    // fused_common.h they change the code the compiler emits for these kernels — DESIGN.md)
     auto rp_of = [&](int it_, int mode_) {
-      const int32_t *rp = p.rowptr + int64_t(mode_) * (p.n + 1);
-      const int row0 = p.node0 + (bid + it_ * nblk) * BM;
-      auto at = [&](int i) {
-        int node = row0 + (i < BM ? i : BM);
-        node = node < p.node1 ? node : p.node1;
-        return rp[node];
-      };
-      RowPtrs r;
-      r.a = at(lig); r.b = at(lig + 32); r.c = at(lig + 64);
-      return r;
+      return rp_load(p.rowptr + int64_t(mode_) * (p.n + 1), p.node0 + (bid + it_ * nblk) * BM, BM, p.node1, lig);
     };
     auto rp_get = [&](const RowPtrs &r, int idx) {      // idx group-uniform, 0..BM: the tile's row pointer idx
       const int from = glane0 + (idx & 31);
@@ -330,7 +258,7 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
                     nb = __shfl(myrp, glane0 + (row - e_lo) + 1);
                   }
                   const float4 rr = RELLDS ? *reinterpret_cast<const float4 *>(relb + uint32_t(rtyp[u]) * d32) : rv[u];
-                  const float4 m = f4mul2(f4mul2(xv[u], rr), ev[u]);
+                  const float4 m = f4mul(f4mul(xv[u], rr), ev[u]);
                   const float wgt = __int_as_float(rnrm[u]);
                   sum = make_float4(sum.x + m.x * wgt, sum.y + m.y * wgt, sum.z + m.z * wgt, sum.w + m.w * wgt);
                 }
@@ -365,7 +293,7 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
               xs[i] = *reinterpret_cast<const float4 *>(p.x + int64_t(node) * p.ldx + coff);
             }
 #pragma unroll
-            for (int i = 0; i < RPG; ++i) write_row(img, g_lo + i, f4mul2(f4mul2(xs[i], lr), le), col_ok);
+            for (int i = 0; i < RPG; ++i) write_row(img, g_lo + i, f4mul(f4mul(xs[i], lr), le), col_ok);
             if (wave == 8) MGCN_STAMP(1, 2 * stage + 1);
             stage_barrier();
           }
@@ -373,41 +301,8 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
       }
     }
     // all_rel = rel @ rels_weight (model.py:107), by the gather waves once their last stage is in LDS (the MFMA waves
-    // still have that stage and the last epilogue to go). One item = one relation row x 16 columns per wave: the four
-    // 16-lane groups run the four K quarters of small_matmul_kernel's arithmetic (sequential fmaf chains), the partial
-    // sums are added in quarter order — values bit-identical to the separate launch, one load round trip per 32 k.
-    if (p.rel_out) {
-      const int rows = p.rel_rows - 1, k = p.d, n = p.o;
-      const int ncg = (n + 15) / 16, items = rows * ncg;
-      const int kper = (k + 3) / 4;
-      const int qd = lane >> 4;
-      const int k0 = qd * kper, k1 = (k0 + kper < k) ? k0 + kper : k;
-      for (int item = (wave - 8) * nblk + bid; item < items; item += nblk * 8) {
-        const int row = item / ncg, col = (item - row * ncg) * 16 + (lane & 15);
-        const bool ok = col < n;
-        const float *ap = p.rel + int64_t(row) * k;
-        const float *bp = p.rw + (ok ? col : 0);
-        float a = 0.f;
-        constexpr int UR = 32;
-        for (int i0 = 0; i0 < kper; i0 += UR) {
-          float av[UR], bv[UR];
-#pragma unroll
-          for (int u = 0; u < UR; ++u) {
-            const int kk = k0 + i0 + u;
-            const int kc = (i0 + u < kper && kk < k1) ? kk : 0;
-            av[u] = ap[kc];
-            bv[u] = bp[int64_t(kc) * n];
-          }
-#pragma unroll
-          for (int u = 0; u < UR; ++u) {
-            const int kk = k0 + i0 + u;
-            if (i0 + u < kper && kk < k1) a = fmaf(av[u], bv[u], a);
-          }
-        }
-        const float q1 = __shfl(a, (lane & 15) + 16), q2 = __shfl(a, (lane & 15) + 32), q3 = __shfl(a, (lane & 15) + 48);
-        if (qd == 0 && ok) p.rel_out[int64_t(row) * n + col] = ((a + q1) + q2) + q3;
-      }
-    }
+    // still have that stage and the last epilogue to go)
+    if (p.rel_out) rel_projection(p, wave, 8, 8, lane, bid, nblk);
 #ifdef MGCN_DIAG
     if (p.stamps && lane == 0 && wave == 8) {
       p.stamps[(int64_t(blockIdx.x) * 2 + 1) * 128 + 122] = __builtin_readcyclecounter();
@@ -477,8 +372,8 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
     // lane holds out[row = 16 rt + r][16 ct + 4 gq .. + 3] (operands swapped: W is the MFMA's A operand)
     auto store_unit = [&](f32x4 a, int prow, int col, const float4 &sc, const float4 &sh) {
       if (prow < nrows) {
-        const float4 v = make_float4(tanh2_(fmaf(a[0], sc.x, sh.x)), tanh2_(fmaf(a[1], sc.y, sh.y)),
-                                     tanh2_(fmaf(a[2], sc.z, sh.z)), tanh2_(fmaf(a[3], sc.w, sh.w)));
+        const float4 v = make_float4(tanh_fast(fmaf(a[0], sc.x, sh.x)), tanh_fast(fmaf(a[1], sc.y, sh.y)),
+                                     tanh_fast(fmaf(a[2], sc.z, sh.z)), tanh_fast(fmaf(a[3], sc.w, sh.w)));
         *reinterpret_cast<float4 *>(p.out + int64_t(prow) * p.ldo + col) = v;
       }
     };
@@ -532,20 +427,9 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
     // to the gather waves by the first stage barrier.
     if (H == 0) {
       const int t8 = (wave & 3) * 64 + lane;
-      if (t8 < 208) {
-        const int c = t8;
-        const bool in = c < p.o;
-        const float inv = in ? __builtin_amdgcn_rsqf(p.bn_var[c] + p.bn_eps) * p.bn_gamma[c] : 0.f;
-        constexpr float third = 1.0f / 3.0f;   // (sum of the three modes) / 3, model.py:103, as a multiplication (<= 1 ulp)
-        epi[c] = inv * third;
-        epi[208 + c] = in ? ((p.bias ? p.bias[c] : 0.f) - p.bn_mean[c]) * inv + p.bn_beta[c] : 0.f;
-      }
+      if (t8 < 208) epilogue_table_entry(p, p.bn_eps, epi, 208, t8);
     }
-    if (RELLDS) {
-      const int n4 = ((p.rel_rows - 1) * p.d) >> 2;
-      for (int i = wave * 64 + lane; i < n4; i += 512)
-        reinterpret_cast<float4 *>(rel_lds)[i] = reinterpret_cast<const float4 *>(p.rel)[i];
-    }
+    if (RELLDS) copy_rel_table(p, rel_lds, wave, lane, 8);
     auto kblock = [&](u32x4 (&wq)[QF][3], u32x4 (&wx)[XW][3], u32x4 (&nq)[QF][3], u32x4 (&nx)[XW][3]) {
       wload(nq, nx, gindex());           // the k-block after this one (wraps into the next tile: same weights)
       advance_next();
@@ -649,7 +533,7 @@ Shape2 shape2(int d) {
   s.nch = (d + 127) / 128;
   const int wlast = d - 128 * (s.nch - 1);
   s.nkb_last = (wlast + 31) / 32;
-  s.kbm = 4 * (s.nch - 1) + s.nkb_last;
+  s.kbm = 4 * (s.nch - 1) + s.nkb_last;   // = ceil(d / 32), pack_modes_kbm
   s.G = 3 * s.kbm;
   return s;
 }
@@ -681,52 +565,29 @@ bool fused2_takes(int32_t dim_in, int32_t dim_out) {
   return dim_in > 0 && dim_in % 4 == 0 && dim_in <= 1024 && dim_out > 0 && dim_out % 4 == 0 && dim_out <= 208;
 }
 
-size_t fused2_packed_bytes(int32_t dim_in, int32_t dim_out) {
-  return size_t(shape2(dim_in).G) * pick_nt2(dim_out) * 3 * 64 * 16;
-}
+size_t fused2_packed_bytes(int32_t dim_in, int32_t dim_out) { return pack_modes_bytes(dim_in, pick_nt2(dim_out)); }
 
 int fused2_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_dev, void *stream) {
-  const Shape2 s = shape2(dim_in);
-  const int nt = pick_nt2(dim_out);
-  const int total = s.G * nt * 3 * 64;
-  hipLaunchKernelGGL(pack2_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w_dev,
-                     reinterpret_cast<u32x4 *>(wp_dev), dim_in, dim_out, s.kbm, nt, total);
-  MGCN_CHECK_LAUNCH("pack2_kernel");
-  return MGCN_OK;
+  const int kbm = pack_modes_kbm(dim_in);
+  return pack_launch(wp_dev, 3 * kbm, pick_nt2(dim_out), ModeWeights{w_dev, dim_in, dim_out, kbm}, stream);
 }
 
-int fused2_launch(int64_t num_nodes, int32_t dim_in, int32_t dim_out, int32_t num_rel_rows, const int32_t *rowptr_dev,
-                  const mgcn_edge_rec *rec_dev, const float *x_dev, int64_t ldx, const float *rel_dev,
-                  const float *loop_rel_dev, const float *ee_dev, const float *loop_edge_dev, const void *wp_dev,
-                  const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev, const float *bn_gamma_dev,
-                  const float *bn_beta_dev, float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin,
-                  int64_t node_end, int64_t ee_sub_in, int64_t ee_sub_out, const int32_t *hubinfo_dev, int64_t chunk_begin,
-                  const float *partial_dev, const float *rels_weight_dev, float *rel_out_dev, void *stream) {
+int fused2_launch(const FusedLaunch &a) {
+  const int32_t dim_in = a.dim_in, dim_out = a.dim_out;
   const Shape2 s = shape2(dim_in);
   Args2 p = {};
-  p.rowptr = rowptr_dev; p.rec = reinterpret_cast<const int4 *>(rec_dev);
-  p.x = x_dev; p.rel = rel_dev; p.loop_rel = loop_rel_dev; p.ee = ee_dev; p.loop_edge = loop_edge_dev;
-  p.wp = reinterpret_cast<const u32x4 *>(wp_dev);
-  p.bias = bias_dev; p.bn_mean = bn_mean_dev; p.bn_var = bn_var_dev; p.bn_gamma = bn_gamma_dev; p.bn_beta = bn_beta_dev;
-  p.out = out_dev; p.ldx = ldx; p.ldo = ldo;
-  p.n = int32_t(num_nodes); p.d = dim_in; p.o = dim_out; p.rel_rows = num_rel_rows;
-  p.node0 = int32_t(node_begin); p.node1 = int32_t(node_end);
-  p.ee_sub[0] = int32_t(ee_sub_in); p.ee_sub[1] = int32_t(ee_sub_out);
-  p.hubinfo = reinterpret_cast<const int2 *>(hubinfo_dev); p.partial = partial_dev; p.chunk0 = int32_t(chunk_begin);
-  p.rw = rel_out_dev ? rels_weight_dev : nullptr; p.rel_out = rel_out_dev;
+  fill_layer_args(p, a);
   p.nch = s.nch; p.nkb_last = s.nkb_last; p.kbm = s.kbm; p.G = s.G;
-  p.bn_eps = bn_eps;
+  p.bn_eps = a.bn_eps;
 #ifdef MGCN_DIAG
   if (const char *ab = getenv("MGCN_FUSED_ABLATE")) p.ablate = atoi(ab);
   p.stamps = diag_stamps();
 #endif
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const int cus = cu_count();
   // Tile height: 80 rows (5 row tiles per weight fragment) unless 64-row tiles finish the launch in fewer row-steps on
   // this chip (makespan = tiles per CU, rounded up, x rows per tile): FB15k-237's 14 541 rows are one 64-row tile on
   // 228 CUs instead of one 80-row tile on 182.
-  const int64_t nrows = node_end - node_begin;
+  const int64_t nrows = a.node_end - a.node_begin;
   auto grid_for = [&](int rt) { const int64_t t = (nrows + rt * 16 - 1) / (rt * 16); return int(t < cus ? (t > 0 ? t : 1) : cus); };
   auto makespan = [&](int bm) { return ((nrows + bm - 1) / bm + cus - 1) / cus * bm; };
   int nrt = makespan(64) < makespan(80) ? 4 : 5;
@@ -734,11 +595,11 @@ int fused2_launch(int64_t num_nodes, int32_t dim_in, int32_t dim_out, int32_t nu
   if (const char *e = getenv("MGCN_FUSED_NRT")) nrt = atoi(e) == 4 ? 4 : 5;
 #endif
   const int grid = grid_for(nrt);                          // persistent: one workgroup per CU
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = static_cast<hipStream_t>(a.stream);
   // the relation table rides in LDS when it fits beside the stage images (a third of the gather's row loads)
-  const bool rel_lds = rel_dev && size_t(num_rel_rows - 1) * dim_in * 4 <= size_t(REL_LDS_MAX_BYTES);
+  const bool rel_lds = a.rel && size_t(a.num_rel_rows - 1) * dim_in * 4 <= size_t(REL_LDS_MAX_BYTES);
   // NT = 13 (the 200-wide layers) has all variants; narrower outputs take the general one
-  const bool hubs = hubinfo_dev != nullptr;
+  const bool hubs = a.hubinfo != nullptr;
   switch (pick_nt2(dim_out)) {
     case 2: return launch2<2, 5, false, true>(p, grid_for(5), st);
     case 4: return launch2<4, 5, false, true>(p, grid_for(5), st);

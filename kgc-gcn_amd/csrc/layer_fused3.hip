@@ -11,7 +11,7 @@
 //               rows are dealt to the groups by work; a group sums its rows' slots in slot order (the sums of
 //               agg_fwd_kernel) and writes each finished row, split exactly into three bf16 pieces, to an LDS image.
 //   waves 0-7   MULTIPLY  v_mfma_f32_16x16x32_bf16 on the six significant products of the split operands (f32-faithful:
-//               see split3 below / DESIGN.md), weights pre-split and pre-packed, streamed from L2 one k-block ahead;
+//               see split3p in fused_common.h / DESIGN.md), weights pre-split and pre-packed, streamed from L2 one k-block ahead;
 //               epilogue tanh(acc * scale + shift) (model.py:103-106) on the accumulators.
 // Stage = (mode, pass of 128 * NCH columns). The gather role is the launch's critical path (its waves run ~15 cycles per
 // instruction beside the MFMA waves' LDS traffic), the multiply role has slack: so the gather only STORES finished f32
@@ -25,34 +25,15 @@
 
 #include <type_traits>
 
-#include "mgcn_common.h"
+#include "fused_common.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int T3 = 1024;
 constexpr int SPIN_LIMIT = 1 << 22;   // bounded spins: a protocol error (or a wave parked by a debugger / preemption for ~0.1 s)
                                       // never hangs a wave; it is REPORTED through Args3::status, the caller's status word
 
-struct Args3 {
-  const int32_t *rowptr;
-  const int4 *rec;
-  const float *x, *rel, *loop_rel, *ee, *loop_edge;
-  const u32x4 *wp;        // packed weights [G][NT][3][64] (8 bf16 per lane), pack3_kernel
-  const float *bias, *bn_mean, *bn_var, *bn_gamma, *bn_beta;
-  float *out;
-  int64_t ldx, ldo;
-  int32_t n, d, o, rel_rows;
-  int32_t node0, node1;   // destinations [node0, node1) are this launch's share; out row 0 = node0
-  int32_t ee_sub[2];      // slot-order per-edge table shard: row of (absolute) slot s of half h = s - ee_sub[h]
-  const int2 *hubinfo;    // [2][N] (first chunk, chunk count) or null
-  const float *partial;   // folded hub totals (pre-pass), row (first chunk - chunk0)
-  int32_t chunk0;
-  const float *rw;        // relation projection: rels_weight [D, O] (model.py:107) or null
-  float *rel_out;         // [rel_rows - 1, O]
+struct Args3 : LayerArgs {   // wp: [G][NT][3][64], pack_kernel<ModeWeights>
   int32_t npass, nkb_last, kbp, kbm, G;   // passes per mode, k-blocks of the last pass / of a full pass / per mode / per tile
   int32_t ncc;            // 16-byte chunk columns of a stage image (8 bf16 each)
   int32_t rows_per_wg, nimg;
@@ -70,32 +51,6 @@ struct Args3 {
 #define DIAG_NOW() 0ull
 #define DIAG_LAP(acc) do {} while (0)
 #endif
-
-__device__ __forceinline__ float tanh3_(float v) {   // exp2 + rcp, 7 VALU per value
-  const float t = __builtin_amdgcn_exp2f(fabsf(v) * -2.885390081777927f);
-  return copysignf((1.0f - t) * __builtin_amdgcn_rcpf(1.0f + t), v);
-}
-
-// Exact three-way split of two f32 values into bf16 pieces, packed {even, odd}: hi = bf16(v) (round to nearest even),
-// mid = bf16(v - hi), lo = v - hi - mid. Each difference is exact (v - hi has at most 16 significant bits, the next
-// one at most 8), so hi + mid + lo == v bit for bit for finite v. Rounding (not truncating) keeps every residual at
-// most HALF an ulp of the piece above it, with either sign: the cross terms the multiply drops (mid x lo, lo x mid, lo x
-// lo) are below 2^-26 |a| |w| and unbiased, where a truncating split leaves 2^-24 with the sign of the product
-// (tests/test_gpu_round3.py feeds rows with 2^40 of dynamic range). A non-finite v gives NaN pieces: the output row is
-// NaN where the exact-f32 path may give +-1 (documented in DESIGN.md).
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split3p(float v0, float v1, uint32_t &h, uint32_t &m, uint32_t &l) {
-  h = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{v0, v1}, bf16x2));            // v_cvt_pk_bf16_f32
-  const float r0 = v0 - __uint_as_float(h << 16), r1 = v1 - __uint_as_float(h & 0xffff0000u);
-  m = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
-  const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-  l = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{s0, s1}, bf16x2));
-}
-__device__ __forceinline__ float4 f4mul3(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 f4axpy(float4 s, float4 m, float w) {
-  return make_float4(s.x + m.x * w, s.y + m.y * w, s.z + m.z * w, s.w + m.w * w);
-}
 
 // LDS counters: [0..3] rows staged per staging buffer, [4..7] buffer converted (free again), [8] one-time tables ready,
 // [9] MFMA waves that have converted their share of the current stage, [10] MFMA waves done multiplying a stage
@@ -212,24 +167,16 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
     // tile's slot count so that no group gets more than 31 rows). Every row's slots are summed by ONE group in slot
     // order, so sums do not depend on the partition, the tile or the launch. Lane l holds the tile's row pointers
     // l, l + 32, l + 64 (clamped); pointers and the group's first slot records are fetched one (tile, mode) ahead.
-    struct RowPtrs { int a, b, c; };
     auto tile_rows16 = [&](int it_) {
       const int left = myrows - it_ * BM;
       const int r = left < BM ? left : BM;
       return (r + 15) & ~15;
     };
     auto rp_of = [&](int it_, int mode_) {
-      const int32_t *rp = p.rowptr + int64_t(mode_) * (p.n + 1);
-      const int row0 = row_lo + it_ * BM;
-      auto at = [&](int i) {
-        int node = row0 + (i < BM ? i : BM);
-        node = node < row_hi ? node : row_hi;
-        return rp[node];
-      };
-      RowPtrs r;
-      r.a = at(lig); r.b = at(lig + 32); r.c = at(lig + 64);
-      return r;
+      return rp_load(p.rowptr + int64_t(mode_) * (p.n + 1), row_lo + it_ * BM, BM, row_hi, lig);
     };
+    // (rp_get, partition and rec_chunk below are layer_fused2.hip's with a run-time tile height: kept per kernel, because as
+    // functions of fused_common.h they change the code the compiler emits for these kernels — DESIGN.md)
     auto rp_get = [&](const RowPtrs &r, int idx) {      // idx group-uniform, 0..BM: the tile's row pointer idx
       const int from = glane0 + (idx & 31);
       const int va = __shfl(r.a, from), vb = __shfl(r.b, from), vc = __shfl(r.c, from);
@@ -385,7 +332,7 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
 #pragma unroll
                   for (int j = 0; j < NCH; ++j) {
                     const float4 rr = RELLDS ? *reinterpret_cast<const float4 *>(relbase + coff[j] + uint32_t(rtyp[u]) * d32) : rv[u][j];
-                    sum[j] = f4axpy(sum[j], f4mul3(f4mul3(xv[u][j], rr), ev[u][j]), wgt);
+                    sum[j] = f4axpy(sum[j], f4mul(f4mul(xv[u][j], rr), ev[u][j]), wgt);
                   }
                 }
               }
@@ -427,7 +374,7 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
               if (g_lo + i < nr) {
                 float4 v[NCH];
 #pragma unroll
-                for (int j = 0; j < NCH; ++j) v[j] = f4mul3(f4mul3(xs[i][j], lr[j]), le[j]);
+                for (int j = 0; j < NCH; ++j) v[j] = f4mul(f4mul(xs[i][j], lr[j]), le[j]);
                 write_row(img, g_lo + i, v, col_ok);
               }
             }
@@ -437,41 +384,8 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
       }
     }
     // all_rel = rel @ rels_weight (model.py:107), by the gather waves once their last stage is in LDS (the MFMA waves
-    // still have stages and the last epilogue to go). One item = one relation row x 16 columns per wave: the four
-    // 16-lane groups run the four K quarters of small_matmul_kernel's arithmetic (sequential fmaf chains), the partial
-    // sums are added in quarter order — values bit-identical to the separate launch, one load round trip per 32 k.
-    if (p.rel_out) {
-      const int rows = p.rel_rows - 1, k = p.d, n = p.o;
-      const int ncg = (n + 15) / 16, items = rows * ncg;
-      const int kper = (k + 3) / 4;
-      const int qd = lane >> 4;
-      const int k0 = qd * kper, k1 = (k0 + kper < k) ? k0 + kper : k;
-      for (int item = (wave - 8) * nblk + bid; item < items; item += nblk * 8) {
-        const int row = item / ncg, col = (item - row * ncg) * 16 + (lane & 15);
-        const bool ok = col < n;
-        const float *ap = p.rel + int64_t(row) * k;
-        const float *bp = p.rw + (ok ? col : 0);
-        float a = 0.f;
-        constexpr int UR = 32;
-        for (int i0 = 0; i0 < kper; i0 += UR) {
-          float av[UR], bv[UR];
-#pragma unroll
-          for (int u = 0; u < UR; ++u) {
-            const int kk = k0 + i0 + u;
-            const int kc = (i0 + u < kper && kk < k1) ? kk : 0;
-            av[u] = ap[kc];
-            bv[u] = bp[int64_t(kc) * n];
-          }
-#pragma unroll
-          for (int u = 0; u < UR; ++u) {
-            const int kk = k0 + i0 + u;
-            if (i0 + u < kper && kk < k1) a = fmaf(av[u], bv[u], a);
-          }
-        }
-        const float q1 = __shfl(a, (lane & 15) + 16), q2 = __shfl(a, (lane & 15) + 32), q3 = __shfl(a, (lane & 15) + 48);
-        if (qd == 0 && ok) p.rel_out[int64_t(row) * n + col] = ((a + q1) + q2) + q3;
-      }
-    }
+    // still have stages and the last epilogue to go)
+    if (p.rel_out) rel_projection(p, wave, 8, 8, lane, bid, nblk);
     diag_end();
   } else {
     // ------------------------------------------------------------------------------------------ MULTIPLY
@@ -510,8 +424,8 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
     // lane holds out[row = 16 rt + r][16 ct + 4 gq .. + 3] (operands swapped: W is the MFMA's A operand)
     auto store_unit = [&](f32x4 a, int node, int col, const float4 &sc, const float4 &sh) {
       if (node < row_hi) {
-        const float4 v = make_float4(tanh3_(fmaf(a[0], sc.x, sh.x)), tanh3_(fmaf(a[1], sc.y, sh.y)),
-                                     tanh3_(fmaf(a[2], sc.z, sh.z)), tanh3_(fmaf(a[3], sc.w, sh.w)));
+        const float4 v = make_float4(tanh_fast(fmaf(a[0], sc.x, sh.x)), tanh_fast(fmaf(a[1], sc.y, sh.y)),
+                                     tanh_fast(fmaf(a[2], sc.z, sh.z)), tanh_fast(fmaf(a[3], sc.w, sh.w)));
         *reinterpret_cast<float4 *>(p.out + int64_t(node - p.node0) * p.ldo + col) = v;
       }
     };
@@ -560,19 +474,9 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
     // (model.py:103-106 as one fma: tanh(acc * scale + shift)) and, when it fits, the relation table; published through
     // the `ready` counter.
     if (H == 0) {
-      for (int c = (wave & 3) * 64 + lane; c < OP; c += 256) {
-        const bool in = c < p.o;
-        const float inv = in ? __builtin_amdgcn_rsqf(p.bn_var[c] + p.bn_eps) * p.bn_gamma[c] : 0.f;
-        constexpr float third = 1.0f / 3.0f;   // (sum of the three modes) / 3, model.py:103, as a multiplication (<= 1 ulp)
-        epi[c] = inv * third;
-        epi[OP + c] = in ? ((p.bias ? p.bias[c] : 0.f) - p.bn_mean[c]) * inv + p.bn_beta[c] : 0.f;
-      }
+      for (int c = (wave & 3) * 64 + lane; c < OP; c += 256) epilogue_table_entry(p, p.bn_eps, epi, OP, c);
     }
-    if (RELLDS) {
-      const int n4 = ((p.rel_rows - 1) * p.d) >> 2;
-      for (int i = wave * 64 + lane; i < n4; i += 512)
-        reinterpret_cast<float4 *>(rel_lds)[i] = reinterpret_cast<const float4 *>(p.rel)[i];
-    }
+    if (RELLDS) copy_rel_table(p, rel_lds, wave, lane, 8);
     signal_add(cnt + 8, lane);
     int m_img = 0;
     uint32_t m_round = 0, m_stage = 0;
@@ -715,31 +619,6 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
 
 int pick_nt3(int o) { return o <= 208 ? 13 : 32; }   // column tiles of the multiply role (narrower outputs ride along zero-padded)
 
-// wp[((g * NT + ct) * 3 + piece) * 64 + lane] = 8 bf16: W[mode * D + 32 kbi + 8 (lane >> 4) + i][16 ct + (lane & 15)],
-// i = 0..7, zero outside; g = mode * kbm + kbi (k-block kbi of the mode: 32 consecutive input columns).
-__global__ __launch_bounds__(256) void pack3_kernel(const float *__restrict__ w, u32x4 *__restrict__ wp, int d, int o,
-                                                    int kbm, int nt, int total) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int lane = idx & 63, piece = (idx >> 6) % 3, ct = ((idx >> 6) / 3) % nt, g = (idx >> 6) / (3 * nt);
-  const int mode = g / kbm, kbi = g - mode * kbm;
-  const int col = ct * 16 + (lane & 15), k0 = 32 * kbi + 8 * (lane >> 4);
-  uint32_t bits[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float v[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int k = k0 + 2 * i + j;
-      v[j] = (k < d && col < o) ? w[(int64_t(mode) * d + k) * o + col] : 0.f;
-    }
-    uint32_t h, m, l;
-    split3p(v[0], v[1], h, m, l);
-    bits[i] = piece == 0 ? h : piece == 1 ? m : l;
-  }
-  wp[idx] = u32x4{bits[0], bits[1], bits[2], bits[3]};
-}
-
 struct Shape3 {
   int nch, npass, nkb_last, kbp, kbm, G, ncc;
 };
@@ -754,7 +633,7 @@ Shape3 shape3(int d, int nch = 0) {   // nch: float4 per lane and slot walk (0 =
   const int wlast = d - wpass * (s.npass - 1);
   s.nkb_last = (wlast + 31) / 32;
   s.kbp = 4 * s.nch;
-  s.kbm = s.kbp * (s.npass - 1) + s.nkb_last;
+  s.kbm = s.kbp * (s.npass - 1) + s.nkb_last;   // = ceil(d / 32) whatever nch, pack_modes_kbm
   s.G = 3 * s.kbm;
   const int w0 = d < wpass ? d : wpass;
   s.ncc = (w0 + 7) / 8;
@@ -818,63 +697,41 @@ bool fused3_takes(int32_t dim_in, int32_t dim_out) {
   return dim_in > 0 && dim_in % 4 == 0 && dim_in <= 1024 && dim_out > 0 && dim_out % 4 == 0 && dim_out <= 512;
 }
 
-size_t fused3_packed_bytes(int32_t dim_in, int32_t dim_out) { return size_t(shape3(dim_in).G) * pick_nt3(dim_out) * 3 * 64 * 16; }
+size_t fused3_packed_bytes(int32_t dim_in, int32_t dim_out) { return pack_modes_bytes(dim_in, pick_nt3(dim_out)); }
 
 int fused3_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_dev, void *stream) {
-  const Shape3 s = shape3(dim_in);
-  const int nt = pick_nt3(dim_out);
-  const int total = s.G * nt * 3 * 64;
-  hipLaunchKernelGGL(pack3_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w_dev,
-                     reinterpret_cast<u32x4 *>(wp_dev), dim_in, dim_out, s.kbm, nt, total);
-  MGCN_CHECK_LAUNCH("pack3_kernel");
-  return MGCN_OK;
+  const int kbm = pack_modes_kbm(dim_in);
+  return pack_launch(wp_dev, 3 * kbm, pick_nt3(dim_out), ModeWeights{w_dev, dim_in, dim_out, kbm}, stream);
 }
 
 // tune: 0 = automatic; bits 0-3 row tiles per tile (3 / 4 / 5), bits 4-7 staging buffers (1..4), bits 8-9 relation table in LDS
 // (1 = never, 2 = whenever it fits), bits 12-13 columns per slot walk (1 = 128, 2 = 256): for A/B runs (tools/), never
 // needed for correctness (the packed weights do not depend on it).
-int fused3_launch(int64_t num_nodes, int32_t dim_in, int32_t dim_out, int32_t num_rel_rows, const int32_t *rowptr_dev,
-                  const mgcn_edge_rec *rec_dev, const float *x_dev, int64_t ldx, const float *rel_dev,
-                  const float *loop_rel_dev, const float *ee_dev, const float *loop_edge_dev, const void *wp_dev,
-                  const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev, const float *bn_gamma_dev,
-                  const float *bn_beta_dev, float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin,
-                  int64_t node_end, int64_t ee_sub_in, int64_t ee_sub_out, const int32_t *hubinfo_dev, int64_t chunk_begin,
-                  const float *partial_dev, const float *rels_weight_dev, float *rel_out_dev, const int32_t *row_bounds_dev,
-                  int32_t num_row_bounds, int32_t tune, uint32_t *status_dev, void *stream) {
+int fused3_launch(const FusedLaunch &a) {
+  const int32_t dim_in = a.dim_in, dim_out = a.dim_out, tune = a.tune;
   const int t_nch = (tune >> 12) & 3;
   if (t_nch > 2) return mgcn::fail(MGCN_EINVAL, "layer_fwd_fused: bad tune %d", tune);
   const Shape3 s = shape3(dim_in, t_nch);
   Args3 p = {};
-  p.rowptr = rowptr_dev; p.rec = reinterpret_cast<const int4 *>(rec_dev);
-  p.x = x_dev; p.rel = rel_dev; p.loop_rel = loop_rel_dev; p.ee = ee_dev; p.loop_edge = loop_edge_dev;
-  p.wp = reinterpret_cast<const u32x4 *>(wp_dev);
-  p.bias = bias_dev; p.bn_mean = bn_mean_dev; p.bn_var = bn_var_dev; p.bn_gamma = bn_gamma_dev; p.bn_beta = bn_beta_dev;
-  p.out = out_dev; p.ldx = ldx; p.ldo = ldo;
-  p.n = int32_t(num_nodes); p.d = dim_in; p.o = dim_out; p.rel_rows = num_rel_rows;
-  p.node0 = int32_t(node_begin); p.node1 = int32_t(node_end);
-  p.ee_sub[0] = int32_t(ee_sub_in); p.ee_sub[1] = int32_t(ee_sub_out);
-  p.hubinfo = reinterpret_cast<const int2 *>(hubinfo_dev); p.partial = partial_dev; p.chunk0 = int32_t(chunk_begin);
-  p.rw = rel_out_dev ? rels_weight_dev : nullptr; p.rel_out = rel_out_dev;
+  fill_layer_args(p, a);
   p.npass = s.npass; p.nkb_last = s.nkb_last; p.kbp = s.kbp; p.kbm = s.kbm; p.G = s.G; p.ncc = s.ncc;
-  p.bn_eps = bn_eps;
-  p.status = status_dev;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  p.bn_eps = a.bn_eps;
+  p.status = a.status;
+  const int cus = cu_count();
   // one contiguous run of rows per workgroup, a multiple of 16; one workgroup per CU
-  const int64_t nrows = node_end - node_begin;
+  const int64_t nrows = a.node_end - a.node_begin;
   int64_t rpw = ((nrows + cus - 1) / cus + 15) / 16 * 16;
   if (rpw < 16) rpw = 16;
   int grid = int(nrows > 0 ? (nrows + rpw - 1) / rpw : 1);
   p.rows_per_wg = int32_t(rpw);
-  if (row_bounds_dev && num_row_bounds > 0 && nrows > 0) {   // the caller's runs, one workgroup each (at most one per CU is the point)
-    p.bounds = row_bounds_dev;
-    grid = num_row_bounds;
+  if (a.row_bounds && a.num_row_bounds > 0 && nrows > 0) {   // the caller's runs, one workgroup each (at most one per CU is the point)
+    p.bounds = a.row_bounds;
+    grid = a.num_row_bounds;
     const int64_t per = (nrows + grid - 1) / grid;            // (GraphCSR.workgroup_bounds caps its runs by the same rule)
     rpw = per <= 80 ? (per + 15) / 16 * 16 : (per + 79) / 80 * 80;
   }
   const int nt = pick_nt3(dim_out);
-  const size_t rel_bytes = rel_dev ? size_t(num_rel_rows - 1) * dim_in * 4 : 0;
+  const size_t rel_bytes = a.rel ? size_t(a.num_rel_rows - 1) * dim_in * 4 : 0;
   // Geometry: the tallest tile (weight fragments feed 6 * NRT MFMAs) that leaves room for three staging buffers, else two;
   // the relation table rides in LDS when it fits beside them (a third of the gather's row loads). Tiles taller than
   // the run are pointless.
@@ -898,7 +755,7 @@ int fused3_launch(int64_t num_nodes, int32_t dim_in, int32_t dim_out, int32_t nu
         }
       }
     }
-    if (!nrt && fits(3, 1, false)) { nrt = 3; nimg = 1; }   // 256-column passes (D > 248): one staging buffer
+    if (!nrt && fits(3, 1, false)) { nrt = 3; nimg = 1; }   // last resort, one staging buffer (256-column passes needed it for D > 248; 128-column passes always fit two)
     if (!nrt) return mgcn::fail(MGCN_EUNSUPPORTED, "layer_fwd_fused: no tile geometry fits the LDS (D=%d O=%d)", dim_in, dim_out);
   }
   p.nimg = nimg;
@@ -906,7 +763,7 @@ int fused3_launch(int64_t num_nodes, int32_t dim_in, int32_t dim_out, int32_t nu
   p.diag = diag_buf3();
 #endif
   const size_t lds = lds_bytes3(s, nrt, nimg, nt, rel_lds ? rel_bytes : 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = static_cast<hipStream_t>(a.stream);
   if (nt == 32) {
     if (s.nch == 1) return launch3_rel<32, 3, 1>(p, grid, lds, rel_lds, st);
     return launch3_rel<32, 3, 2>(p, grid, lds, rel_lds, st);

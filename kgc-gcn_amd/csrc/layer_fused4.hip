@@ -9,7 +9,7 @@
 //      whole stage: up to 320 columns of the CONCATENATED K axis [in-half | self loop | out-half] (a 100-wide layer:
 //      all three modes = one stage per tile; a 200-wide layer: two stages, only the cheap self-loop mode is cut);
 //   M  four waves per SIMD issue v_mfma_f32_16x16x32_bf16 back to back (the six significant products of the split
-//      operands, f32 accumulation: f32-faithful, see layer_fused3.hip / DESIGN.md): wave (simd, j < 3) owns column
+//      operands, f32 accumulation: f32-faithful, see split3p in fused_common.h / DESIGN.md): wave (simd, j < 3) owns column
 //      tile 3 simd + j for all row tiles, wave (simd, 3) the 13th column tile's row tiles simd, simd + 4; weights
 //      pre-split, pre-packed in the concatenated K order (pack4_kernel), streamed from L2 one k-block ahead. The
 //      three modes' K tails are folded: K = 3 D is padded ONCE (300 -> 320, 600 -> 608), not per mode (3 x 128,
@@ -29,37 +29,16 @@
 
 #include <type_traits>
 
-#include "mgcn_common.h"
+#include "fused_common.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int T4 = 1024;
 constexpr int NT4 = 13;        // column tiles of the multiply (O <= 208; narrower outputs ride along zero-padded)
 constexpr int OP4 = NT4 * 16;
 constexpr int SKB4 = 10;       // k-blocks (of 32 columns of the concatenated K axis) per stage image
 
-struct Args4 {
-  const int32_t *rowptr;
-  const int4 *rec;
-  const float *x, *rel, *loop_rel, *ee, *loop_edge;
-  const u32x4 *wp;        // packed weights [KB][NT4][3][64] (8 bf16 per lane), pack4_kernel
-  const float *bias, *bn_mean, *bn_var, *bn_gamma, *bn_beta;
-  float *out;
-  int64_t ldx, ldo;
-  int32_t n, d, o, rel_rows;
-  int32_t node0, node1;   // destinations [node0, node1) are this launch's share; out row 0 = node0
-  int32_t ee_sub[2];      // slot-order per-edge table shard: row of (absolute) slot s of half h = s - ee_sub[h]
-  const int2 *hubinfo;    // [2][N] (first chunk, chunk count) or null
-  const float *partial;   // folded hub totals (pre-pass), row (first chunk - chunk0)
-  int32_t chunk0;
-  const float *rw;        // relation projection: rels_weight [D, O] (model.py:107) or null
-  float *rel_out;         // [rel_rows - 1, O]
+struct Args4 : LayerArgs {   // wp: [KB][NT4][3][64], pack4_kernel
   int32_t kb_total, nstage, skb, ncc;   // k-blocks of the K axis, stages per tile, k-blocks per stage, 16-B chunk columns of the image
   int32_t rows_per_wg;
   int32_t nphase;         // phase groups of the stagger (1 = none): group ph's FIRST tile is cut so that its gather phases fall into the others' multiply phases
@@ -77,24 +56,6 @@ struct Args4 {
 #else
 #define STAMP4(idx) do {} while (0)
 #endif
-
-__device__ __forceinline__ float tanh4_(float v) {   // exp2 + rcp, 7 VALU per value
-  const float t = __builtin_amdgcn_exp2f(fabsf(v) * -2.885390081777927f);
-  return copysignf((1.0f - t) * __builtin_amdgcn_rcpf(1.0f + t), v);
-}
-
-// Exact three-way split (layer_fused3.hip): hi = bf16(v) rounded to nearest, mid = bf16(v - hi), lo = v - hi - mid.
-__device__ __forceinline__ void split3p(float v0, float v1, uint32_t &h, uint32_t &m, uint32_t &l) {
-  h = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{v0, v1}, bf16x2));            // v_cvt_pk_bf16_f32
-  const float r0 = v0 - __uint_as_float(h << 16), r1 = v1 - __uint_as_float(h & 0xffff0000u);
-  m = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
-  const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-  l = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{s0, s1}, bf16x2));
-}
-__device__ __forceinline__ float4 f4mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 f4axpy4(float4 s, float4 m, float w) {
-  return make_float4(s.x + m.x * w, s.y + m.y * w, s.z + m.z * w, s.w + m.w * w);
-}
 
 // Position mi of the concatenated K axis -> mode of the CSR / the stacked weights (0 in-half, 1 out-half, 2 self loop)
 __host__ __device__ __forceinline__ int mode_of_pos(int mi) { return mi == 0 ? 0 : (mi == 1 ? 2 : 1); }
@@ -147,24 +108,13 @@ __global__ __launch_bounds__(T4, 4) void layer_fused4_kernel(Args4 p) {
   const int grp = tid >> 5, lig = tid & 31;        // 32 lane groups of 32
   const int glane0 = lane & 32;
   const uint32_t ldx32 = uint32_t(p.ldx), d32 = uint32_t(p.d);
-  struct RowPtrs { int a, b, c; };
   auto tile_rows16 = [&](int it_) {
     const int left = myrows - tile_off(it_), h = it_ == 0 ? h0 : BM;
     const int r = left < h ? left : h;
     return (r + 15) & ~15;
   };
   auto rp_of = [&](int it_, int mode_) {           // lane l: the tile's row pointers l, l + 32, l + 64 (clamped)
-    const int32_t *rp = p.rowptr + int64_t(mode_) * (p.n + 1);
-    const int row0 = row_lo + tile_off(it_);
-    const int h = it_ == 0 ? h0 : BM;
-    auto at = [&](int i) {
-      int node = row0 + (i < h ? i : h);
-      node = node < row_hi ? node : row_hi;
-      return rp[node];
-    };
-    RowPtrs r;
-    r.a = at(lig); r.b = at(lig + 32); r.c = at(lig + 64);
-    return r;
+    return rp_load(p.rowptr + int64_t(mode_) * (p.n + 1), row_lo + tile_off(it_), it_ == 0 ? h0 : BM, row_hi, lig);
   };
   auto rp_get = [&](const RowPtrs &r, int idx) {   // idx group-uniform, 0..BM: the tile's row pointer idx
     const int from = glane0 + (idx & 31);
@@ -311,14 +261,7 @@ __global__ __launch_bounds__(T4, 4) void layer_fused4_kernel(Args4 p) {
   {  // one-time LDS set-up
     const int n16 = (3 * piece) >> 4;        // the image starts as zeros: columns past K are read against zero weights
     for (int i = tid; i < n16; i += T4) reinterpret_cast<uint4 *>(lds4)[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (tid < OP4) {
-      const int c = tid;
-      const bool in = c < p.o;
-      const float inv = in ? __builtin_amdgcn_rsqf(p.bn_var[c] + p.bn_eps) * p.bn_gamma[c] : 0.f;
-      constexpr float third = 1.0f / 3.0f;   // (sum of the three modes) / 3, model.py:103, as a multiplication (<= 1 ulp)
-      epi[c] = inv * third;
-      epi[OP4 + c] = in ? ((p.bias ? p.bias[c] : 0.f) - p.bn_mean[c]) * inv + p.bn_beta[c] : 0.f;
-    }
+    if (tid < OP4) epilogue_table_entry(p, p.bn_eps, epi, OP4, tid);
     for (int i = tid; i < 2 * d; i += T4) lrle[i] = i < d ? p.loop_rel[i] : p.loop_edge[i - d];
     if (RELLDS) {
       const int n4 = ((p.rel_rows - 1) * p.d) >> 2;
@@ -360,7 +303,7 @@ __global__ __launch_bounds__(T4, 4) void layer_fused4_kernel(Args4 p) {
             if (grp + 32 * i < nr) {
               float4 v[NCH];
 #pragma unroll
-              for (int j = 0; j < NCH; ++j) v[j] = f4mul4(f4mul4(pre.xs[i][j], lrv[j]), lev[j]);
+              for (int j = 0; j < NCH; ++j) v[j] = f4mul(f4mul(pre.xs[i][j], lrv[j]), lev[j]);
               write_row(grp + 32 * i, v, lok, lkq);
             }
           }
@@ -448,7 +391,7 @@ __global__ __launch_bounds__(T4, 4) void layer_fused4_kernel(Args4 p) {
 #pragma unroll
               for (int j = 0; j < NCH; ++j) {
                 const float4 rr = RELLDS ? *reinterpret_cast<const float4 *>(relbase + coff[j] + typ * d32) : rv[u][j];
-                sum[j] = f4axpy4(sum[j], f4mul4(f4mul4(xv[u][j], rr), ev[u][j]), wgt);
+                sum[j] = f4axpy(sum[j], f4mul(f4mul(xv[u][j], rr), ev[u][j]), wgt);
               }
             }
           }
@@ -535,8 +478,8 @@ __global__ __launch_bounds__(T4, 4) void layer_fused4_kernel(Args4 p) {
         const float4 sc = *reinterpret_cast<const float4 *>(epi + col), sh = *reinterpret_cast<const float4 *>(epi + OP4 + col);
         auto store_unit = [&](f32x4 a, int node) __attribute__((always_inline)) {
           if (node < row_hi) {
-            const float4 v = make_float4(tanh4_(fmaf(a[0], sc.x, sh.x)), tanh4_(fmaf(a[1], sc.y, sh.y)),
-                                         tanh4_(fmaf(a[2], sc.z, sh.z)), tanh4_(fmaf(a[3], sc.w, sh.w)));
+            const float4 v = make_float4(tanh_fast(fmaf(a[0], sc.x, sh.x)), tanh_fast(fmaf(a[1], sc.y, sh.y)),
+                                         tanh_fast(fmaf(a[2], sc.z, sh.z)), tanh_fast(fmaf(a[3], sc.w, sh.w)));
             *reinterpret_cast<float4 *>(p.out + int64_t(node - p.node0) * p.ldo + col) = v;
           }
         };
@@ -551,9 +494,8 @@ __global__ __launch_bounds__(T4, 4) void layer_fused4_kernel(Args4 p) {
     }
   }
   STAMP4(62);
-  // all_rel = rel @ rels_weight (model.py:107). One item = one relation row x 16 columns per wave: the four 16-lane
-  // groups run the four K quarters of small_matmul_kernel's arithmetic (sequential fmaf chains), the partial sums are
-  // added in quarter order — values bit-identical to the separate launch.
+  // all_rel = rel @ rels_weight (model.py:107) by all sixteen waves: rel_projection of fused_common.h, written out (called as a
+  // function it moves this kernel's register allocation and spills; the arithmetic and the order of the sums are the same)
   if (p.rel_out) {
     const int rows = p.rel_rows - 1, k = p.d, n = p.o;
     const int ncg = (n + 15) / 16, items = rows * ncg;
@@ -705,47 +647,30 @@ int fused4_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_de
 // tune: 0 = automatic; bits 0-3 row tiles per tile (3 / 4 / 5), bits 4-7 slots per gather batch (2 or, one float4 per lane and row, 4; 0 = default), bits 8-9
 // relation table in LDS (1 = never), bits 12-13 phase groups of the stagger (1 = none, 2 = two, 3 = four; 0 = two): for A/B runs,
 // never needed for correctness.
-int fused4_launch(int64_t num_nodes, int32_t dim_in, int32_t dim_out, int32_t num_rel_rows, const int32_t *rowptr_dev,
-                  const mgcn_edge_rec *rec_dev, const float *x_dev, int64_t ldx, const float *rel_dev,
-                  const float *loop_rel_dev, const float *ee_dev, const float *loop_edge_dev, const void *wp_dev,
-                  const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev, const float *bn_gamma_dev,
-                  const float *bn_beta_dev, float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin,
-                  int64_t node_end, int64_t ee_sub_in, int64_t ee_sub_out, const int32_t *hubinfo_dev, int64_t chunk_begin,
-                  const float *partial_dev, const float *rels_weight_dev, float *rel_out_dev, const int32_t *row_bounds_dev,
-                  int32_t num_row_bounds, int32_t tune, void *stream) {
+int fused4_launch(const FusedLaunch &a) {
+  const int32_t dim_in = a.dim_in, dim_out = a.dim_out, tune = a.tune;
   const Shape4 s = shape4(dim_in);
   Args4 p = {};
-  p.rowptr = rowptr_dev; p.rec = reinterpret_cast<const int4 *>(rec_dev);
-  p.x = x_dev; p.rel = rel_dev; p.loop_rel = loop_rel_dev; p.ee = ee_dev; p.loop_edge = loop_edge_dev;
-  p.wp = reinterpret_cast<const u32x4 *>(wp_dev);
-  p.bias = bias_dev; p.bn_mean = bn_mean_dev; p.bn_var = bn_var_dev; p.bn_gamma = bn_gamma_dev; p.bn_beta = bn_beta_dev;
-  p.out = out_dev; p.ldx = ldx; p.ldo = ldo;
-  p.n = int32_t(num_nodes); p.d = dim_in; p.o = dim_out; p.rel_rows = num_rel_rows;
-  p.node0 = int32_t(node_begin); p.node1 = int32_t(node_end);
-  p.ee_sub[0] = int32_t(ee_sub_in); p.ee_sub[1] = int32_t(ee_sub_out);
-  p.hubinfo = reinterpret_cast<const int2 *>(hubinfo_dev); p.partial = partial_dev; p.chunk0 = int32_t(chunk_begin);
-  p.rw = rel_out_dev ? rels_weight_dev : nullptr; p.rel_out = rel_out_dev;
+  fill_layer_args(p, a);
   p.kb_total = s.kb_total; p.nstage = s.nstage; p.skb = s.skb; p.ncc = s.ncc;
-  p.bn_eps = bn_eps;
+  p.bn_eps = a.bn_eps;
 #ifdef MGCN_DIAG
   p.diag = diag_buf4();
 #endif
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const int cus = cu_count();
   // one contiguous run of rows per workgroup, a multiple of 16; one workgroup per CU
-  const int64_t nrows = node_end - node_begin;
+  const int64_t nrows = a.node_end - a.node_begin;
   int64_t rpw = ((nrows + cus - 1) / cus + 15) / 16 * 16;
   if (rpw < 16) rpw = 16;
   int grid = int(nrows > 0 ? (nrows + rpw - 1) / rpw : 1);
   p.rows_per_wg = int32_t(rpw);
-  if (row_bounds_dev && num_row_bounds > 0 && nrows > 0) {   // the caller's runs, one workgroup each
-    p.bounds = row_bounds_dev;
-    grid = num_row_bounds;
+  if (a.row_bounds && a.num_row_bounds > 0 && nrows > 0) {   // the caller's runs, one workgroup each
+    p.bounds = a.row_bounds;
+    grid = a.num_row_bounds;
     const int64_t per = (nrows + grid - 1) / grid;            // (GraphCSR.workgroup_bounds caps its runs by the same rule)
     rpw = per <= 80 ? (per + 15) / 16 * 16 : (per + 79) / 80 * 80;         // (the longest run the convention allows: whole 80-row tiles)
   }
-  const size_t rel_bytes = rel_dev ? size_t(num_rel_rows - 1) * dim_in * 4 : 0;
+  const size_t rel_bytes = a.rel ? size_t(a.num_rel_rows - 1) * dim_in * 4 : 0;
   const int t_nrt = tune & 15, t_ub = (tune >> 4) & 15, t_rel = (tune >> 8) & 3, t_ph = (tune >> 12) & 3;
   p.nphase = t_ph == 1 ? 1 : (t_ph == 3 ? 4 : 2);
   const int nrt_cap = rpw >= 80 ? 5 : rpw >= 64 ? 4 : 3;     // (a tile taller than the run is pointless)
@@ -767,7 +692,7 @@ int fused4_launch(int64_t num_nodes, int32_t dim_in, int32_t dim_out, int32_t nu
     if (!nrt) return mgcn::fail(MGCN_EUNSUPPORTED, "layer_fwd_fused: no tile geometry fits the LDS (D=%d O=%d)", dim_in, dim_out);
   }
   const size_t lds = lds_bytes4(s, dim_in, nrt, rel_lds ? rel_bytes : 0);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipStream_t st = static_cast<hipStream_t>(a.stream);
   if (s.nch == 1) {
     if (t_ub == 2) return launch4_nrt<1, 2>(p, nrt, grid, lds, rel_lds, st);
     return launch4_nrt<1, 4>(p, nrt, grid, lds, rel_lds, st);

@@ -34,46 +34,54 @@ int launch_hub_partials(int64_t num_nodes, int32_t dim, int32_t num_rel_rows, co
                         const float *ee_dev, int32_t ee_in_slot_order, int64_t ee_sub_hub, const int32_t *chunks_dev,
                         int64_t chunk_begin, int64_t chunk_end, float *partial_dev, void *stream);
 
+// The validated parameters of one mgcn_layer_fwd_fused call (include/mgcn_hip.h (4): the same names without _dev), filled once by
+// the dispatcher (layer_fused.hip) and read by the generation it picks.
+struct FusedLaunch {
+  int64_t num_nodes;
+  int32_t dim_in, dim_out, num_rel_rows;
+  const int32_t *rowptr;
+  const mgcn_edge_rec *rec;
+  const float *x;
+  int64_t ldx;
+  const float *rel, *loop_rel, *ee, *loop_edge;
+  const void *wp;
+  const float *bias, *bn_mean, *bn_var, *bn_gamma, *bn_beta;
+  float bn_eps;
+  float *out;
+  int64_t ldo;
+  int64_t node_begin, node_end, ee_sub_in, ee_sub_out;
+  const int32_t *hubinfo;      // null when the launch has no hub chunks
+  int64_t chunk_begin;
+  const float *partial;
+  const float *rels_weight;    // null, with rel_out, when the launch does not project the relations
+  float *rel_out;
+  const int32_t *row_bounds;   // generations 3 and 4
+  int32_t num_row_bounds;
+  int32_t tune;
+  uint32_t *status;            // generation 3
+  void *stream;
+};
+
 // fused layer, lockstep generation (layer_fused2.hip): D <= 256 and O <= 208 (the shapes whose alternating layers keep
 // the packed weights L2-resident only when every workgroup walks them in step)
 bool fused2_takes(int32_t dim_in, int32_t dim_out);
 size_t fused2_packed_bytes(int32_t dim_in, int32_t dim_out);
 int fused2_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_dev, void *stream);
-int fused2_launch(int64_t num_nodes, int32_t dim_in, int32_t dim_out, int32_t num_rel_rows, const int32_t *rowptr_dev,
-                  const mgcn_edge_rec *rec_dev, const float *x_dev, int64_t ldx, const float *rel_dev,
-                  const float *loop_rel_dev, const float *ee_dev, const float *loop_edge_dev, const void *wp_dev,
-                  const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev, const float *bn_gamma_dev,
-                  const float *bn_beta_dev, float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin,
-                  int64_t node_end, int64_t ee_sub_in, int64_t ee_sub_out, const int32_t *hubinfo_dev, int64_t chunk_begin,
-                  const float *partial_dev, const float *rels_weight_dev, float *rel_out_dev, void *stream);
+int fused2_launch(const FusedLaunch &a);
 
 // fused layer, elastic generation (layer_fused3.hip): one slot walk for 256 input columns, exact-width LDS buffers, a ring of staging buffers
 // coupled by LDS counters, one contiguous run of rows per workgroup
 bool fused3_takes(int32_t dim_in, int32_t dim_out);
 size_t fused3_packed_bytes(int32_t dim_in, int32_t dim_out);
 int fused3_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_dev, void *stream);
-int fused3_launch(int64_t num_nodes, int32_t dim_in, int32_t dim_out, int32_t num_rel_rows, const int32_t *rowptr_dev,
-                  const mgcn_edge_rec *rec_dev, const float *x_dev, int64_t ldx, const float *rel_dev,
-                  const float *loop_rel_dev, const float *ee_dev, const float *loop_edge_dev, const void *wp_dev,
-                  const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev, const float *bn_gamma_dev,
-                  const float *bn_beta_dev, float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin,
-                  int64_t node_end, int64_t ee_sub_in, int64_t ee_sub_out, const int32_t *hubinfo_dev, int64_t chunk_begin,
-                  const float *partial_dev, const float *rels_weight_dev, float *rel_out_dev, const int32_t *row_bounds_dev,
-                  int32_t num_row_bounds, int32_t tune, uint32_t *status_dev, void *stream);
+int fused3_launch(const FusedLaunch &a);
 
 // fused layer, phase-alternating generation (layer_fused4.hip): D <= 256, O <= 208; all sixteen waves gather a stage of up to 320
 // columns of the concatenated K axis into one LDS image, then all sixteen multiply it
 bool fused4_takes(int32_t dim_in, int32_t dim_out);
 size_t fused4_packed_bytes(int32_t dim_in, int32_t dim_out);
 int fused4_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_dev, void *stream);
-int fused4_launch(int64_t num_nodes, int32_t dim_in, int32_t dim_out, int32_t num_rel_rows, const int32_t *rowptr_dev,
-                  const mgcn_edge_rec *rec_dev, const float *x_dev, int64_t ldx, const float *rel_dev,
-                  const float *loop_rel_dev, const float *ee_dev, const float *loop_edge_dev, const void *wp_dev,
-                  const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev, const float *bn_gamma_dev,
-                  const float *bn_beta_dev, float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin,
-                  int64_t node_end, int64_t ee_sub_in, int64_t ee_sub_out, const int32_t *hubinfo_dev, int64_t chunk_begin,
-                  const float *partial_dev, const float *rels_weight_dev, float *rel_out_dev, const int32_t *row_bounds_dev,
-                  int32_t num_row_bounds, int32_t tune, void *stream);
+int fused4_launch(const FusedLaunch &a);
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
