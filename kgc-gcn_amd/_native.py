@@ -119,7 +119,7 @@ def _dev(t, dtype, what, allow_none=False):
         raise NativeError('%s must live on a GPU (got %s): the M-GCN hot path has no CPU fallback' % (what, t.device))
     if t.dtype != dtype:
         raise NativeError('%s: dtype %s, expected %s' % (what, t.dtype, dtype))
-    if t.dim() > 0 and t.numel() > 0 and t.stride(-1) != 1:
+    if t.dim() > 0 and t.numel() > 0 and t.size(-1) > 1 and t.stride(-1) != 1:       # (the stride of a last dimension of size 1 is never used)
         raise NativeError('%s: last dimension must be contiguous' % what)
     return t.data_ptr()
 

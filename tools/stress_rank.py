@@ -1,10 +1,14 @@
 """Randomised check (not part of the test suite) of the scoring kernels: score_target / score_rank (bit mask and dense
-label filters, entity shards) against a torch recount over score_fwd's scores, which share the tile arithmetic."""
+label filters, entity shards) against a torch recount over score_fwd's scores, which share the tile arithmetic -- and,
+because a fault in that shared arithmetic moves all three together, score_fwd's VALUES against float64 with the scoring
+bar of tests/dense_ref.py (4 u mag + 2e-7 on the logit for the bf16-split shapes, c u mag for the exact-f32 ones, seen
+through the sigmoid's slope)."""
 import importlib, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 pkg = importlib.import_module('kgc-gcn_amd'); nat = pkg._native
+from tests import dense_ref as R
 dev = torch.device('cuda:0')
 
 
@@ -25,6 +29,11 @@ def run(seed=0, trials=60):
         bits = torch.zeros(B, words * 32, dtype=torch.int64, device=dev); bits[:, :N] = label.long()
         mask = (bits.view(B, words, 32) << torch.arange(32, device=dev)).sum(2).to(torch.int32)   # wraps into the sign bit
         score = nat.score_fwd(x, ent, bias)
+        p64, _, mag = R.ref_scores(x, ent, bias)
+        # mgcn_hip.h (5): contiguous operands with dim % 4 == 0 and dim <= 352 take the bf16 split, the rest the exact-f32 MFMA
+        logit_bar = R.split_logit_bar(mag) if O % 4 == 0 and O <= 352 else R.dot_bar(mag, O)
+        worst = R.max_ratio(score, p64, R.sigmoid_bar(p64, logit_bar))
+        assert worst <= 1.0, ('score_fwd against float64: %.3f x the bar' % worst, trial, B, N, O)
         target = nat.score_target(x, ent, bias, obj)
         rows = torch.arange(B, device=dev)
         assert torch.equal(target, score[rows, obj]), 'target'
@@ -43,7 +52,7 @@ def run(seed=0, trials=60):
                 nat.score_rank(x, ent[lo:hi].contiguous(), bias[lo:hi].contiguous(), obj, target, label=label[:, lo:hi].contiguous(),
                                ent_row0=lo, counts=acc)
         assert torch.equal(acc, want), ('sharded', trial)
-        print('trial %2d B=%3d N=%4d O=%3d scale %.2f  ties %d  ok' % (trial, B, N, O, scale, int(want[:, 2].sum())))
+        print('trial %2d B=%3d N=%4d O=%3d scale %.2f  ties %d  f64 %.3f of the bar  ok' % (trial, B, N, O, scale, int(want[:, 2].sum()), worst))
     print('all trials ok')
     return True
 
