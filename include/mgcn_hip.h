@@ -462,6 +462,49 @@ int mgcn_score_topk(int32_t batch, int64_t n_local, int64_t ent_row0, int32_t di
 int mgcn_topk_merge(int32_t batch, int32_t lists, const float *in_score_dev, const int64_t *in_id_dev, int64_t ld_in,
                     int32_t k, float *out_score_dev, int64_t *out_id_dev, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (8) ConvE query trunk, eval mode (model.py:161-175): from the encoder's two tables to the query embeddings x [B, O]
+ * that (5) and (7) score. For query b with s = ent[src_index[b]] and r = rel[rel_index[b]] (both [O], O = k_w * k_h):
+ *   image [2 k_w, k_h], flat element 2 j = s[j], 2 j + 1 = r[j] (the reference interleaves the two rows);
+ *   bn0 (one channel, running statistics); valid kernel_size x kernel_size convolution to num_filter channels of H x W,
+ *   H = 2 k_w - kernel_size + 1, W = k_h - kernel_size + 1 (conv bias optional); bn1 per channel; relu; flatten to
+ *   f H W + y W + x; fc [O, num_filter H W] + bias; bn2 per output; relu.
+ * mgcn_conve_pack folds bn0 / conv bias / bn1 into scaled taps and one constant per filter, fc bias / bn2 into one
+ * scale and shift per output (in double, rounded once) and lays fc.weight out in MFMA fragment order:
+ * mgcn_conve_packed_bytes bytes (0 for a geometry that is refused), 16-byte aligned. Re-pack whenever one of its inputs
+ * changes. conv_w [num_filter, kernel_size^2] and the BN vectors are contiguous; conv_b, fc_b and the BN gamma / beta
+ * pointers may be NULL (no bias; gamma 1, beta 0); fc_w rows are ldw floats apart.
+ * mgcn_conve_trunk_fwd gathers the rows itself: src_index / rel_index [B] int64, NULL = rows 0 .. B-1 (the table must
+ * then have at least B rows); an index outside [0, rows) is clamped to the table. out [B, ldo >= O] f32.
+ * Arithmetic: the convolution is an f32 fma chain in tap order, the fc product runs on v_mfma_f32_16x16x4_f32 (exact
+ * f32). The [B, num_filter H W] activation is never stored: each activation is formed in the register that feeds the
+ * MFMA. Summation order of one output: the K axis is cut into ceil(H W / 4) segments (four positions of every filter),
+ * each one accumulation chain in filter order from 0; the segment sums are added in ascending order from 0; then
+ * relu(fma(total, scale, shift)). The order is a function of the geometry alone: a query's row has the same bits
+ * whatever the batch, its position in it, or the launch form. Up to 8192 queries the segments are spread over workgroups
+ * through workspace_dev (mgcn_conve_trunk_workspace(batch, ...) bytes, 16-byte aligned; [segments, B, round16(O)] f32)
+ * and a second launch adds them; larger batches walk them inside one wave and need no workspace (0 bytes, NULL allowed).
+ * No atomics, no spinning. A non-finite value in a query's rows makes that output row non-finite and leaves all others
+ * unchanged.
+ * Takes k_w * k_h == O <= 512, 1 <= kernel_size <= min(2 k_w, k_h), num_filter >= 1, a pack below 2^31 floats;
+ * MGCN_EINVAL for anything that is not a ConvE geometry, MGCN_EUNSUPPORTED (nothing done) for O > 512 or a larger pack.
+ */
+size_t mgcn_conve_packed_bytes(int32_t k_w, int32_t k_h, int32_t kernel_size, int32_t num_filter, int32_t dim_out);
+int mgcn_conve_pack(int32_t k_w, int32_t k_h, int32_t kernel_size, int32_t num_filter, int32_t dim_out,
+                    const float *conv_w_dev, const float *conv_b_dev, const float *fc_w_dev, int64_t ldw,
+                    const float *fc_b_dev, const float *bn0_mean_dev, const float *bn0_var_dev,
+                    const float *bn0_gamma_dev, const float *bn0_beta_dev, float bn0_eps, const float *bn1_mean_dev,
+                    const float *bn1_var_dev, const float *bn1_gamma_dev, const float *bn1_beta_dev, float bn1_eps,
+                    const float *bn2_mean_dev, const float *bn2_var_dev, const float *bn2_gamma_dev,
+                    const float *bn2_beta_dev, float bn2_eps, void *packed_dev, size_t packed_bytes, void *stream);
+size_t mgcn_conve_trunk_workspace(int32_t batch, int32_t k_w, int32_t k_h, int32_t kernel_size, int32_t num_filter,
+                                  int32_t dim_out);
+int mgcn_conve_trunk_fwd(int32_t batch, int32_t k_w, int32_t k_h, int32_t kernel_size, int32_t num_filter,
+                         int32_t dim_out, const float *ent_dev, int64_t lde, int64_t ent_rows,
+                         const int64_t *src_index_dev, const float *rel_dev, int64_t ldr, int64_t rel_rows,
+                         const int64_t *rel_index_dev, const void *packed_dev, float *out_dev, int64_t ldo,
+                         void *workspace_dev, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

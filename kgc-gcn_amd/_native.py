@@ -66,6 +66,12 @@ _SIGNATURES = {
     'mgcn_score_topk': (ctypes.c_int, [_i32, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _i64,
                                        _ptr, _i64, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_topk_merge': (ctypes.c_int, [_i32, _i32, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _ptr]),
+    'mgcn_conve_packed_bytes': (ctypes.c_size_t, [_i32] * 5),
+    'mgcn_conve_pack': (ctypes.c_int, [_i32] * 5 + [_ptr, _ptr, _ptr, _i64, _ptr] + ([_ptr] * 4 + [_f32]) * 3 +
+                        [_ptr, ctypes.c_size_t, _ptr]),
+    'mgcn_conve_trunk_workspace': (ctypes.c_size_t, [_i32] * 6),
+    'mgcn_conve_trunk_fwd': (ctypes.c_int, [_i32] * 6 + [_ptr, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _ptr,
+                                            ctypes.c_size_t, _ptr]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
     'mgcn_ingest_count': (_i64, [_ptr, _i32]),
@@ -768,6 +774,68 @@ def topk_merge(scores, ids, k):
                                  scores.size(1), k, _dev(out_s, torch.float32, 'out scores'),
                                  _dev(out_i, torch.int64, 'out ids'), _stream(scores)), 'mgcn_topk_merge')
     return out_s, out_i
+
+
+# ------------------------------------------------------------------------------------------------
+# (8) ConvE query trunk. geom = (k_w, k_h, kernel_size, num_filter, O)
+def conve_supported(k_w, k_h, kernel_size, num_filter, dim_out):
+    """Geometries mgcn_conve_trunk_fwd takes (k_w k_h == O <= 512, 1 <= kernel <= min(2 k_w, k_h), a pack below 2^31 floats)."""
+    geom = tuple(int(v) for v in (k_w, k_h, kernel_size, num_filter, dim_out))
+    return min(geom) >= 1 and lib().mgcn_conve_packed_bytes(*geom) > 0
+
+
+def conve_pack(geom, conv_w, conv_b, fc_w, fc_b, bn0, bn1, bn2, out=None):
+    """Fold and pack the trunk's weights (see mgcn_conve_pack): bn* = (running_mean, running_var, weight, bias, eps) with
+    weight / bias None for a BN without affine pair. `out`: a pack to refresh in place (same geometry and device)."""
+    geom = tuple(int(v) for v in geom)
+    nbytes = lib().mgcn_conve_packed_bytes(*geom)
+    if nbytes == 0:
+        raise NativeError('conve_pack: geometry %s is not supported' % (geom,))
+    if not conv_w.is_contiguous() or fc_w.dim() != 2:
+        raise NativeError('conve_pack: conv weight must be contiguous, fc weight 2-d')
+    if out is None or out.numel() * 4 < nbytes or out.device != fc_w.device:
+        out = torch.empty(nbytes // 4, dtype=torch.float32, device=fc_w.device)
+    args = []
+    for mean, var, gamma, beta, eps in (bn0, bn1, bn2):
+        _same_device(fc_w, mean, var, gamma, beta)
+        args += [_dev(mean, torch.float32, 'bn mean'), _dev(var, torch.float32, 'bn var'), _dev(gamma, torch.float32, 'bn weight', True),
+                 _dev(beta, torch.float32, 'bn bias', True), float(eps)]
+    _same_device(fc_w, conv_w, conv_b, fc_b, out)
+    _check(lib().mgcn_conve_pack(*geom, _dev(conv_w, torch.float32, 'conv weight'), _dev(conv_b, torch.float32, 'conv bias', True),
+                                 _dev(fc_w, torch.float32, 'fc weight'), _ld(fc_w), _dev(fc_b, torch.float32, 'fc bias', True),
+                                 *args, _dev(out, torch.float32, 'pack'), out.numel() * 4, _stream(fc_w)), 'mgcn_conve_pack')
+    return out
+
+
+def conve_trunk(geom, packed, ent, src, rel, rel_idx, out=None):
+    """x [B, O] = trunk(ent[src], rel[rel_idx]) on the HIP kernel; src / rel_idx int64 [B] or None (rows 0 .. B-1 of both
+    tables, which then have the same number of rows). `out`: an f32 [B, >= O] view to fill (row stride = its ldo)."""
+    geom = tuple(int(v) for v in geom)
+    O = geom[4]
+    if ent.dim() != 2 or rel.dim() != 2 or ent.size(1) != O or rel.size(1) != O:
+        raise NativeError('conve_trunk: tables must be [rows, %d], got %s and %s' % (O, tuple(ent.shape), tuple(rel.shape)))
+    if (src is None) != (rel_idx is None):
+        raise NativeError('conve_trunk: give both index vectors or neither')
+    B = int(src.numel()) if src is not None else int(ent.size(0))
+    if src is not None and (rel_idx.numel() != B or not src.is_contiguous() or not rel_idx.is_contiguous()):
+        raise NativeError('conve_trunk: index vectors must be contiguous and of equal length')
+    if src is None and rel.size(0) != B:
+        raise NativeError('conve_trunk: without index vectors both tables need the same number of rows')
+    _same_device(ent, rel, src, rel_idx, packed, out)
+    if out is None:
+        out = torch.empty((B, O), dtype=torch.float32, device=ent.device)
+    elif out.dim() != 2 or out.size(0) != B or out.size(1) != O:
+        raise NativeError('conve_trunk: out must be [%d, %d]' % (B, O))
+    if B == 0:
+        return out
+    nbytes = lib().mgcn_conve_trunk_workspace(B, *geom)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=ent.device) if nbytes else None    # the caching allocator's memory
+    _check(lib().mgcn_conve_trunk_fwd(B, *geom, _dev(ent, torch.float32, 'ent'), _ld(ent), ent.size(0),
+                                      _dev(src, torch.int64, 'src', True), _dev(rel, torch.float32, 'rel'), _ld(rel), rel.size(0),
+                                      _dev(rel_idx, torch.int64, 'rel index', True), _dev(packed, torch.float32, 'pack'),
+                                      _dev(out, torch.float32, 'out'), _ld(out) if B > 1 else max(out.stride(0), O),
+                                      _dev(ws, torch.uint8, 'workspace', True), nbytes, _stream(ent)), 'mgcn_conve_trunk_fwd')
+    return out
 
 
 def filter_mask(qkey, keys, ptr, tails, n_local, ent_row0=0, out=None):

@@ -322,8 +322,7 @@ def evaluate_sharded(model, graph, queries, filt, batch_size=None, group=None, t
     q = torch.zeros((per, 3), dtype=torch.int64, device=dev)   # padding rows are harmless queries, dropped below
     q[:real] = queries[lo:hi].to(dev)
     sub, rel, obj = q[:, 0], q[:, 1], q[:, 2].contiguous()
-    x = torch.cat([model.conv2.trunk(all_ent.index_select(0, sub[i:i + trunk_chunk]),
-                                     all_rel.index_select(0, rel[i:i + trunk_chunk]))
+    x = torch.cat([model.conv2.trunk_indexed(all_ent, sub[i:i + trunk_chunk], all_rel, rel[i:i + trunk_chunk])
                    for i in range(0, per, trunk_chunk)], dim=0) if per > 0 else all_ent.new_zeros((0, all_ent.size(1)))
     keys = filt.query_keys(sub, rel)
     lap('trunk_s')
@@ -400,8 +399,7 @@ def predict_topk_sharded(model, graph, queries, k, filt=None, group=None, trunk_
     q = torch.zeros((per, 2), dtype=torch.int64, device=dev)   # padding rows are harmless queries, dropped below
     q[:hi - lo] = queries[lo:hi, :2].to(dev)
     sub, rel = q[:, 0], q[:, 1]
-    x = torch.cat([model.conv2.trunk(all_ent.index_select(0, sub[i:i + trunk_chunk]),
-                                     all_rel.index_select(0, rel[i:i + trunk_chunk]))
+    x = torch.cat([model.conv2.trunk_indexed(all_ent, sub[i:i + trunk_chunk], all_rel, rel[i:i + trunk_chunk])
                    for i in range(0, per, trunk_chunk)], dim=0) if per > 0 else all_ent.new_zeros((0, all_ent.size(1)))
     keys = filt.query_keys(sub, rel) if filt is not None else sub
     if per == 0:

@@ -10,7 +10,8 @@ What runs where
     launch (csrc/dense.hip). In training mode (batch statistics, dropout) the products, the BN reductions, tanh and
     their backward run on csrc/train_layer.hip kernels behind torch.autograd.Function (only the dropout masks are torch's);
   * full-graph scoring (model.py:177-179) and the filtered rank counts (main.py:122-126): HIP;
-  * the ConvE conv trunk (model.py:161-175): stock torch modules (MIOpen / rocBLAS), out of scope.
+  * the ConvE conv trunk (model.py:161-175): stock torch modules (MIOpen / rocBLAS) by default and always in training; with
+    params.conve_trunk = 'hip' (or MGCN_TRUNK=hip) the eval-mode trunk is ONE HIP launch from the two tables to x (csrc/conve_trunk.hip).
 There is no CPU path: tensors that are not on a GPU make the native layer raise.
 """
 import os
@@ -274,7 +275,7 @@ class MGCNConv(nn.Module):
 
 
 class ConvE(nn.Module):
-    """Decoder (model.py:130-181): torch conv trunk, HIP scoring against every entity."""
+    """Decoder (model.py:130-181): conv trunk (torch, or the opt-in HIP trunk in eval mode), HIP scoring against every entity."""
 
     def __init__(self, params, num_entities):
         super(ConvE, self).__init__()
@@ -292,13 +293,66 @@ class ConvE(nn.Module):
         self.fc = nn.Linear(self.flat_sz, params.gcn_out_dim)
         self.register_parameter('bias', nn.Parameter(torch.zeros(num_entities)))
 
+    # -- HIP trunk (csrc/conve_trunk.hip): opt-in, eval mode without autograd only ------------------
+    def _geometry(self):
+        p = self.params
+        return (int(p.k_w), int(p.k_h), int(p.kernel_size), int(p.num_filter), int(p.gcn_out_dim))
+
+    def _hip_trunk(self, *tensors):
+        """Whether this call takes the HIP trunk: the switch (params.conve_trunk == 'hip', overridden by the environment
+        variable MGCN_TRUNK), eval mode, grad mode off, inputs on the GPU, a geometry the kernel takes."""
+        want = os.environ.get('MGCN_TRUNK') or getattr(self.params, 'conve_trunk', 'torch')
+        if want != 'hip' or self.training or torch.is_grad_enabled():
+            return False
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in tensors) or not self.fc.weight.is_cuda:
+            return False
+        bns = (self.bn0, self.bn1, self.bn2)
+        if any(bn.running_mean is None or bn.running_var is None for bn in bns):
+            return False
+        return _native.conve_supported(*self._geometry())
+
+    def _pack_tensors(self):
+        ts = [self.conv_e.weight, self.conv_e.bias, self.fc.weight, self.fc.bias]
+        for bn in (self.bn0, self.bn1, self.bn2):
+            ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        return ts
+
+    def packed_weights(self):
+        """The trunk's folded taps / constants and fc.weight in MFMA fragment order (mgcn_conve_pack), in a PERSISTENT buffer
+        that is refreshed in place only when the (_version, data_ptr) stamp of a weight, a bias or a BN tensor changed
+        (load_state_dict, an optimizer step and a training-mode forward all bump one of them), as MGCNConv.derived_weights."""
+        stamp = tuple((t._version, t.data_ptr()) if t is not None else None for t in self._pack_tensors())
+        if getattr(self, '_pack_stamp', None) != stamp:
+            bn = lambda m: (m.running_mean, m.running_var, m.weight, m.bias, m.eps)
+            self._pack = _native.conve_pack(self._geometry(), self.conv_e.weight.detach(),
+                                            None if self.conv_e.bias is None else self.conv_e.bias.detach(),
+                                            self.fc.weight.detach(), self.fc.bias.detach(), bn(self.bn0), bn(self.bn1), bn(self.bn2),
+                                            out=getattr(self, '_pack', None))
+            self._pack_stamp = stamp
+            self._pack_count = getattr(self, '_pack_count', 0) + 1
+        return self._pack
+
     def trunk(self, src_emb, rel_emb):
+        if self._hip_trunk(src_emb, rel_emb) and src_emb.dim() == 2 and src_emb.shape == rel_emb.shape \
+                and src_emb.size(1) == self.params.gcn_out_dim:
+            src_emb = src_emb if src_emb.stride(1) == 1 else src_emb.contiguous()
+            rel_emb = rel_emb if rel_emb.stride(1) == 1 else rel_emb.contiguous()
+            return _native.conve_trunk(self._geometry(), self.packed_weights(), src_emb, None, rel_emb, None)
         o = self.params.gcn_out_dim
         stack = torch.cat([src_emb.view(-1, 1, o), rel_emb.view(-1, 1, o)], dim=1)
         stack = stack.transpose(2, 1).reshape(-1, 1, 2 * self.params.k_w, self.params.k_h)
         x = self.feature_drop(F.relu(self.bn1(self.conv_e(self.bn0(stack)))))
         x = self.hidden_drop(self.fc(x.view(-1, self.flat_sz)))
         return F.relu(self.bn2(x)).contiguous()
+
+    def trunk_indexed(self, all_ent, src, all_rel, rel):
+        """trunk(all_ent[src], all_rel[rel]); on the HIP trunk the rows are gathered inside the kernel."""
+        if self._hip_trunk(all_ent, all_rel) and all_ent.dim() == 2 and all_rel.dim() == 2 and src.dtype == torch.int64 \
+                and rel.dtype == torch.int64 and src.dim() == 1 and src.shape == rel.shape:
+            all_ent = all_ent if all_ent.stride(1) == 1 else all_ent.contiguous()
+            all_rel = all_rel if all_rel.stride(1) == 1 else all_rel.contiguous()
+            return _native.conve_trunk(self._geometry(), self.packed_weights(), all_ent, src.contiguous(), all_rel, rel.contiguous())
+        return self.trunk(torch.index_select(all_ent, 0, src), torch.index_select(all_rel, 0, rel))
 
     def forward(self, src_emb, rel_emb, all_ent):
         x = self.trunk(src_emb, rel_emb)
@@ -591,7 +645,7 @@ class MGCN(nn.Module):
         The filter is the dense `label` block of the reference loader, or (label=None) a dist.FilterIndex from
         which the bits are built on the device."""
         all_ent, all_rel = self.encode(data)
-        x = self.conv2.trunk(torch.index_select(all_ent, 0, src), torch.index_select(all_rel, 0, rel))
+        x = self.conv2.trunk_indexed(all_ent, src, all_rel, rel)
         ent = all_ent.contiguous()
         target = _native.score_target(x, ent, self.conv2.bias, obj)
         if label is not None:
@@ -615,7 +669,7 @@ class MGCN(nn.Module):
         self.eval()
         try:
             all_ent, all_rel = self.encode(data)
-            x = self.conv2.trunk(torch.index_select(all_ent, 0, src), torch.index_select(all_rel, 0, rel))
+            x = self.conv2.trunk_indexed(all_ent, src, all_rel, rel)
             ent = all_ent.contiguous()
             mask = None
             if filter_index is not None:

@@ -1,6 +1,10 @@
-"""ConvE trunk (model.py:161-175, torch / MIOpen / hipBLASLt — outside the HIP path) on 6268 queries: chunk size and
-MIOpen find mode, to see what the evaluation's largest share responds to."""
-import importlib, os, sys, time, types
+"""ConvE trunk (model.py:161-175) at the production geometry.
+Default: the torch trunk (MIOpen / hipBLASLt) on 6268 queries over chunk size and MIOpen find mode, to see what the
+evaluation's largest share responds to.
+--compare: the HIP trunk (csrc/conve_trunk.hip) against the torch trunk on the same inputs at B = 128, 2048, 6268, 40932, in
+one process, alternating; HIP events, median of --runs runs after warm-up. The torch baseline is the better of
+cudnn.benchmark off / on and of the chunk sizes below; one JSON line at the end (--out: also written to that file)."""
+import importlib, json, os, sys, time, types
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -21,7 +25,74 @@ def t(fn, n=5):
     for _ in range(n): fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / n * 1e3
+CHUNKS = (512, 1024, 2048, 4096, 6268)
+
+
+def event_ms(fn, runs):
+    """Median device time of fn() over `runs` runs, HIP events, after three warm-up calls."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(runs):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    times.sort()
+    return times[len(times) // 2]
+
+
+def compare(runs, out_path):
+    MFLOP_PER_QUERY, PEAK_F32_MFMA_TF = 19.5, 155.0          # issue arithmetic; measured peak (tools/mfma_peak.hip)
+    hip = pkg.model.ConvE(types.SimpleNamespace(**dict(vars(params), conve_trunk='hip')), 1000).to(dev).eval()
+    hip.load_state_dict(conv.state_dict())
+    rows = []
+    for B in (128, 2048, 6268, 40932):
+        s, r = torch.randn(B, 200, device=dev), torch.randn(B, 200, device=dev)
+        with torch.no_grad():
+            run_hip = lambda: hip.trunk(s, r)
+            y_hip = run_hip()
+            assert hip._pack_count == 1
+            best = None
+            for bench_mode in (False, True):
+                torch.backends.cudnn.benchmark = bench_mode
+                for chunk in sorted({min(c, B) for c in CHUNKS} | {B}):
+                    run_torch = lambda: torch.cat([conv.trunk(s[i:i + chunk], r[i:i + chunk]) for i in range(0, B, chunk)])
+                    y_torch = run_torch()
+                    # alternate: torch, hip, torch (the first torch figure also warms MIOpen's find for this chunk)
+                    event_ms(run_torch, 3)
+                    ms_hip = event_ms(run_hip, runs)
+                    ms_torch = event_ms(run_torch, runs)
+                    if best is None or ms_torch < best['torch_ms']:
+                        best = dict(torch_ms=ms_torch, torch_chunk=chunk, torch_cudnn_benchmark=bench_mode)
+                    best.setdefault('hip_ms_all', []).append(ms_hip)
+            torch.backends.cudnn.benchmark = False
+        hip_all = sorted(best.pop('hip_ms_all'))
+        ms_hip = hip_all[len(hip_all) // 2]
+        tf = B * MFLOP_PER_QUERY * 1e6 / (ms_hip * 1e-3) / 1e12
+        row = dict(B=B, hip_ms=round(ms_hip, 4), hip_ms_min=round(hip_all[0], 4), hip_ms_max=round(hip_all[-1], 4),
+                   hip_tflops=round(tf, 2), hip_fraction_of_f32_mfma_peak=round(tf / PEAK_F32_MFMA_TF, 3),
+                   speedup=round(best['torch_ms'] / ms_hip, 2), max_abs_diff=float((y_hip - y_torch).abs().max()), **best)
+        row['torch_ms'] = round(row['torch_ms'], 4)
+        rows.append(row)
+        print('B %6d: hip %.3f ms (%.1f TF, %.0f %% of the f32 MFMA peak)  torch %.3f ms (chunk %d, cudnn.benchmark=%s)  x%.2f  |diff| %.2g'
+              % (B, ms_hip, tf, 100 * tf / PEAK_F32_MFMA_TF, row['torch_ms'], row['torch_chunk'], row['torch_cudnn_benchmark'],
+                 row['speedup'], row['max_abs_diff']), flush=True)
+    line = json.dumps(dict(bench='trunk_compare', geometry=[10, 20, 7, 200, 200], runs=runs, rows=rows))
+    print(line)
+    if out_path:
+        with open(out_path, 'w') as f:
+            f.write(line + '\n')
+
+
+if '--compare' in sys.argv:
+    arg = lambda name, default: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
+    compare(int(arg('--runs', 20)), arg('--out', None))
+    sys.exit(0)
 for bench_mode in (False, True):
     torch.backends.cudnn.benchmark = bench_mode
-    for chunk in (512, 1024, 2048, 4096, 6268):
+    for chunk in CHUNKS:
         print('cudnn.benchmark=%s chunk %5d: %.3f ms' % (bench_mode, chunk, t(lambda: run(chunk))))
