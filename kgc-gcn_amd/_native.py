@@ -265,8 +265,23 @@ def aggregate_fwd(csr, x, rel, ee, ee_in_slot_order, loop_edge, out, loop_rel=No
     return out
 
 
-def aggregate_bwd(csr, x, rel, ee, g, want_gx=True, want_gee=True, want_grel=True):
-    """(3) Gradients of aggregate_fwd's first 2D columns w.r.t. x, the per-edge table (slot order) and rel."""
+def _bwd_out(out, i, want, shape, device, what):
+    """Output i of a backward: the caller's tensor (`out` = (gx, gee, grel), entries may be None) or a fresh one."""
+    given = None if out is None else out[i]
+    if not want:
+        if given is not None:
+            raise NativeError('%s: out[%d] given for a gradient that is not computed' % (what, i))
+        return None
+    if given is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(given.shape) != tuple(shape) or given.dtype != torch.float32 or given.device != device or not given.is_contiguous():
+        raise NativeError('%s: out[%d] must be a contiguous float32 %s on %s' % (what, i, tuple(shape), device))
+    return given
+
+
+def aggregate_bwd(csr, x, rel, ee, g, want_gx=True, want_gee=True, want_grel=True, out=None):
+    """(3) Gradients of aggregate_fwd's first 2D columns w.r.t. x, the per-edge table (slot order) and rel. `out` =
+    (gx, gee, grel): tensors to write instead of fresh ones (contiguous, entries may be None)."""
     N, E, D = csr.num_nodes, csr.num_edges_half, x.size(1)
     _same_device(csr.rowptr, x, rel, ee, g)
     if not csr.has_backward:
@@ -281,9 +296,11 @@ def aggregate_bwd(csr, x, rel, ee, g, want_gx=True, want_gee=True, want_grel=Tru
         raise NativeError('aggregate_bwd: x / rel do not match the graph')
     if ee is not None and (tuple(ee.shape) != (2 * E, D) or not ee.is_contiguous()):
         raise NativeError('aggregate_bwd: per-edge table must be contiguous (%d, %d) in slot order' % (2 * E, D))
-    gx = torch.empty((N, D), dtype=torch.float32, device=x.device) if want_gx else None
-    gee = torch.empty((2 * E, D), dtype=torch.float32, device=x.device) if (want_gee and ee is not None) else None
-    grel = torch.empty((csr.num_rel_rows, D), dtype=torch.float32, device=x.device) if want_grel else None
+    if out is not None and len(out) != 3:
+        raise NativeError('aggregate_bwd: out must be (gx, gee, grel)')
+    gx = _bwd_out(out, 0, want_gx, (N, D), x.device, 'aggregate_bwd')
+    gee = _bwd_out(out, 1, want_gee and ee is not None, (2 * E, D), x.device, 'aggregate_bwd')
+    grel = _bwd_out(out, 2, want_grel, (csr.num_rel_rows, D), x.device, 'aggregate_bwd')
     need_ws = want_grel or (want_gx and csr.num_chunks > 0)
     ws_bytes = lib().mgcn_aggregate_bwd_workspace(E, D, csr.num_rel_rows, csr.num_chunks) if need_ws else 0
     ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=x.device) if need_ws else None
@@ -301,11 +318,12 @@ def aggregate_bwd(csr, x, rel, ee, g, want_gx=True, want_gee=True, want_grel=Tru
     return gx, gee, grel
 
 
-def aggregate_bwd_shard(csr, x, rel, ee, g, node_range, want_gx=True):
+def aggregate_bwd_shard(csr, x, rel, ee, g, node_range, want_gx=True, out=None):
     """(3s) aggregate_bwd for the destinations [n0, n1) of one rank from its table shard `ee` (slot order, the rows of
     GraphCSR.edge_table_shard); `g` [n1 - n0, >= 2D] holds the gradient of those rows only. Returns (gx [N, D] partial or None,
     gee [shard rows, D] complete, grel [num_rel_rows, D] partial): summed over the ranks of a partition, gx / grel are
-    aggregate_bwd's (bit-identical with one range covering the graph)."""
+    aggregate_bwd's (bit-identical with one range covering the graph). `out` = (gx, gee, grel): tensors to write instead
+    of fresh ones (contiguous, entries may be None)."""
     N, E, D = csr.num_nodes, csr.num_edges_half, x.size(1)
     n0, n1 = int(node_range[0]), int(node_range[1])
     _same_device(csr.rowptr, x, rel, ee, g)
@@ -325,9 +343,11 @@ def aggregate_bwd_shard(csr, x, rel, ee, g, node_range, want_gx=True):
         raise NativeError('aggregate_bwd_shard: g %s must be [%d, >= %d]' % (tuple(g.shape), n1 - n0, 2 * D))
     idx = csr.shard_backward_index(n0, n1)
     sub = csr.shard_ee_sub(n0, n1)
-    gx = torch.empty((N, D), dtype=torch.float32, device=x.device) if want_gx else None
-    gee = torch.empty((sum(rows), D), dtype=torch.float32, device=x.device)
-    grel = torch.empty((csr.num_rel_rows, D), dtype=torch.float32, device=x.device)
+    if out is not None and len(out) != 3:
+        raise NativeError('aggregate_bwd_shard: out must be (gx, gee, grel)')
+    gx = _bwd_out(out, 0, want_gx, (N, D), x.device, 'aggregate_bwd_shard')
+    gee = _bwd_out(out, 1, True, (sum(rows), D), x.device, 'aggregate_bwd_shard')
+    grel = _bwd_out(out, 2, True, (csr.num_rel_rows, D), x.device, 'aggregate_bwd_shard')
     hubs = csr.num_chunks > 0
     ws_bytes = lib().mgcn_aggregate_bwd_shard_workspace(sum(rows), D, csr.num_rel_rows, csr.num_chunks)
     ws = torch.empty(max(ws_bytes // 4, 4), dtype=torch.float32, device=x.device)

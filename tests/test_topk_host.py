@@ -188,8 +188,8 @@ def _worker(rank, world, port, q):
         for f in (filt, None):
             s, i = pkg.dist.sharded_topk(x[rank], filt.query_keys(sub[rank], rel[rank]), ent[b[rank]:b[rank + 1]],
                                          bias[b[rank]:b[rank + 1]], b[rank], k, filt=f, kernels=TorchTopkKernels)
-            out.append((s.clone(), i.clone()))
-    q.put((rank, out))
+            out.append((s.numpy().copy(), i.numpy().copy()))
+    q.put((rank, out))      # arrays travel by value: a tensor's shared-memory handle dies with this process
     dist.barrier()
     dist.destroy_process_group()
 
@@ -215,7 +215,7 @@ def test_sharded_topk_equals_unsharded_gloo(world):
             for f in (filt, None):
                 want_s, want_i = pkg.dist.sharded_topk(x[r], filt.query_keys(sub[r], rel[r]), ent, bias, 0, k, filt=f,
                                                        kernels=TorchTopkKernels)
-                got_s, got_i = got[r][j]
+                got_s, got_i = (torch.from_numpy(v) for v in got[r][j])
                 j += 1
                 assert torch.equal(got_i, want_i), (r, k, f is None)
                 assert torch.equal(got_s, want_s), (r, k, f is None)

@@ -1,21 +1,25 @@
 """Randomised check (not part of the test suite) of the aggregation forward + backward kernels against a float64 torch
-restatement (index_add in edge order): random graphs, dims, hub settings; gradients w.r.t. x, the relation table and
-the per-edge table."""
+restatement (index_add in edge order): random graphs, dims (every VEC x CPL geometry of aggregate.hip), hub settings;
+gradients w.r.t. x, the relation table and the per-edge table. Two bars: the tensor-wide max|got - ref| / max|ref| < 2e-5,
+and per element |got - ref| <= (n + 6) u mag of that element's own terms (tests/aggregate_ref.py), which a wrong term in
+a small row or a row that was never written cannot pass."""
 import importlib, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 pkg = importlib.import_module('kgc-gcn_amd')
+A = importlib.import_module('tests.aggregate_ref')
 dev = torch.device('cuda:0')
 
 
 def run(seed=0, trials=50):
     """-> (all trials ok, worst relative deviation); tests/test_gpu_random_shapes.py runs a short instance of it."""
+    # widths: VEC 4 with CPL 1 (4, 36, 100, 128, 200), 2 (300), 4 (516), 8 (1028); VEC 1 with CPL 1 (3), 2 (65), 8 (257)
     rng = np.random.default_rng(seed)
     worst = 0.0
     for trial in range(trials):
         N = int(rng.integers(1, 500)); R = int(rng.integers(1, 7)); E = int(rng.integers(1, 3000))
-        D = int(rng.choice([3, 4, 36, 100, 128, 200, 300]))
+        D = int(rng.choice([3, 4, 36, 100, 128, 200, 300, 65, 257, 516, 1028]))
         s = rng.integers(0, N, E)
         if rng.integers(0, 2) and N > 1:
             pz = 1.0 / np.arange(1, N + 1) ** 1.2
@@ -53,9 +57,16 @@ def run(seed=0, trials=50):
         errs = (dev_max(out, ref.detach()), dev_max(xg.grad, xd.grad), dev_max(rg.grad, rd.grad),
                 dev_max(eg.grad.index_select(0, csr.inv_perm), ed.grad))
         worst = max(worst, max(errs))
-        ok = max(errs) < 2e-5
-        print('trial %2d N=%3d R=%d E=%4d D=%3d hubs(thr=%d, chunks=%d)  rel.err fwd %.1e gx %.1e grel %.1e gee %.1e %s'
-              % ((trial, N, R, E, D, thr, csr.num_chunks) + errs + ('ok' if ok else 'MISMATCH',)))
+        # per element against the bar of its own terms (explicit float64 sums of the same edge list)
+        fwd_ref = A.ref_forward(N, ei, et, x, rel, ee)
+        gx_ref, gee_ref, grel_ref = A.ref_grads(N, ei, et, x, rel, ee, G)
+        per = [A.worst_ratio(got.detach().cpu(), ref) for got, ref in
+               ((out, fwd_ref), (xg.grad, gx_ref), (rg.grad, grel_ref), (eg.grad.index_select(0, csr.inv_perm), gee_ref))]
+        ratios, nonzero = tuple(p[0] for p in per), sum(p[1] for p in per)
+        ok = max(errs) < 2e-5 and max(ratios) <= 1.0 and nonzero == 0
+        print('trial %2d N=%3d R=%d E=%4d D=%4d hubs(thr=%d, chunks=%d)  rel.err fwd %.1e gx %.1e grel %.1e gee %.1e  '
+              'per-element error / bar fwd %.3f gx %.3f grel %.3f gee %.3f, term-less elements not 0.0: %d %s'
+              % ((trial, N, R, E, D, thr, csr.num_chunks) + errs + ratios + (nonzero, 'ok' if ok else 'MISMATCH')))
         if not ok:
             return False, worst
     print('worst relative deviation %.2e' % worst)
