@@ -505,6 +505,64 @@ int mgcn_conve_trunk_fwd(int32_t batch, int32_t k_w, int32_t k_h, int32_t kernel
                          const int64_t *rel_index_dev, const void *packed_dev, float *out_dev, int64_t ldo,
                          void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (9) ConvE query trunk, training mode, forward and backward (csrc/conve_train.hip): bn0 -> convolution -> bn1 -> relu ->
+ * feature_drop -> fc with BATCH statistics, from the gathered rows s, r [B, O] (rows lds / ldr floats apart) to z [B, ldz >= O].
+ * With the image x[b, 2 j] = s[b, j], x[b, 2 j + 1] = r[b, j] of (8), P = H W, K = num_filter P, pi(p, t) the image element
+ * under tap t of position p:
+ *   bn0 (one channel, n0 = 2 O B): mu0, var0 (biased), xh = (x - mu0) rstd0, x0 = g0 xh + b0
+ *   c[b, f, p] = cb[f] + sum_t w[f, t] x0[b, pi(p, t)]            an fma chain in tap order, from cb[f] (0 without a bias)
+ *   bn1 (per filter, n1 = B P): mu1, var1, ch = (c - mu1) rstd1, a = g1 ch + b1
+ *   h[b, k] = keep[b, k] inv_keep max(a, 0), k = f P + p          keep: one byte per element, NULL = keep all (inv_keep is 1)
+ *   z = h fc_w^T + fc_b
+ * and for gz [B, ldg >= O]:
+ *   d fc_b = sum_b gz;  d fc_w[o, k] = sum_b gz[b, o] h[b, k];  gh = gz fc_w
+ *   ga = gh keep inv_keep [a > 0] (0 at a == 0);  d b1[f] = sum_{b, p} ga;  d g1[f] = sum_{b, p} ga ch
+ *   gc = g1 rstd1 (ga - d b1 / n1 - ch d g1 / n1)
+ *   d cb[f] = sum gc;  d w[f, t] = sum_{b, p} gc[b, f, p] x0[b, pi(p, t)];  gx0[b, i] = sum over pi(p, t) = i of gc[b, f, p] w[f, t]
+ *   d b0 = sum gx0;  d g0 = sum gx0 xh;  gx = g0 rstd0 (gx0 - d b0 / n0 - xh d g0 / n0);  ds[b, j] = gx[b, 2 j], dr[b, j] = gx[b, 2 j + 1]
+ * Variances are two-pass (mean, then centred squares), rstd = 1 / sqrt(var + eps). The forward writes saved_dev
+ * [2 + 2 num_filter] = mu0, rstd0, mu1[...], rstd1[...] and updates the running statistics in place as nn.BatchNorm does
+ * (running = (1 - momentum) running + momentum stat, the variance unbiased: n / (n - 1)); num_batches_tracked is the caller's.
+ * Arithmetic: exact f32. The three products (h fc_w^T, gz^T h, gz fc_w) run on v_mfma_f32_16x16x4_f32; h is formed from c in the
+ * register that feeds the MFMA. Convolution, correlation and tap gradients are fmaf chains.
+ * Reductions: no atomics, no spinning, no workgroup waits on another. Every sum over the batch is a multi-launch reduction: one
+ * partial per block of rows (bn0: 8 rows; bn1, its backward sums, taps and conv bias: 16 rows; d fc_b: 32 rows; the bn0 backward
+ * sums: 1 row, folded in blocks of 16 rows and then across the blocks), each a strided per-thread chain and a halving tree over the workgroup, then the partials added in ascending
+ * block order from 0. h fc_w^T is cut along K into up to 128 splits of whole 16-element units; a split is one MFMA chain in
+ * ascending k, the splits are added in ascending order from 0, then the bias. gz^T h is one chain over ascending rows, gz fc_w one
+ * over ascending outputs. The launch plan is a function of (batch, geometry) alone: same inputs and mask, same bits.
+ * workspace_dev: mgcn_conve_train_workspace(batch, ...) bytes (0 = refused), 16-byte aligned, in floats from its start (each
+ * section rounded up to 4): c [B, K] (the forward leaves it there and the backward READS it: pass the same, untouched workspace),
+ * ga / gc [B, K], gx0 [B, 2 O], split partials [S, B, O], the (mu1, rstd1, g1, b1) table [num_filter, 4], (mu0, rstd0, g0, b0),
+ * then the partials of bn0 (sum, squares), bn1 (sum, squares), bn1 backward, bn0 backward, taps + conv bias, d fc_b.
+ * The backward also takes the forward's s, r, weights, mask and saved_dev. A NULL gradient pointer skips that output (and the
+ * launches only it needs) and leaves the bits of the others unchanged. conv_w [num_filter, kernel_size^2] contiguous; conv_b,
+ * fc_b and keep_dev may be NULL; the BN gamma / beta and running pointers are required.
+ * Takes the geometries of (8) (k_w k_h == O <= 512, 1 <= kernel_size <= min(2 k_w, k_h), num_filter >= 1) and 1 <= B <= 4096 with
+ * B P >= 2 and B K < 2^31. All checks precede the first launch: MGCN_EINVAL for a null required pointer, a negative size, a
+ * leading dimension that is too small, a misaligned or too small workspace, and anything that is not a ConvE geometry;
+ * MGCN_EUNSUPPORTED, nothing written, for the rest.
+ */
+size_t mgcn_conve_train_workspace(int32_t batch, int32_t k_w, int32_t k_h, int32_t kernel_size, int32_t num_filter,
+                                  int32_t dim_out);
+int mgcn_conve_train_fwd(int32_t batch, int32_t k_w, int32_t k_h, int32_t kernel_size, int32_t num_filter, int32_t dim_out,
+                         const float *s_dev, int64_t lds, const float *r_dev, int64_t ldr, const float *conv_w_dev,
+                         const float *conv_b_dev, const float *fc_w_dev, int64_t ldw, const float *fc_b_dev,
+                         const float *bn0_gamma_dev, const float *bn0_beta_dev, float *bn0_running_mean_dev,
+                         float *bn0_running_var_dev, float bn0_momentum, float bn0_eps, const float *bn1_gamma_dev,
+                         const float *bn1_beta_dev, float *bn1_running_mean_dev, float *bn1_running_var_dev, float bn1_momentum,
+                         float bn1_eps, const uint8_t *keep_dev, float inv_keep, float *z_dev, int64_t ldz, float *saved_dev,
+                         void *workspace_dev, size_t workspace_bytes, void *stream);
+int mgcn_conve_train_bwd(int32_t batch, int32_t k_w, int32_t k_h, int32_t kernel_size, int32_t num_filter, int32_t dim_out,
+                         const float *s_dev, int64_t lds, const float *r_dev, int64_t ldr, const float *conv_w_dev,
+                         const float *fc_w_dev, int64_t ldw, const float *bn0_gamma_dev, const float *bn0_beta_dev,
+                         const float *bn1_gamma_dev, const float *bn1_beta_dev, const uint8_t *keep_dev, float inv_keep,
+                         const float *saved_dev, const float *gz_dev, int64_t ldg, float *ds_dev, int64_t ldds, float *dr_dev,
+                         int64_t lddr, float *d_conv_w_dev, float *d_conv_b_dev, float *d_bn0_gamma_dev, float *d_bn0_beta_dev,
+                         float *d_bn1_gamma_dev, float *d_bn1_beta_dev, float *d_fc_w_dev, int64_t lddw, float *d_fc_b_dev,
+                         void *workspace_dev, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

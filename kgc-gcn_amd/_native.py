@@ -72,6 +72,11 @@ _SIGNATURES = {
     'mgcn_conve_trunk_workspace': (ctypes.c_size_t, [_i32] * 6),
     'mgcn_conve_trunk_fwd': (ctypes.c_int, [_i32] * 6 + [_ptr, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _ptr,
                                             ctypes.c_size_t, _ptr]),
+    'mgcn_conve_train_workspace': (ctypes.c_size_t, [_i32] * 6),
+    'mgcn_conve_train_fwd': (ctypes.c_int, [_i32] * 6 + [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr] +
+                             [_ptr, _ptr, _ptr, _ptr, _f32, _f32] * 2 + [_ptr, _f32, _ptr, _i64, _ptr, _ptr, ctypes.c_size_t, _ptr]),
+    'mgcn_conve_train_bwd': (ctypes.c_int, [_i32] * 6 + [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64] + [_ptr] * 5 + [_f32, _ptr, _ptr, _i64,
+                                                         _ptr, _i64, _ptr, _i64] + [_ptr] * 7 + [_i64, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
     'mgcn_ingest_count': (_i64, [_ptr, _i32]),
@@ -855,6 +860,73 @@ def conve_trunk(geom, packed, ent, src, rel, rel_idx, out=None):
                                       _dev(rel_idx, torch.int64, 'rel index', True), _dev(packed, torch.float32, 'pack'),
                                       _dev(out, torch.float32, 'out'), _ld(out) if B > 1 else max(out.stride(0), O),
                                       _dev(ws, torch.uint8, 'workspace', True), nbytes, _stream(ent)), 'mgcn_conve_trunk_fwd')
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# (9) ConvE query trunk, training mode. geom = (k_w, k_h, kernel_size, num_filter, O)
+def conve_train_supported(batch, geom):
+    """Batches and geometries mgcn_conve_train_fwd takes (those of (8), 1 <= B <= 4096, B H W >= 2, B F H W < 2^31)."""
+    geom = tuple(int(v) for v in geom)
+    return min(geom) >= 1 and int(batch) >= 1 and lib().mgcn_conve_train_workspace(int(batch), *geom) > 0
+
+
+def _rows(t, O, what):
+    if t.dim() != 2 or t.size(1) != O:
+        raise NativeError('%s must be [B, %d], got %s' % (what, O, tuple(t.shape)))
+    return _dev(t, torch.float32, what), (_ld(t) if t.size(0) > 1 else max(t.stride(0), O))
+
+
+def conve_train_fwd(geom, s, r, conv_w, conv_b, fc_w, fc_b, bn0, bn1, keep, inv_keep):
+    """z [B, O], saved statistics [2 + 2 F] (mu0, rstd0, mu1, rstd1) and the workspace that holds c for the backward.
+    bn* = (weight, bias, running_mean, running_var, momentum, eps); the running statistics are updated in place.
+    keep: bool / uint8 [B, F H W] contiguous or None (keep all)."""
+    geom = tuple(int(v) for v in geom)
+    O, B = geom[4], int(s.size(0))
+    nbytes = lib().mgcn_conve_train_workspace(B, *geom)
+    if nbytes == 0:
+        raise NativeError('conve_train_fwd: batch %d of geometry %s is not supported' % (B, geom))
+    if not conv_w.is_contiguous() or fc_w.dim() != 2 or (keep is not None and not keep.is_contiguous()):
+        raise NativeError('conve_train_fwd: conv weight and mask must be contiguous, fc weight 2-d')
+    _same_device(s, r, conv_w, conv_b, fc_w, fc_b, keep, *bn0[:4], *bn1[:4])
+    sp, lds = _rows(s, O, 's')
+    rp, ldr = _rows(r, O, 'r')
+    z = torch.empty((B, O), dtype=torch.float32, device=s.device)
+    saved = torch.empty(2 + 2 * geom[3], dtype=torch.float32, device=s.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+    bn_args = []
+    for gamma, beta, rm, rv, mom, eps in (bn0, bn1):
+        bn_args += [_dev(gamma, torch.float32, 'bn weight'), _dev(beta, torch.float32, 'bn bias'), _dev(rm, torch.float32, 'running mean'),
+                    _dev(rv, torch.float32, 'running var'), float(mom), float(eps)]
+    _check(lib().mgcn_conve_train_fwd(B, *geom, sp, lds, rp, ldr, _dev(conv_w, torch.float32, 'conv weight'),
+                                      _dev(conv_b, torch.float32, 'conv bias', True), _dev(fc_w, torch.float32, 'fc weight'), _ld(fc_w),
+                                      _dev(fc_b, torch.float32, 'fc bias', True), *bn_args,
+                                      None if keep is None else keep.data_ptr(), float(inv_keep), _dev(z, torch.float32, 'z'), O,
+                                      _dev(saved, torch.float32, 'saved'), ws.data_ptr(), nbytes, _stream(s)), 'mgcn_conve_train_fwd')
+    return z, saved, ws
+
+
+def conve_train_bwd(geom, s, r, conv_w, fc_w, bn0_weight, bn0_bias, bn1_weight, bn1_bias, keep, inv_keep, saved, ws, gz, want):
+    """The gradients named in `want` (a set of 's', 'r', 'conv_w', 'conv_b', 'g0', 'b0', 'g1', 'b1', 'fc_w', 'fc_b') as a
+    dict; `ws` is the forward's workspace, untouched."""
+    geom = tuple(int(v) for v in geom)
+    k_w, k_h, ks, F, O = geom
+    B = int(s.size(0))
+    sp, lds = _rows(s, O, 's')
+    rp, ldr = _rows(r, O, 'r')
+    gp, ldg = _rows(gz, O, 'gz')
+    _same_device(s, r, conv_w, fc_w, keep, saved, ws, gz)
+    shapes = {'s': (B, O), 'r': (B, O), 'conv_w': tuple(conv_w.shape), 'conv_b': (F,), 'g0': (1,), 'b0': (1,), 'g1': (F,), 'b1': (F,),
+              'fc_w': (O, fc_w.size(1)), 'fc_b': (O,)}
+    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=s.device) for k in shapes if k in want}
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    _check(lib().mgcn_conve_train_bwd(B, *geom, sp, lds, rp, ldr, _dev(conv_w, torch.float32, 'conv weight'),
+                                      _dev(fc_w, torch.float32, 'fc weight'), _ld(fc_w), _dev(bn0_weight, torch.float32, 'bn0 weight'),
+                                      _dev(bn0_bias, torch.float32, 'bn0 bias'), _dev(bn1_weight, torch.float32, 'bn1 weight'),
+                                      _dev(bn1_bias, torch.float32, 'bn1 bias'), None if keep is None else keep.data_ptr(),
+                                      float(inv_keep), _dev(saved, torch.float32, 'saved'), gp, ldg, ptr('s'), O, ptr('r'), O,
+                                      ptr('conv_w'), ptr('conv_b'), ptr('g0'), ptr('b0'), ptr('g1'), ptr('b1'), ptr('fc_w'),
+                                      fc_w.size(1), ptr('fc_b'), ws.data_ptr(), ws.numel(), _stream(s)), 'mgcn_conve_train_bwd')
     return out
 
 

@@ -605,13 +605,9 @@ class _ScoreBCEShardFn(torch.autograd.Function):
 
 
 def _dropout(x, p, generator):
-    """F.dropout with the keep-mask drawn from `generator`."""
-    if p <= 0:
-        return x
-    if p >= 1:
-        return x * 0.0
-    keep = 1.0 - p
-    return x * torch.empty_like(x).bernoulli_(keep, generator=generator) * (1.0 / keep)
+    """F.dropout with the keep-mask drawn from `generator` (model._drawn_dropout: the one both trunk paths use)."""
+    from .model import _drawn_dropout
+    return _drawn_dropout(x, p, generator)
 
 
 def _trunk(conv2, src_emb, rel_emb, generator):
@@ -619,6 +615,8 @@ def _trunk(conv2, src_emb, rel_emb, generator):
     import torch.nn.functional as F
     if generator is None or not conv2.training:
         return conv2.trunk(src_emb, rel_emb)
+    if conv2._hip_trunk_train(src_emb, rel_emb):      # the HIP training trunk draws the same two masks from `generator`
+        return conv2._trunk_train(src_emb, rel_emb, generator)
     p = conv2.params
     o = p.gcn_out_dim
     stack = torch.cat([src_emb.view(-1, 1, o), rel_emb.view(-1, 1, o)], dim=1)

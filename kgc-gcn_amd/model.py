@@ -10,8 +10,10 @@ What runs where
     launch (csrc/dense.hip). In training mode (batch statistics, dropout) the products, the BN reductions, tanh and
     their backward run on csrc/train_layer.hip kernels behind torch.autograd.Function (only the dropout masks are torch's);
   * full-graph scoring (model.py:177-179) and the filtered rank counts (main.py:122-126): HIP;
-  * the ConvE conv trunk (model.py:161-175): stock torch modules (MIOpen / rocBLAS) by default and always in training; with
-    params.conve_trunk = 'hip' (or MGCN_TRUNK=hip) the eval-mode trunk is ONE HIP launch from the two tables to x (csrc/conve_trunk.hip).
+  * the ConvE conv trunk (model.py:161-175): stock torch modules (MIOpen / rocBLAS) by default; with
+    params.conve_trunk = 'hip' (or MGCN_TRUNK=hip) the eval-mode trunk is ONE HIP launch from the two tables to x (csrc/conve_trunk.hip);
+    with params.conve_trunk_train = 'hip' (or MGCN_TRUNK_TRAIN=hip) the training-mode trunk up to fc, forward and backward, runs on
+    csrc/conve_train.hip (hidden_drop, bn2 and the last relu stay torch modules).
 There is no CPU path: tensors that are not on a GPU make the native layer raise.
 """
 import os
@@ -101,6 +103,42 @@ class _LayerTrainFn(torch.autograd.Function):
             g_wloop = _native.matmul_tn(a_loop.contiguous(), gu)
         g_bias = gz.sum(0) if (ctx.has_bias and need[5]) else None
         return g_agg, g_loop, g_win, g_wout, g_wloop, g_bias, ggamma, gbeta, None, None, None, None, None
+
+
+class _TrunkTrainFn(torch.autograd.Function):
+    """Training-mode ConvE trunk from the gathered rows to the fc output (model.py:164-171 under .train()) on the kernels of
+    csrc/conve_train.hip: z = fc(feature_drop(relu(bn1(conv_e(bn0(image(s, r))))))) with batch statistics, and its backward.
+    Saves the workspace that holds the pre-BN convolution output c, the bool keep-mask (1 byte per element, scaled by
+    1 / keep at use) and the batch statistics; the running statistics of bn0 / bn1 are updated in place."""
+
+    @staticmethod
+    def forward(ctx, s, r, conv_w, conv_b, fc_w, fc_b, g0, b0, g1, b1, bn0_stats, bn1_stats, keep, inv_keep, geom):
+        z, saved, ws = _native.conve_train_fwd(geom, s, r, conv_w, conv_b, fc_w, fc_b, (g0, b0) + bn0_stats, (g1, b1) + bn1_stats,
+                                               keep, inv_keep)
+        ctx.save_for_backward(s, r, conv_w, fc_w, g0, b0, g1, b1, keep, saved, ws)
+        ctx.geom, ctx.inv_keep, ctx.has_conv_bias, ctx.has_fc_bias = geom, inv_keep, conv_b is not None, fc_b is not None
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        s, r, conv_w, fc_w, g0, b0, g1, b1, keep, saved, ws = ctx.saved_tensors
+        names = ('s', 'r', 'conv_w', 'conv_b', 'fc_w', 'fc_b', 'g0', 'b0', 'g1', 'b1')
+        want = {n for i, n in enumerate(names) if ctx.needs_input_grad[i]}
+        want -= set() if ctx.has_conv_bias else {'conv_b'}
+        want -= set() if ctx.has_fc_bias else {'fc_b'}
+        gz = gz if gz.stride(-1) == 1 else gz.contiguous()
+        g = _native.conve_train_bwd(ctx.geom, s, r, conv_w, fc_w, g0, b0, g1, b1, keep, ctx.inv_keep, saved, ws, gz, want)
+        return tuple(g.get(n) for n in names) + (None,) * 5
+
+
+def _drawn_dropout(x, p, generator):
+    """F.dropout with the keep-mask drawn by bernoulli_ from `generator` (None: the default generator); dist._dropout is this."""
+    if p <= 0:
+        return x
+    if p >= 1:
+        return x * 0.0
+    keep = 1.0 - p
+    return x * torch.empty_like(x).bernoulli_(keep, generator=generator) * (1.0 / keep)
 
 
 class _ScoreFn(torch.autograd.Function):
@@ -332,7 +370,55 @@ class ConvE(nn.Module):
             self._pack_count = getattr(self, '_pack_count', 0) + 1
         return self._pack
 
-    def trunk(self, src_emb, rel_emb):
+    def _hip_trunk_train(self, src_emb, rel_emb):
+        """Whether this call takes the HIP training trunk: the switch (params.conve_trunk_train == 'hip', overridden in both
+        directions by the environment variable MGCN_TRUNK_TRAIN), training mode, f32 inputs and weights on the GPU, bn0 / bn1
+        affine and tracking running statistics with a numeric momentum, more than one value per channel, a batch and geometry
+        the kernels take."""
+        want = os.environ.get('MGCN_TRUNK_TRAIN') or getattr(self.params, 'conve_trunk_train', 'torch')
+        if want != 'hip' or not self.training:
+            return False
+        if src_emb.dim() != 2 or src_emb.shape != rel_emb.shape or src_emb.size(1) != self.params.gcn_out_dim:
+            return False
+        ts = [src_emb, rel_emb, self.conv_e.weight, self.fc.weight, self.bn0.weight, self.bn0.bias, self.bn1.weight, self.bn1.bias,
+              self.bn0.running_mean, self.bn0.running_var, self.bn1.running_mean, self.bn1.running_var]
+        if any(t is None or not t.is_cuda or t.dtype != torch.float32 for t in ts) or self.fc.bias is None:
+            return False
+        if any(not isinstance(bn.momentum, float) or not bn.track_running_stats for bn in (self.bn0, self.bn1)):
+            return False
+        k_w, k_h, ks, _, _ = self._geometry()
+        if src_emb.size(0) * (2 * k_w - ks + 1) * (k_h - ks + 1) <= 1:
+            return False
+        return _native.conve_train_supported(src_emb.size(0), self._geometry())
+
+    def _trunk_train(self, src_emb, rel_emb, generator):
+        src_emb = src_emb if src_emb.stride(1) == 1 else src_emb.contiguous()
+        rel_emb = rel_emb if rel_emb.stride(1) == 1 else rel_emb.contiguous()
+        # the feature mask is drawn first, then the hidden one: dist._dropout's draws, on tensors of the activations' shapes
+        p, keep, inv_keep = self.feature_drop.p, None, 1.0
+        shape = (src_emb.size(0), self.flat_sz)
+        if p >= 1:
+            keep, inv_keep = torch.zeros(shape, dtype=torch.bool, device=src_emb.device), 0.0
+        elif p > 0:
+            keep = torch.empty(shape, dtype=torch.float32, device=src_emb.device).bernoulli_(1.0 - p, generator=generator).bool()
+            inv_keep = 1.0 / (1.0 - p)
+        bn0, bn1 = self.bn0, self.bn1
+        z = _TrunkTrainFn.apply(src_emb, rel_emb, self.conv_e.weight, self.conv_e.bias, self.fc.weight, self.fc.bias, bn0.weight,
+                                bn0.bias, bn1.weight, bn1.bias, (bn0.running_mean, bn0.running_var, bn0.momentum, bn0.eps),
+                                (bn1.running_mean, bn1.running_var, bn1.momentum, bn1.eps), keep, inv_keep, self._geometry())
+        with torch.no_grad():
+            bn0.num_batches_tracked += 1
+            bn1.num_batches_tracked += 1
+        self._trunk_train_count = getattr(self, '_trunk_train_count', 0) + 1
+        return F.relu(self.bn2(_drawn_dropout(z, self.hidden_drop.p, generator))).contiguous()
+
+    def trunk(self, src_emb, rel_emb, generator=None):
+        """x [B, O] of the queries. In training mode with params.conve_trunk_train == 'hip' (or MGCN_TRUNK_TRAIN=hip) the block
+        up to fc runs on csrc/conve_train.hip, forward and backward; its two dropout masks are then drawn with bernoulli_
+        from `generator` (None: the default generator), feature mask first -- the same masks dist._trunk's torch path draws
+        from the same generator state, but not the stream F.dropout itself would consume. `generator` is not used otherwise."""
+        if self._hip_trunk_train(src_emb, rel_emb):
+            return self._trunk_train(src_emb, rel_emb, generator)
         if self._hip_trunk(src_emb, rel_emb) and src_emb.dim() == 2 and src_emb.shape == rel_emb.shape \
                 and src_emb.size(1) == self.params.gcn_out_dim:
             src_emb = src_emb if src_emb.stride(1) == 1 else src_emb.contiguous()
