@@ -563,6 +563,41 @@ int mgcn_conve_train_bwd(int32_t batch, int32_t k_w, int32_t k_h, int32_t kernel
                          float *d_bn1_gamma_dev, float *d_bn1_beta_dev, float *d_fc_w_dev, int64_t lddw, float *d_fc_b_dev,
                          void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (10) Global-norm clipping and the Adam update (csrc/optim.hip; replaces main.py:69-70, clip_grad_norm_ followed by
+ * torch.optim.Adam.step, amsgrad = False, maximize = False). Three entry points over a LIST of n f32 tensors, given as HOST
+ * arrays of device pointers and of int64 element counts; a tensor with a NULL gradient or 0 elements is skipped (its other
+ * pointers may be NULL, nothing of it is read or written). Nothing is kept between calls: the pointers travel by value in
+ * the kernel arguments, MGCN_ADAM_BATCH tensors per launch, one workgroup per MGCN_ADAM_CHUNK elements of a tensor.
+ * mgcn_adam_sq_norms: sq_dev[i] = sum of squares of gradient i (0 for a skipped one), i < n. Order: a workgroup sums its
+ *   chunk (256 threads, each four chains over its float4s in ascending order, combined (c0 + c1) + (c2 + c3), then a halving
+ *   tree); one wave folds a tensor's chunk partials in double (lane l takes chunks l, l + 64, ... in ascending order, then
+ *   a halving tree over the lanes). No atomics: same inputs, same bits. workspace_dev: mgcn_adam_sq_norms_workspace bytes
+ *   (one float per chunk of EVERY tensor of the list, 4-byte aligned; NULL allowed when that is 0).
+ * mgcn_adam_clip_coef: out_dev[0] = total = sqrt(sum of sq_dev[0 .. n)) (summed in double as above), out_dev[1] = coef =
+ *   min(max_norm / (total + 1e-6), 1), clip_grad_norm_'s formulas in f32. A caller that shards tensors over devices
+ *   all-reduces those entries of sq_dev between the two calls; the host never reads the norm.
+ * mgcn_adam_step, per element, in f32, in this order of operations (torch's single-tensor Adam; no contraction):
+ *   g' = coef g;  g' = g' + weight_decay p (only when weight_decay != 0);  m = m + (1 - beta1)(g' - m);
+ *   v = v beta2 + ((1 - beta2) g') g';  p = p + (-step_size)(m / (sqrt(v) / bc2_sqrt + eps))
+ *   with step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) formed by the caller in double; coef is read from
+ *   coef_dev (out_dev + 1 of the call above), NULL = 1. Gradients are read, never written. 16-byte accesses when the four
+ *   bases of a tensor are 16-byte aligned, scalar accesses otherwise and for the last numel % 4 elements.
+ * All checks precede the first launch and write nothing: MGCN_EINVAL for n < 0, a NULL array, a negative length, a live
+ * tensor with a NULL p / m / v, a beta outside [0, 1), eps, weight_decay, max_norm or step_size (a negative lr) below 0 or
+ * not a number, bc2_sqrt outside (0, 1], a NULL, misaligned or too small workspace; MGCN_EUNSUPPORTED for more than 2^31
+ * chunks in one launch.
+ */
+#define MGCN_ADAM_CHUNK 8192 /* elements per workgroup */
+#define MGCN_ADAM_BATCH 64   /* tensors per launch */
+size_t mgcn_adam_sq_norms_workspace(int64_t n, const int64_t *numel_host);
+int mgcn_adam_sq_norms(int64_t n, const float *const *grad_host, const int64_t *numel_host, float *sq_dev,
+                       void *workspace_dev, size_t workspace_bytes, void *stream);
+int mgcn_adam_clip_coef(int64_t n, const float *sq_dev, float max_norm, float *out_dev, void *stream);
+int mgcn_adam_step(int64_t n, const float *const *grad_host, float *const *param_host, float *const *exp_avg_host,
+                   float *const *exp_avg_sq_host, const int64_t *numel_host, const float *coef_dev, float step_size,
+                   float bc2_sqrt, double beta1, double beta2, double eps, double weight_decay, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

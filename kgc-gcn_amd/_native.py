@@ -77,6 +77,10 @@ _SIGNATURES = {
                              [_ptr, _ptr, _ptr, _ptr, _f32, _f32] * 2 + [_ptr, _f32, _ptr, _i64, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_conve_train_bwd': (ctypes.c_int, [_i32] * 6 + [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64] + [_ptr] * 5 + [_f32, _ptr, _ptr, _i64,
                                                          _ptr, _i64, _ptr, _i64] + [_ptr] * 7 + [_i64, _ptr, _ptr, ctypes.c_size_t, _ptr]),
+    'mgcn_adam_sq_norms_workspace': (ctypes.c_size_t, [_i64, _ptr]),
+    'mgcn_adam_sq_norms': (ctypes.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
+    'mgcn_adam_clip_coef': (ctypes.c_int, [_i64, _ptr, _f32, _ptr, _ptr]),
+    'mgcn_adam_step': (ctypes.c_int, [_i64] + [_ptr] * 6 + [_f32, _f32] + [ctypes.c_double] * 4 + [_ptr]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
     'mgcn_ingest_count': (_i64, [_ptr, _i32]),
@@ -997,6 +1001,74 @@ def label_rows(qkey, keys, ptr, tails, n_local, lbl_smooth=0.0, num_entities=Non
                                  int(n_local), float(y[0]), float(y[1]), _dev(out, torch.float32, 'labels'),
                                  out.stride(0), _stream(qkey)), 'mgcn_label_rows')
     return out
+
+
+ADAM_CHUNK = 8192     # MGCN_ADAM_CHUNK: elements per workgroup of the optimizer kernels (csrc/optim.hip)
+ADAM_BATCH = 64       # MGCN_ADAM_BATCH: tensors per launch
+
+
+def _ptr_array(tensors):
+    """Host array of the tensors' device pointers (None -> NULL)."""
+    return (_ptr * max(len(tensors), 1))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _adam_list(what, lists):
+    """Check a list of f32 device tensors per role (contiguous, same device, same element counts as the first role)."""
+    first = lists[0]
+    for ts in lists:
+        if len(ts) != len(first):
+            raise NativeError('%s: the tensor lists differ in length' % what)
+        for t, ref in zip(ts, first):
+            if t is None:
+                continue
+            _dev(t, torch.float32, what)
+            if not t.is_contiguous() or (ref is not None and t.numel() != ref.numel()):
+                raise NativeError('%s: tensors must be contiguous with matching element counts' % what)
+    _same_device(*[t for ts in lists for t in ts])
+
+
+def adam_sq_norms(grads, out=None):
+    """(10) sq [n] f32: the sum of squares of every gradient of the list (0 for a None or empty one), in a fixed order."""
+    _adam_list('adam_sq_norms', [grads])
+    live = [g for g in grads if g is not None]
+    if not live:
+        raise NativeError('adam_sq_norms: no gradient to take the device from')
+    dev, n = live[0].device, len(grads)
+    numel = (_i64 * max(n, 1))(*[0 if g is None else g.numel() for g in grads])
+    sq = torch.empty(n, dtype=torch.float32, device=dev) if out is None else out
+    if sq.numel() != n or not sq.is_contiguous():
+        raise NativeError('adam_sq_norms: out must be contiguous [%d]' % n)
+    nbytes = lib().mgcn_adam_sq_norms_workspace(n, numel)
+    ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
+    _check(lib().mgcn_adam_sq_norms(n, _ptr_array(grads), numel, _dev(sq, torch.float32, 'sq'), _dev(ws, torch.float32, 'ws'),
+                                    nbytes, _stream(sq)), 'mgcn_adam_sq_norms')
+    return sq
+
+
+def adam_clip_coef(sq, max_norm, out=None):
+    """(10) [2] f32 = (total norm, clip coefficient) from the per-tensor sums of squares; stays on the device."""
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=sq.device)
+    _same_device(sq, out)
+    if not sq.is_contiguous() or out.numel() != 2 or not out.is_contiguous():
+        raise NativeError('adam_clip_coef: sq must be contiguous and out [2]')
+    _check(lib().mgcn_adam_clip_coef(sq.numel(), _dev(sq, torch.float32, 'sq'), float(max_norm), _dev(out, torch.float32, 'out'),
+                                     _stream(sq)), 'mgcn_adam_clip_coef')
+    return out
+
+
+def adam_step(grads, params, exp_avgs, exp_avg_sqs, coef, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay):
+    """(10) One Adam update of the listed tensors in place; `coef`: a 1-element device tensor (None = no clipping). A None
+    or empty gradient skips its tensor."""
+    _adam_list('adam_step', [params, grads, exp_avgs, exp_avg_sqs])
+    _same_device(coef, *params)
+    n = len(params)
+    if n == 0:
+        return
+    numel = (_i64 * n)(*[p.numel() for p in params])
+    _check(lib().mgcn_adam_step(n, _ptr_array(grads), _ptr_array(params), _ptr_array(exp_avgs), _ptr_array(exp_avg_sqs), numel,
+                                _dev(coef, torch.float32, 'coef', True), float(step_size), float(bc2_sqrt), float(beta1),
+                                float(beta2), float(eps), float(weight_decay), _stream(params[0])), 'mgcn_adam_step')
 
 
 class IngestUnsupported(NativeError):

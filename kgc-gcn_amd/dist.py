@@ -741,6 +741,22 @@ def clip_grad_norm_sharded(model, max_norm, group=None):
     return total
 
 
+def _shard_sq_reducer(model, group):
+    """`reduce_sq_norms` of optim.ClipAdam.clip_and_step for the destination-partitioned model: the table shards' sums of
+    squares become their sums over all ranks (SUM all-reduce), as in clip_grad_norm_sharded; the replicated parameters'
+    gradients are already complete on every rank."""
+    shard = {id(p) for _, p in model._edge_tables()}
+
+    def reduce(sq, params):
+        idx = [i for i, p in enumerate(params) if id(p) in shard]
+        if idx:
+            part = torch.stack([sq[i] for i in idx])
+            dist.all_reduce(part, op=dist.ReduceOp.SUM, group=group)
+            for j, i in enumerate(idx):
+                sq[i].copy_(part[j])
+    return reduce
+
+
 def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0, clip=None, group=None, generator=None):
     """One training step (main.py:59-70: forward, BCE against the train index's targets, backward, clipping, optimizer) of the
     destination-partitioned model: rank r owns destinations [n0, n1) = graph.csr(...).balanced_bounds(W)[r:r + 2], the table
@@ -810,9 +826,12 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
     loss.backward()
     if W > 1:
         _reduce_bucket(model, ex, *bucket)
-    if clip is not None:
-        clip_grad_norm_sharded(model, clip, group)
-    optimizer.step()
+    if hasattr(optimizer, 'clip_and_step'):              # optim.ClipAdam: clip=None is a plain step
+        optimizer.clip_and_step(clip, reduce_sq_norms=_shard_sq_reducer(model, group) if W > 1 else None)
+    else:
+        if clip is not None:
+            clip_grad_norm_sharded(model, clip, group)
+        optimizer.step()
     loss = loss.detach().clone()
     return ex.all_reduce(loss)
 

@@ -27,8 +27,11 @@ def train(model, data_iter, graph, optimizer, params):
         pred = model(triplets[:, 0], triplets[:, 1], graph)
         loss = model.loss(pred, labels.to(params.device))
         loss.backward()
-        nn.utils.clip_grad_norm_(parameters=model.parameters(), max_norm=params.clip_grad)
-        optimizer.step()
+        if hasattr(optimizer, 'clip_and_step'):          # optim.ClipAdam: norm, clipping and update on the HIP kernels
+            optimizer.clip_and_step(params.clip_grad)
+        else:
+            nn.utils.clip_grad_norm_(parameters=model.parameters(), max_norm=params.clip_grad)
+            optimizer.step()
         loss_avg.update(loss.item())
     return loss_avg()
 
@@ -55,8 +58,11 @@ def train_device_labels(model, queries, index, graph, optimizer, params, batch_s
                                         lbl_smooth=params.lbl_smooth)
             loss = model.loss(model(q[:, 0], q[:, 1], graph), labels)
         loss.backward()
-        nn.utils.clip_grad_norm_(parameters=model.parameters(), max_norm=params.clip_grad)
-        optimizer.step()
+        if hasattr(optimizer, 'clip_and_step'):          # optim.ClipAdam: norm, clipping and update on the HIP kernels
+            optimizer.clip_and_step(params.clip_grad)
+        else:
+            nn.utils.clip_grad_norm_(parameters=model.parameters(), max_norm=params.clip_grad)
+            optimizer.step()
         loss_avg.update(loss.item())
     return loss_avg()
 
