@@ -437,6 +437,10 @@ int mgcn_label_rows(int32_t batch, const int64_t *qkey_dev, int64_t num_keys, co
  *          mgcn_filter_mask; ldm words per row); mask_dev == NULL excludes nothing;
  *   order  score descending, then global id ascending (compared as f32 values: -0 == +0): the order of a stable
  *          descending sort over the ids in ascending order, the tie rule of the rank counts (rank = 1 + gt + tl);
+ *          NaN scores (mgcn_score_fwd gives none for finite operands; a merge may be handed some) are ordered too: a
+ *          NaN with the sign bit clear ranks above +inf, a NaN with the sign bit set below -inf, and NaNs among
+ *          themselves by bit pattern (IEEE totalOrder with the two zeros merged: the order of an order-preserving
+ *          integer key). A returned zero is +0; a returned NaN is a NaN, its payload unspecified;
  *   output out_score [B, ldo >= k] f32 and out_id [B, ldi >= k] int64 in that order; a row with fewer than k unfiltered
  *          entities is padded at its end with score -inf and id -1.
  * The result depends on nothing but the scores: not on the chunking, the launch geometry, the arrival order of the

@@ -766,39 +766,57 @@ def _check_k(k, what):
     return int(k)
 
 
-def score_topk(x, ent, bias, k, mask=None, ent_row0=0):
+def _topk_out(out, B, k, device, what, contiguous):
+    """The (scores [B, k] f32, ids [B, k] int64) pair a top-k call writes: fresh, or the caller's `out` views."""
+    if out is None:
+        return (torch.empty((B, k), dtype=torch.float32, device=device),
+                torch.empty((B, k), dtype=torch.int64, device=device))
+    scores, ids = out
+    for t, name in ((scores, 'scores'), (ids, 'ids')):
+        if t.dim() != 2 or tuple(t.shape) != (B, k):
+            raise NativeError('%s: out %s %s must be (%d, %d)' % (what, name, tuple(t.shape), B, k))
+        if contiguous and not t.is_contiguous():
+            raise NativeError('%s: out %s must be contiguous' % (what, name))
+        if B > 1 and t.stride(0) < k:
+            raise NativeError('%s: out %s rows overlap (stride %d < %d)' % (what, name, t.stride(0), k))
+    return scores, ids
+
+
+def score_topk(x, ent, bias, k, mask=None, ent_row0=0, out=None):
     """(7) The k best entities of this shard per query: (scores [B, k] f32, ids [B, k] int64 global ids), score
     descending then id ascending, each score the f32 value of score_fwd; entities whose bit is set in the bit-packed
     `mask` [B, >= ceil(n/32)] int32 of filter_mask() are excluded; a row with fewer than k entities left ends in
-    (-inf, -1) padding (see mgcn_score_topk)."""
+    (-inf, -1) padding (see mgcn_score_topk). out = (scores, ids): 2-d [B, k] views to write into, their row strides
+    are the ABI's ldo / ldi (columns outside the views are left alone)."""
     B, n, O = _score_args(x, ent, bias)
     k = _check_k(k, 'score_topk')
     if mask is not None and (mask.dim() != 2 or mask.size(0) != B or mask.size(1) < (n + 31) // 32 or not mask.is_contiguous()):
         raise NativeError('score_topk: mask must be contiguous (%d, >= %d)' % (B, (n + 31) // 32))
-    _same_device(x, ent, bias, mask)
-    scores = torch.empty((B, k), dtype=torch.float32, device=x.device)
-    ids = torch.empty((B, k), dtype=torch.int64, device=x.device)
+    scores, ids = _topk_out(out, B, k, x.device, 'score_topk', False)
+    _same_device(x, ent, bias, mask, scores, ids)
     nbytes = lib().mgcn_score_topk_workspace(B, n, k)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)    # the caching allocator's memory
     _check(lib().mgcn_score_topk(B, n, int(ent_row0), O, _dev(x, torch.float32, 'x'), _ld(x),
                                  _dev(ent, torch.float32, 'ent'), _ld(ent), _dev(bias, torch.float32, 'bias'),
                                  _dev(mask, torch.int32, 'mask', True), mask.size(1) if mask is not None else 0, k,
-                                 _dev(scores, torch.float32, 'scores'), k, _dev(ids, torch.int64, 'ids'), k,
+                                 _dev(scores, torch.float32, 'scores'), _ld(scores),
+                                 _dev(ids, torch.int64, 'ids'), _ld(ids),
                                  _dev(ws, torch.uint8, 'workspace'), nbytes, _stream(x)), 'mgcn_score_topk')
     return scores, ids
 
 
-def topk_merge(scores, ids, k):
+def topk_merge(scores, ids, k, out=None):
     """(7) The top-k of candidate lists laid side by side: scores [B, L] f32, ids [B, L] int64 with L a multiple of k
-    (L / k lists of k, id -1 = padding) -> (scores [B, k], ids [B, k]) in the order of score_topk (see mgcn_topk_merge)."""
+    (L / k lists of k, id -1 = padding) -> (scores [B, k], ids [B, k]) in the order of score_topk (see mgcn_topk_merge).
+    out = (scores, ids): contiguous [B, k] tensors to write into (the ABI has no output stride)."""
     k = _check_k(k, 'topk_merge')
     _same_device(scores, ids)
     if scores.dim() != 2 or ids.shape != scores.shape or scores.size(1) % k != 0:
         raise NativeError('topk_merge: scores %s / ids %s must be equal [B, lists * %d]' % (tuple(scores.shape), tuple(ids.shape), k))
     B, lists = scores.size(0), scores.size(1) // k
     scores, ids = scores.contiguous(), ids.contiguous()
-    out_s = torch.empty((B, k), dtype=torch.float32, device=scores.device)
-    out_i = torch.empty((B, k), dtype=torch.int64, device=scores.device)
+    out_s, out_i = _topk_out(out, B, k, scores.device, 'topk_merge', True)
+    _same_device(scores, out_s, out_i)
     _check(lib().mgcn_topk_merge(B, lists, _dev(scores, torch.float32, 'scores'), _dev(ids, torch.int64, 'ids'),
                                  scores.size(1), k, _dev(out_s, torch.float32, 'out scores'),
                                  _dev(out_i, torch.int64, 'out ids'), _stream(scores)), 'mgcn_topk_merge')

@@ -49,13 +49,13 @@ struct TopkShared {
   uint32_t count, ocount, digit, above, bin;
 };
 
-// Order-preserving key of an f32 score; 0 is kept free to mean "no candidate" (only the NaN pattern 0xffffffff maps
-// there, and it is moved to 1).
+// Order-preserving key of an f32 score: a bijection of the bit patterns (-0 folded onto +0 first) onto an unsigned order
+// that is IEEE totalOrder, so NaNs with the sign bit clear rank above +inf, NaNs with it set below -inf, by bit pattern.
+// Every value of the key is a candidate's (0 is the NaN 0xffffffff): "no candidate" is carried beside the key.
 __device__ __forceinline__ uint32_t score_key(float s) {
   uint32_t u = __float_as_uint(s);
   if (u == 0x80000000u) u = 0u;
-  const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return key ? key : 1u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 __device__ __forceinline__ float key_score(uint32_t key) {
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkArgs p) {
   int count = 0;
   if (!MERGE) {   // a segment is one fill: all its loads first, then the appends
     constexpr int PER = TK_SEG / TK_THREADS;
-    uint32_t key[PER];
+    uint32_t key[PER], live = 0u;   // bit r of live: column r of this thread is an unfiltered candidate
 #pragma unroll
     for (int r = 0; r < PER; ++r) {
       const int64_t j = begin + r * TK_THREADS + tid;
@@ -176,13 +176,17 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkArgs p) {
           const int64_t m = p.mask0 + j;
           filtered = (p.mask[b * p.ldm + (m >> 5)] >> (m & 31)) & 1u;
         }
-        if (!filtered) key[r] = score_key(p.score[b * p.lds + j]);
+        if (!filtered) {
+          key[r] = score_key(p.score[b * p.lds + j]);
+          live |= 1u << r;
+        }
       }
     }
 #pragma unroll
     for (int r = 0; r < PER; ++r) {
-      const uint32_t slot = wave_append(key[r] != 0u, &sh.count);
-      if (key[r] != 0u) {
+      const bool has = (live >> r) & 1u;
+      const uint32_t slot = wave_append(has, &sh.count);
+      if (has) {
         sh.key[slot] = key[r];
         sh.id[slot] = uint32_t(p.id0 + begin + r * TK_THREADS + tid);
       }
@@ -199,16 +203,18 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkArgs p) {
     for (int base = 0; base < take; base += TK_THREADS) {
       const int i = base + tid;
       uint32_t key = 0u, id = 0u;
+      bool has = false;
       if (i < take) {
         const int64_t j = pos + i;
         const int64_t gid = p.in_id[b * p.ld_in + j];
         if (gid >= 0) {
           key = score_key(p.in_score[b * p.ld_in + j]);
           id = uint32_t(gid);
+          has = true;
         }
       }
-      const uint32_t slot = wave_append(key != 0u, &sh.count);
-      if (key != 0u) {
+      const uint32_t slot = wave_append(has, &sh.count);
+      if (has) {
         sh.key[slot] = key;
         sh.id[slot] = id;
       }
@@ -227,7 +233,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkArgs p) {
   }
 
   // order the count <= k survivors: bitonic sort of P = 2^ceil(log2 k) words, best first; padding (key 0, id ~0: word 0)
-  // sorts last
+  // sorts last (a candidate's id is below 2^31, so its word is never 0)
   int P = 1;
   while (P < k) P <<= 1;
   for (int i = tid; i < P; i += TK_THREADS) {
