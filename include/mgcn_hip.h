@@ -602,6 +602,56 @@ int mgcn_adam_step(int64_t n, const float *const *grad_host, float *const *param
                    float *const *exp_avg_sq_host, const int64_t *numel_host, const float *coef_dev, float step_size,
                    float bc2_sqrt, double beta1, double beta2, double eps, double weight_decay, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (11) The training step's query path between the encoder and the scorer (csrc/query_train.hip): the backward of the two
+ * query-row gathers of MGCN.forward (model.py:35-36, all_ent[src] and all_rel[rel]) and the trunk's tail hidden_drop -> bn2 ->
+ * relu (model.py:173-175) with batch statistics, forward and backward. Plain pointers with leading dimensions (every tensor may
+ * be a column window of a wider one), all checks before the first launch, a refusal writes nothing. No float atomics, no
+ * spinning, no workgroup waits on another: the same inputs give the same bits at every launch.
+ *
+ * mgcn_query_rows_bwd: out [num_rows, dim] (rows ldo floats apart) is written completely, bit for bit as the sequential f32 loop
+ *     out[:] = 0;  for b in 0 .. batch - 1: out[idx[b], :] += d[b, :]
+ *   writes it: the addends of a row are added one after another in ascending b, from 0. Rows that no b names are zero; columns
+ *   dim .. ldo of a window are not touched. An idx[b] outside [0, num_rows) is never followed and adds nothing. Three launches:
+ *   one workgroup sorts the unique 64-bit keys idx[b] << 12 | b in LDS (so the plan is a function of idx alone) and leaves the
+ *   sorted (row, b) pairs in the workspace; a fill zeroes the window; a sum gives each run of equal rows to the workgroup of its
+ *   first sorted position, whose threads (one per column) walk the run. workspace_dev: mgcn_query_rows_bwd_workspace(batch)
+ *   bytes (0 = refused), 16-byte aligned. 1 <= batch <= MGCN_QUERY_MAX_BATCH, dim >= 1, 1 <= num_rows <= 2^50.
+ *
+ * mgcn_conve_tail_fwd, for z [batch, dim] and the optional byte keep-mask keep [batch, dim] (NULL = keep all, inv_keep is 1; the
+ *   convention of (9)), per column:
+ *     u = (z keep) inv_keep;  mean = (sum_b u) / B;  res = (sum_b (u - mean)) / B;  c = (u - mean) - res
+ *     var = (sum_b c^2) / B;  rstd = 1 / sqrt(var + eps);  x = max((c rstd) gamma + beta, 0)
+ *   (res is what the f32 mean leaves of the centred column: rows that nearly coincide cancel in u - mean down to the mean's own
+ *   rounding error, which rstd then multiplies; c sums to zero to the accuracy of the differences themselves.)
+ *   saved_dev [2, dim] (rows ldsv apart) = mean, rstd; the running statistics are updated in place as nn.BatchNorm1d does
+ *   (running = (1 - momentum) running + momentum stat, the variance unbiased: sum / (B - 1)); num_batches_tracked is the caller's.
+ * mgcn_conve_tail_bwd, for gx [batch, dim] and the forward's z, keep, x and saved_dev:
+ *     ga = gx [x > 0];  d beta = sum_b ga;  d gamma = sum_b ga uh, uh = c rstd with c centred as in the forward
+ *     gz = ((gamma rstd ((ga - d beta / B) - uh d gamma / B)) keep) inv_keep
+ *   The relu mask is read from the forward's own output. gz_dev, d_gamma_dev and d_beta_dev may each be NULL, which only
+ *   removes work and leaves the bits of the others unchanged.
+ *   One launch each: a workgroup owns 16 columns over all rows. Every batch sum is a per-thread chain over rows t, t + 16, ...
+ *   in ascending order and a halving tree over the 16 chains, so its order depends on B alone and a column's results do not
+ *   depend on which other columns are in the call. 2 <= batch <= MGCN_QUERY_MAX_BATCH, dim >= 1.
+ * MGCN_EINVAL for a null required pointer, a negative batch, dim < 1, num_rows < 1, a leading dimension below dim, an inv_keep
+ * that is negative or not finite, a momentum outside [0, 1], a negative eps, a misaligned or too small workspace;
+ * MGCN_EUNSUPPORTED, nothing written, for a batch outside the limits (batch = 1 for the tail: one value per channel has no
+ * batch statistics) and for num_rows > 2^50.
+ */
+#define MGCN_QUERY_MAX_BATCH 4096
+size_t mgcn_query_rows_bwd_workspace(int32_t batch);
+int mgcn_query_rows_bwd(int32_t batch, int64_t num_rows, int32_t dim, const int64_t *idx_dev, const float *d_dev, int64_t ldd,
+                        float *out_dev, int64_t ldo, void *workspace_dev, size_t workspace_bytes, void *stream);
+int mgcn_conve_tail_fwd(int32_t batch, int32_t dim, const float *z_dev, int64_t ldz, const uint8_t *keep_dev, int64_t ldk,
+                        float inv_keep, const float *gamma_dev, const float *beta_dev, float *running_mean_dev,
+                        float *running_var_dev, float momentum, float eps, float *x_dev, int64_t ldx, float *saved_dev,
+                        int64_t ldsv, void *stream);
+int mgcn_conve_tail_bwd(int32_t batch, int32_t dim, const float *z_dev, int64_t ldz, const uint8_t *keep_dev, int64_t ldk,
+                        float inv_keep, const float *x_dev, int64_t ldx, const float *saved_dev, int64_t ldsv,
+                        const float *gamma_dev, const float *gx_dev, int64_t ldg, float *gz_dev, int64_t ldgz,
+                        float *d_gamma_dev, float *d_beta_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

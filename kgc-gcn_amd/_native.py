@@ -81,6 +81,12 @@ _SIGNATURES = {
     'mgcn_adam_sq_norms': (ctypes.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_adam_clip_coef': (ctypes.c_int, [_i64, _ptr, _f32, _ptr, _ptr]),
     'mgcn_adam_step': (ctypes.c_int, [_i64] + [_ptr] * 6 + [_f32, _f32] + [ctypes.c_double] * 4 + [_ptr]),
+    'mgcn_query_rows_bwd_workspace': (ctypes.c_size_t, [_i32]),
+    'mgcn_query_rows_bwd': (ctypes.c_int, [_i32, _i64, _i32, _ptr, _ptr, _i64, _ptr, _i64, _ptr, ctypes.c_size_t, _ptr]),
+    'mgcn_conve_tail_fwd': (ctypes.c_int, [_i32, _i32, _ptr, _i64, _ptr, _i64, _f32, _ptr, _ptr, _ptr, _ptr, _f32, _f32, _ptr, _i64, _ptr,
+                                           _i64, _ptr]),
+    'mgcn_conve_tail_bwd': (ctypes.c_int, [_i32, _i32, _ptr, _i64, _ptr, _i64, _f32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64,
+                                           _ptr, _ptr, _ptr]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
     'mgcn_ingest_count': (_i64, [_ptr, _i32]),
@@ -950,6 +956,85 @@ def conve_train_bwd(geom, s, r, conv_w, fc_w, bn0_weight, bn0_bias, bn1_weight, 
                                       ptr('conv_w'), ptr('conv_b'), ptr('g0'), ptr('b0'), ptr('g1'), ptr('b1'), ptr('fc_w'),
                                       fc_w.size(1), ptr('fc_b'), ws.data_ptr(), ws.numel(), _stream(s)), 'mgcn_conve_train_bwd')
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# (11) the training step's query path: the row gathers' backward and the trunk's tail
+QUERY_MAX_BATCH = 4096
+
+
+def query_rows_supported(batch):
+    return 1 <= int(batch) <= QUERY_MAX_BATCH
+
+
+def query_rows_bwd(idx, d, num_rows, out=None):
+    """out [num_rows, dim] with out[idx[b]] += d[b] added in ascending b (bit for bit the sequential f32 loop), rows that no
+    b names zero. idx: int64 [B], d: f32 [B, dim]; `out` may be a column window of a wider tensor (its other columns stay)."""
+    if idx.dim() != 1 or d.dim() != 2 or d.size(0) != idx.numel():
+        raise NativeError('query_rows_bwd: idx must be [B] and d [B, dim], got %s and %s' % (tuple(idx.shape), tuple(d.shape)))
+    B, dim = int(d.size(0)), int(d.size(1))
+    if out is None:
+        out = torch.empty((int(num_rows), dim), dtype=torch.float32, device=d.device)
+    elif out.dim() != 2 or tuple(out.shape) != (int(num_rows), dim):
+        raise NativeError('query_rows_bwd: out must be [%d, %d]' % (num_rows, dim))
+    _same_device(idx, d, out)
+    dp, ldd = _rows(d, dim, 'd')
+    op, ldo = _rows(out, dim, 'out')
+    nbytes = lib().mgcn_query_rows_bwd_workspace(B)
+    if nbytes == 0:
+        raise NativeError('query_rows_bwd: a batch of %d is not supported' % B)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=d.device)
+    _check(lib().mgcn_query_rows_bwd(B, int(num_rows), dim, _dev(idx.contiguous(), torch.int64, 'idx'), dp, ldd, op, ldo, ws.data_ptr(),
+                                     nbytes, _stream(d)), 'mgcn_query_rows_bwd')
+    return out
+
+
+def conve_tail_supported(batch, dim):
+    """Shapes mgcn_conve_tail_fwd takes: batch statistics need 2 <= B (<= 4096)."""
+    return 2 <= int(batch) <= QUERY_MAX_BATCH and int(dim) >= 1
+
+
+def _keep_rows(keep, B, O):
+    if keep is None:
+        return None, O
+    if keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (B, O) or (O > 1 and keep.stride(1) != 1):
+        raise NativeError('conve tail: keep must be bool / uint8 [%d, %d] with a contiguous last dimension' % (B, O))
+    return keep.data_ptr(), max(keep.stride(0), O)
+
+
+def conve_tail_fwd(z, keep, inv_keep, gamma, beta, running_mean, running_var, momentum, eps):
+    """x = relu(bn2_batch(z keep inv_keep)) [B, O] and saved [2, O] (mean, rstd); the running statistics are updated in
+    place. keep: bool / uint8 [B, O] or None (keep all)."""
+    B, O = int(z.size(0)), int(z.size(1))
+    _same_device(z, keep, gamma, beta, running_mean, running_var)
+    zp, ldz = _rows(z, O, 'z')
+    kp, ldk = _keep_rows(keep, B, O)
+    x = torch.empty((B, O), dtype=torch.float32, device=z.device)
+    saved = torch.empty((2, O), dtype=torch.float32, device=z.device)
+    _check(lib().mgcn_conve_tail_fwd(B, O, zp, ldz, kp, ldk, float(inv_keep), _dev(gamma, torch.float32, 'bn weight'),
+                                     _dev(beta, torch.float32, 'bn bias'), _dev(running_mean, torch.float32, 'running mean'),
+                                     _dev(running_var, torch.float32, 'running var'), float(momentum), float(eps), x.data_ptr(), O,
+                                     saved.data_ptr(), O, _stream(z)), 'mgcn_conve_tail_fwd')
+    return x, saved
+
+
+def conve_tail_bwd(z, keep, inv_keep, x, saved, gamma, gx, want=('z', 'gamma', 'beta')):
+    """(gz [B, O], d gamma [O], d beta [O]) of the forward's (z, keep, x, saved) for gx; None for what `want` leaves out."""
+    B, O = int(z.size(0)), int(z.size(1))
+    _same_device(z, keep, x, saved, gamma, gx)
+    zp, ldz = _rows(z, O, 'z')
+    kp, ldk = _keep_rows(keep, B, O)
+    xp, ldx = _rows(x, O, 'x')
+    gp, ldg = _rows(gx, O, 'gx')
+    if tuple(saved.shape) != (2, O) or not saved.is_contiguous():
+        raise NativeError('conve_tail_bwd: saved must be contiguous [2, %d]' % O)
+    new = lambda name, shape: torch.empty(shape, dtype=torch.float32, device=z.device) if name in want else None
+    gz, dg, db = new('z', (B, O)), new('gamma', (O,)), new('beta', (O,))
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _check(lib().mgcn_conve_tail_bwd(B, O, zp, ldz, kp, ldk, float(inv_keep), xp, ldx, _dev(saved, torch.float32, 'saved'), O,
+                                     _dev(gamma, torch.float32, 'bn weight'), gp, ldg, ptr(gz), O, ptr(dg), ptr(db), _stream(z)),
+           'mgcn_conve_tail_bwd')
+    return gz, dg, db
 
 
 def filter_mask(qkey, keys, ptr, tails, n_local, ent_row0=0, out=None):

@@ -1,0 +1,299 @@
+// The training step's query path between the encoder and the scorer (gfx950), paragraph (11) of include/mgcn_hip.h:
+//   (a) the backward of the two query-row gathers all_ent[src], all_rel[rel]: out[idx[b], :] += d[b, :] with the addends of a row
+//       added one after another in ascending b, bit for bit the sequential f32 loop -- a one-workgroup plan launch sorts the unique
+//       keys idx << 12 | b in LDS, a fill launch zeroes the window, a sum launch gives every run of equal rows to the workgroup
+//       of its first position, which walks the run with threads over columns;
+//   (b) the trunk's tail hidden_drop -> bn2 -> relu on [B, O] with batch statistics, forward and backward, one launch each: a
+//       workgroup owns 16 columns over all rows, so nothing crosses workgroups.
+// No float atomics, no spinning, no workgroup waits on another: every sum has a fixed order, so the same inputs give the same bits.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "mgcn_common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int MAX_BATCH = MGCN_QUERY_MAX_BATCH;
+constexpr int KEY_BITS = 12;                          // b < 4096 in the low bits of a sort key
+constexpr uint64_t BAD_KEY = 1ull << 63;              // an index outside [0, num_rows): sorted behind every row, never followed
+constexpr int64_t MAX_ROWS = int64_t(1) << 50;
+constexpr int SORT_TPB = 1024;
+constexpr int TPB = 256;
+static_assert(MAX_BATCH == 1 << KEY_BITS, "b must fit the low bits of a key");
+
+// ------------------------------------------------------------------------------------------------ (a) row gradients
+// plan: row_sorted[pos], b_sorted[pos] of the keys idx[b] << 12 | b in ascending order (a bitonic network over `padded`, the
+// next power of two, filled up with all-ones keys). The keys are unique, so the plan is a function of idx alone.
+__global__ __launch_bounds__(SORT_TPB) void rows_plan_kernel(int batch, int padded, int64_t num_rows, const int64_t *__restrict__ idx,
+                                                             int64_t *__restrict__ row_sorted, int32_t *__restrict__ b_sorted) {
+  __shared__ uint64_t key[MAX_BATCH];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < padded; i += SORT_TPB) {
+    uint64_t k = ~0ull;
+    if (i < batch) {
+      const int64_t n = idx[i];
+      k = (n >= 0 && n < num_rows) ? ((uint64_t(n) << KEY_BITS) | uint64_t(i)) : (BAD_KEY | uint64_t(i));
+    }
+    key[i] = k;
+  }
+  __syncthreads();
+  for (int k = 2; k <= padded; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < padded; i += SORT_TPB) {
+        const int l = i ^ j;
+        if (l > i) {                                  // every pair belongs to one thread
+          const uint64_t a = key[i], b = key[l];
+          const bool up = (i & k) == 0;
+          if ((a > b) == up) {
+            key[i] = b;
+            key[l] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  for (int i = tid; i < batch; i += SORT_TPB) {
+    const uint64_t k = key[i];
+    row_sorted[i] = (k & BAD_KEY) ? int64_t(-1) : int64_t(k >> KEY_BITS);
+    b_sorted[i] = int32_t(k & uint64_t(MAX_BATCH - 1));
+  }
+}
+
+// zero fill of a window whose rows are ldo > dim apart: one wave per row, lanes over columns; the guard columns are not touched
+__global__ __launch_bounds__(TPB) void rows_fill_window_kernel(int64_t num_rows, int dim, float *__restrict__ out, int64_t ldo) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t r = int64_t(blockIdx.x) * (TPB / 64) + wave; r < num_rows; r += int64_t(gridDim.x) * (TPB / 64))
+    for (int c = lane; c < dim; c += 64) out[r * ldo + c] = 0.f;
+}
+
+// zero fill of n contiguous floats: scalars up to the first 16-byte boundary and for the last n % 4, float4 stores between
+__global__ __launch_bounds__(TPB) void rows_fill_flat_kernel(int64_t n, float *__restrict__ out) {
+  const int64_t head0 = int64_t((16u - (reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) >> 2;
+  const int64_t head = head0 < n ? head0 : n;
+  const int64_t nv = (n - head) >> 2;
+  const int64_t t = int64_t(blockIdx.x) * TPB + threadIdx.x, step = int64_t(gridDim.x) * TPB;
+  f32x4 *__restrict__ v = reinterpret_cast<f32x4 *>(out + head);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  for (int64_t i = t; i < nv; i += step) v[i] = zero;
+  if (t < head) out[t] = 0.f;
+  const int64_t tail = head + (nv << 2) + t;
+  if (tail < n) out[tail] = 0.f;
+}
+
+// sum: workgroup `pos` owns the run of equal rows that starts at sorted position pos (any other position exits); thread t adds
+// d[b, c] for the run's b in ascending order, columns c = t, t + 256, ..., starting from 0 as the sequential loop does
+__global__ __launch_bounds__(TPB) void rows_sum_kernel(int batch, int dim, const int64_t *__restrict__ row_sorted,
+                                                       const int32_t *__restrict__ b_sorted, const float *__restrict__ d, int64_t ldd,
+                                                       float *__restrict__ out, int64_t ldo) {
+  const int pos = blockIdx.x;
+  const int64_t row = row_sorted[pos];
+  if (row < 0 || (pos > 0 && row_sorted[pos - 1] == row)) return;
+  int end = pos + 1;
+  while (end < batch && row_sorted[end] == row) ++end;
+  for (int c = threadIdx.x; c < dim; c += TPB) {
+    float acc = 0.f;
+    for (int k = pos; k < end; ++k) acc += d[int64_t(b_sorted[k]) * ldd + c];
+    out[row * ldo + c] = acc;
+  }
+}
+
+inline size_t rows_workspace(int64_t batch) { return (size_t(batch) * (sizeof(int64_t) + sizeof(int32_t)) + 15u) & ~size_t(15); }
+
+// ------------------------------------------------------------------------------------------------ (b) trunk tail
+constexpr int CW = 16;                                // columns of a workgroup
+constexpr int RL = TPB / CW;                          // row lanes: thread (ty, tx) walks rows ty, ty + RL, ... of column tx
+
+// u = z keep inv_keep in the order of model._drawn_dropout: (x * mask) * (1 / keep)
+__device__ __forceinline__ float dropped(float z, const uint8_t *__restrict__ keep, int64_t at, float inv_keep) {
+  return keep ? (z * (keep[at] ? 1.f : 0.f)) * inv_keep : z;
+}
+
+// the sum of the RL row lanes of every column: a halving tree of fixed shape, the result handed to all lanes of the column
+__device__ __forceinline__ float column_sum(float v, float *red, int ty, int tx) {
+  red[ty * CW + tx] = v;
+  __syncthreads();
+  for (int w = RL / 2; w > 0; w >>= 1) {
+    if (ty < w) red[ty * CW + tx] += red[(ty + w) * CW + tx];
+    __syncthreads();
+  }
+  const float s = red[tx];
+  __syncthreads();
+  return s;
+}
+
+struct TailArgs {
+  int batch, dim;
+  const float *z;
+  int64_t ldz;
+  const uint8_t *keep;
+  int64_t ldk;
+  float inv_keep;
+};
+
+// res = (sum_b (u - mean)) / B: what the f32 mean leaves of the centred column. Rows that nearly coincide (two-row batches
+// above all) cancel in u - mean down to the mean's own rounding error, which rstd then multiplies; (u - mean) - res sums to
+// zero to the accuracy of the differences themselves. Forward and backward centre with the same expression.
+__device__ __forceinline__ float centring_residual(const TailArgs &a, float mean, bool live, int c, float *red, int ty, int tx) {
+  float s = 0.f;
+  if (live)
+    for (int b = ty; b < a.batch; b += RL) s += dropped(a.z[b * a.ldz + c], a.keep, b * a.ldk + c, a.inv_keep) - mean;
+  return column_sum(s, red, ty, tx) / float(a.batch);
+}
+
+__global__ __launch_bounds__(TPB) void tail_fwd_kernel(TailArgs a, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                       float *__restrict__ running_mean, float *__restrict__ running_var,
+                                                       float momentum, float eps, float *__restrict__ x, int64_t ldx,
+                                                       float *__restrict__ saved, int64_t ldsv) {
+  __shared__ float red[TPB];
+  const int tx = threadIdx.x % CW, ty = threadIdx.x / CW;
+  const int c = blockIdx.x * CW + tx;
+  const bool live = c < a.dim;
+  const float count = float(a.batch);
+  float s = 0.f;
+  if (live)
+    for (int b = ty; b < a.batch; b += RL) s += dropped(a.z[b * a.ldz + c], a.keep, b * a.ldk + c, a.inv_keep);
+  const float mean = column_sum(s, red, ty, tx) / count;
+  const float res = centring_residual(a, mean, live, c, red, ty, tx);
+  float q = 0.f;
+  if (live)
+    for (int b = ty; b < a.batch; b += RL) {
+      const float dl = (dropped(a.z[b * a.ldz + c], a.keep, b * a.ldk + c, a.inv_keep) - mean) - res;
+      q += dl * dl;
+    }
+  const float sq = column_sum(q, red, ty, tx);
+  if (!live) return;
+  const float var = sq / count;
+  const float rstd = 1.0f / sqrtf(var + eps);
+  const float g = gamma[c], be = beta[c];
+  for (int b = ty; b < a.batch; b += RL) {
+    const float u = dropped(a.z[b * a.ldz + c], a.keep, b * a.ldk + c, a.inv_keep);
+    const float v = (((u - mean) - res) * rstd) * g + be;
+    x[b * ldx + c] = v <= 0.f ? 0.f : v;              // (a NaN stays a NaN)
+  }
+  if (ty == 0) {
+    saved[c] = mean;
+    saved[ldsv + c] = rstd;
+    running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mean;
+    running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (sq / (count - 1.0f));
+  }
+}
+
+__global__ __launch_bounds__(TPB) void tail_bwd_kernel(TailArgs a, const float *__restrict__ x, int64_t ldx,
+                                                       const float *__restrict__ saved, int64_t ldsv, const float *__restrict__ gamma,
+                                                       const float *__restrict__ gx, int64_t ldg, float *__restrict__ gz, int64_t ldgz,
+                                                       float *__restrict__ d_gamma, float *__restrict__ d_beta) {
+  __shared__ float red[TPB];
+  const int tx = threadIdx.x % CW, ty = threadIdx.x / CW;
+  const int c = blockIdx.x * CW + tx;
+  const bool live = c < a.dim;
+  const float mean = live ? saved[c] : 0.f, rstd = live ? saved[ldsv + c] : 0.f;
+  const float res = centring_residual(a, mean, live, c, red, ty, tx);
+  float sb = 0.f, sg = 0.f;
+  if (live)
+    for (int b = ty; b < a.batch; b += RL) {
+      const float ga = x[b * ldx + c] > 0.f ? gx[b * ldg + c] : 0.f;      // the forward's relu mask, from its own output
+      const float uh = ((dropped(a.z[b * a.ldz + c], a.keep, b * a.ldk + c, a.inv_keep) - mean) - res) * rstd;
+      sb += ga;
+      sg += ga * uh;
+    }
+  const float db = column_sum(sb, red, ty, tx);
+  const float dg = column_sum(sg, red, ty, tx);
+  if (!live) return;
+  if (ty == 0) {
+    if (d_beta) d_beta[c] = db;
+    if (d_gamma) d_gamma[c] = dg;
+  }
+  if (!gz) return;
+  const float count = float(a.batch);
+  const float k = gamma[c] * rstd, mb = db / count, mg = dg / count;
+  for (int b = ty; b < a.batch; b += RL) {
+    const float ga = x[b * ldx + c] > 0.f ? gx[b * ldg + c] : 0.f;
+    const float uh = ((dropped(a.z[b * a.ldz + c], a.keep, b * a.ldk + c, a.inv_keep) - mean) - res) * rstd;
+    const float gu = k * ((ga - mb) - uh * mg);
+    gz[b * ldgz + c] = a.keep ? (gu * (a.keep[b * a.ldk + c] ? 1.f : 0.f)) * a.inv_keep : gu;
+  }
+}
+
+// what both tail entry points check of the arguments they share; MGCN_OK, or the code with the message set
+int check_tail(const char *what, int32_t batch, int32_t dim, const float *z, int64_t ldz, const uint8_t *keep, int64_t ldk,
+               float inv_keep) {
+  MGCN_REQUIRE(batch >= 0 && dim >= 1, "%s: bad sizes (batch = %d, dim = %d)", what, batch, dim);
+  MGCN_REQUIRE(z, "%s: null pointer (z)", what);
+  MGCN_REQUIRE(ldz >= dim && (!keep || ldk >= dim), "%s: leading dimension smaller than dim = %d", what, dim);
+  MGCN_REQUIRE(std::isfinite(inv_keep) && inv_keep >= 0.f, "%s: inv_keep must be a finite number >= 0", what);
+  if (batch < 2 || batch > MAX_BATCH)
+    return mgcn::fail(MGCN_EUNSUPPORTED, "%s: batch = %d outside [2, %d] (batch statistics need more than one value per channel)", what,
+                      batch, MAX_BATCH);
+  return MGCN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t mgcn_query_rows_bwd_workspace(int32_t batch) {
+  return (batch >= 1 && batch <= MAX_BATCH) ? rows_workspace(batch) : 0;
+}
+
+extern "C" int mgcn_query_rows_bwd(int32_t batch, int64_t num_rows, int32_t dim, const int64_t *idx_dev, const float *d_dev, int64_t ldd,
+                                   float *out_dev, int64_t ldo, void *workspace_dev, size_t workspace_bytes, void *stream) {
+  MGCN_REQUIRE(batch >= 0 && num_rows >= 1 && dim >= 1, "mgcn_query_rows_bwd: bad sizes (batch = %d, num_rows = %lld, dim = %d)", batch,
+               (long long)num_rows, dim);
+  MGCN_REQUIRE(idx_dev && d_dev && out_dev, "mgcn_query_rows_bwd: null pointer");
+  MGCN_REQUIRE(ldd >= dim && ldo >= dim, "mgcn_query_rows_bwd: leading dimension smaller than dim = %d", dim);
+  if (batch < 1 || batch > MAX_BATCH)
+    return mgcn::fail(MGCN_EUNSUPPORTED, "mgcn_query_rows_bwd: batch = %d outside [1, %d]", batch, MAX_BATCH);
+  if (num_rows > MAX_ROWS) return mgcn::fail(MGCN_EUNSUPPORTED, "mgcn_query_rows_bwd: more than 2^50 rows");
+  MGCN_REQUIRE(workspace_dev && mgcn::aligned16(workspace_dev), "mgcn_query_rows_bwd: null pointer or misaligned workspace");
+  MGCN_REQUIRE(workspace_bytes >= rows_workspace(batch), "mgcn_query_rows_bwd: workspace too small (%zu < %zu bytes)", workspace_bytes,
+               rows_workspace(batch));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int64_t *row_sorted = static_cast<int64_t *>(workspace_dev);
+  int32_t *b_sorted = reinterpret_cast<int32_t *>(row_sorted + batch);
+  int padded = 2;
+  while (padded < batch) padded <<= 1;
+  rows_plan_kernel<<<dim3(1), dim3(SORT_TPB), 0, s>>>(batch, padded, num_rows, idx_dev, row_sorted, b_sorted);
+  MGCN_CHECK_LAUNCH("mgcn_query_rows_bwd (plan)");
+  if (ldo == dim) {
+    const int64_t n = num_rows * dim, groups = (n / 4 + TPB - 1) / TPB + 1;
+    rows_fill_flat_kernel<<<dim3(unsigned(groups < 8192 ? groups : 8192)), dim3(TPB), 0, s>>>(n, out_dev);
+  } else {
+    const int64_t groups = (num_rows + TPB / 64 - 1) / (TPB / 64);
+    rows_fill_window_kernel<<<dim3(unsigned(groups < 16384 ? groups : 16384)), dim3(TPB), 0, s>>>(num_rows, dim, out_dev, ldo);
+  }
+  MGCN_CHECK_LAUNCH("mgcn_query_rows_bwd (fill)");
+  rows_sum_kernel<<<dim3(batch), dim3(TPB), 0, s>>>(batch, dim, row_sorted, b_sorted, d_dev, ldd, out_dev, ldo);
+  MGCN_CHECK_LAUNCH("mgcn_query_rows_bwd (sum)");
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_conve_tail_fwd(int32_t batch, int32_t dim, const float *z_dev, int64_t ldz, const uint8_t *keep_dev, int64_t ldk,
+                                   float inv_keep, const float *gamma_dev, const float *beta_dev, float *running_mean_dev,
+                                   float *running_var_dev, float momentum, float eps, float *x_dev, int64_t ldx, float *saved_dev,
+                                   int64_t ldsv, void *stream) {
+  if (int rc = check_tail("mgcn_conve_tail_fwd", batch, dim, z_dev, ldz, keep_dev, ldk, inv_keep)) return rc;
+  MGCN_REQUIRE(gamma_dev && beta_dev && running_mean_dev && running_var_dev && x_dev && saved_dev, "mgcn_conve_tail_fwd: null pointer");
+  MGCN_REQUIRE(ldx >= dim && ldsv >= dim, "mgcn_conve_tail_fwd: leading dimension smaller than dim = %d", dim);
+  MGCN_REQUIRE(momentum >= 0.f && momentum <= 1.f && eps >= 0.f, "mgcn_conve_tail_fwd: momentum must lie in [0, 1] and eps be >= 0");
+  const TailArgs a = {batch, dim, z_dev, ldz, keep_dev, ldk, inv_keep};
+  tail_fwd_kernel<<<dim3((dim + CW - 1) / CW), dim3(TPB), 0, static_cast<hipStream_t>(stream)>>>(
+      a, gamma_dev, beta_dev, running_mean_dev, running_var_dev, momentum, eps, x_dev, ldx, saved_dev, ldsv);
+  MGCN_CHECK_LAUNCH("mgcn_conve_tail_fwd");
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_conve_tail_bwd(int32_t batch, int32_t dim, const float *z_dev, int64_t ldz, const uint8_t *keep_dev, int64_t ldk,
+                                   float inv_keep, const float *x_dev, int64_t ldx, const float *saved_dev, int64_t ldsv,
+                                   const float *gamma_dev, const float *gx_dev, int64_t ldg, float *gz_dev, int64_t ldgz,
+                                   float *d_gamma_dev, float *d_beta_dev, void *stream) {
+  if (int rc = check_tail("mgcn_conve_tail_bwd", batch, dim, z_dev, ldz, keep_dev, ldk, inv_keep)) return rc;
+  MGCN_REQUIRE(x_dev && saved_dev && gamma_dev && gx_dev, "mgcn_conve_tail_bwd: null pointer");
+  MGCN_REQUIRE(ldx >= dim && ldsv >= dim && ldg >= dim && (!gz_dev || ldgz >= dim),
+               "mgcn_conve_tail_bwd: leading dimension smaller than dim = %d", dim);
+  if (!gz_dev && !d_gamma_dev && !d_beta_dev) return MGCN_OK;
+  const TailArgs a = {batch, dim, z_dev, ldz, keep_dev, ldk, inv_keep};
+  tail_bwd_kernel<<<dim3((dim + CW - 1) / CW), dim3(TPB), 0, static_cast<hipStream_t>(stream)>>>(
+      a, x_dev, ldx, saved_dev, ldsv, gamma_dev, gx_dev, ldg, gz_dev, ldgz, d_gamma_dev, d_beta_dev);
+  MGCN_CHECK_LAUNCH("mgcn_conve_tail_bwd");
+  return MGCN_OK;
+}

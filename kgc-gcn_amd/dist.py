@@ -622,8 +622,7 @@ def _trunk(conv2, src_emb, rel_emb, generator):
     stack = torch.cat([src_emb.view(-1, 1, o), rel_emb.view(-1, 1, o)], dim=1)
     stack = stack.transpose(2, 1).reshape(-1, 1, 2 * p.k_w, p.k_h)
     x = _dropout(F.relu(conv2.bn1(conv2.conv_e(conv2.bn0(stack)))), conv2.feature_drop.p, generator)
-    x = _dropout(conv2.fc(x.view(-1, conv2.flat_sz)), conv2.hidden_drop.p, generator)
-    return F.relu(conv2.bn2(x)).contiguous()
+    return conv2._tail(conv2.fc(x.view(-1, conv2.flat_sz)), generator, True)      # (the HIP tail with MGCN_QUERY_TRAIN=hip)
 
 
 def _agreed_seed(group, device):
@@ -802,7 +801,8 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
     if W > 1 and generator is None and (model.conv2.feature_drop.p > 0 or model.conv2.hidden_drop.p > 0):
         generator = torch.Generator(device=ent.device)
         generator.manual_seed(_agreed_seed(group, ent.device))
-    xt = _trunk(model.conv2, torch.index_select(x, 0, src), torch.index_select(rel_e, 0, rel), generator)
+    from .model import query_rows
+    xt = _trunk(model.conv2, query_rows(model, x, src), query_rows(model, rel_e, rel), generator)
     if W > 1:
         xt = _AllReduceGradFn.apply(xt, ex)
     bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]

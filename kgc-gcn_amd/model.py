@@ -13,7 +13,9 @@ What runs where
   * the ConvE conv trunk (model.py:161-175): stock torch modules (MIOpen / rocBLAS) by default; with
     params.conve_trunk = 'hip' (or MGCN_TRUNK=hip) the eval-mode trunk is ONE HIP launch from the two tables to x (csrc/conve_trunk.hip);
     with params.conve_trunk_train = 'hip' (or MGCN_TRUNK_TRAIN=hip) the training-mode trunk up to fc, forward and backward, runs on
-    csrc/conve_train.hip (hidden_drop, bn2 and the last relu stay torch modules).
+    csrc/conve_train.hip; with params.query_path_train = 'hip' (or MGCN_QUERY_TRAIN=hip) the rest of the training step's query path
+    runs on csrc/query_train.hip: the trunk's tail hidden_drop -> bn2 -> relu, forward and backward, and the backward of the two
+    query-row gathers all_ent[src], all_rel[rel] (a fixed-order sum in place of index_add_'s float atomics).
 There is no CPU path: tensors that are not on a GPU make the native layer raise.
 """
 import os
@@ -129,6 +131,62 @@ class _TrunkTrainFn(torch.autograd.Function):
         gz = gz if gz.stride(-1) == 1 else gz.contiguous()
         g = _native.conve_train_bwd(ctx.geom, s, r, conv_w, fc_w, g0, b0, g1, b1, keep, ctx.inv_keep, saved, ws, gz, want)
         return tuple(g.get(n) for n in names) + (None,) * 5
+
+
+class _QueryRowsFn(torch.autograd.Function):
+    """table[idx] (model.py:35-36). The forward stays torch.index_select (a copy); the backward is the fixed-order row sum of
+    csrc/query_train.hip, bit for bit the sequential loop d table[idx[b]] += g[b] in ascending b, instead of index_add_'s float
+    atomics."""
+
+    @staticmethod
+    def forward(ctx, table, idx):
+        ctx.save_for_backward(idx)
+        ctx.num_rows = table.size(0)
+        return torch.index_select(table, 0, idx)
+
+    @staticmethod
+    def backward(ctx, g):
+        (idx,) = ctx.saved_tensors
+        g = g if (g.stride(1) == 1 and g.stride(0) >= g.size(1)) else g.contiguous()
+        return _native.query_rows_bwd(idx, g, ctx.num_rows), None
+
+
+class _TrunkTailFn(torch.autograd.Function):
+    """The trunk's tail x = relu(bn2(z keep inv_keep)) with batch statistics (model.py:173-175 under .train()) on the kernels of
+    csrc/query_train.hip, one launch forward and one backward. Saves z, the bool keep-mask, the batch statistics and the output
+    (the backward reads the relu mask from it); bn2's running statistics are updated in place."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, running_mean, running_var, momentum, eps, keep, inv_keep):
+        x, saved = _native.conve_tail_fwd(z, keep, inv_keep, gamma, beta, running_mean, running_var, momentum, eps)
+        ctx.save_for_backward(z, gamma, keep, saved, x)
+        ctx.inv_keep = inv_keep
+        return x
+
+    @staticmethod
+    def backward(ctx, gx):
+        z, gamma, keep, saved, x = ctx.saved_tensors
+        gx = gx if (gx.stride(1) == 1 and gx.stride(0) >= gx.size(1)) else gx.contiguous()
+        want = {n for i, n in enumerate(('z', 'gamma', 'beta')) if ctx.needs_input_grad[i]}
+        return _native.conve_tail_bwd(z, keep, ctx.inv_keep, x, saved, gamma, gx, want) + (None,) * 6
+
+
+def _query_train_wanted(params):
+    """The switch of the HIP query path: params.query_path_train == 'hip', overridden in both directions by the environment
+    variable MGCN_QUERY_TRAIN."""
+    return (os.environ.get('MGCN_QUERY_TRAIN') or getattr(params, 'query_path_train', 'torch')) == 'hip'
+
+
+def query_rows(model, table, idx):
+    """table[idx], the query-row gather of MGCN.forward, MGCN.forward_loss and dist.train_step_sharded. With the switch on
+    (_query_train_wanted), in training mode with autograd on, for an f32 GPU table that takes a gradient and int64 1-D indices of
+    a batch the kernel takes, the backward is the fixed-order sum of _QueryRowsFn; anything else is torch.index_select."""
+    if model.training and torch.is_grad_enabled() and table.requires_grad and _query_train_wanted(model.params) \
+            and table.is_cuda and table.dtype == torch.float32 and table.dim() == 2 and table.size(0) >= 1 and table.size(1) >= 1 \
+            and idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 1 and _native.query_rows_supported(idx.numel()):
+        model._query_rows_count = getattr(model, '_query_rows_count', 0) + 1
+        return _QueryRowsFn.apply(table, idx)
+    return torch.index_select(table, 0, idx)
 
 
 def _drawn_dropout(x, p, generator):
@@ -410,13 +468,51 @@ class ConvE(nn.Module):
             bn0.num_batches_tracked += 1
             bn1.num_batches_tracked += 1
         self._trunk_train_count = getattr(self, '_trunk_train_count', 0) + 1
-        return F.relu(self.bn2(_drawn_dropout(z, self.hidden_drop.p, generator))).contiguous()
+        return self._tail(z, generator, True)
+
+    def _hip_tail(self, z):
+        """Whether this call takes the HIP tail: the switch (params.query_path_train == 'hip', overridden in both directions by
+        the environment variable MGCN_QUERY_TRAIN), training mode with autograd on, f32 z [B, O] on the GPU, bn2 affine and
+        tracking running statistics with a numeric momentum, a batch the kernels take (B = 1 keeps torch's own error)."""
+        if not self.training or not torch.is_grad_enabled() or not _query_train_wanted(self.params):
+            return False
+        bn = self.bn2
+        ts = [z, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        if any(t is None or not t.is_cuda or t.dtype != torch.float32 for t in ts):
+            return False
+        if not isinstance(bn.momentum, float) or not bn.track_running_stats or z.dim() != 2 or z.size(1) != bn.num_features:
+            return False
+        return _native.conve_tail_supported(z.size(0), z.size(1))
+
+    def _tail(self, z, generator, drawn):
+        """relu(bn2(hidden_drop(z))), the trunk after fc whichever conv block ran. `drawn`: the torch path draws its mask with
+        bernoulli_ from `generator` (_drawn_dropout) instead of calling hidden_drop. On the HIP tail the mask is always drawn with
+        bernoulli_(1 - p, generator=generator) on an f32 [B, O] tensor, after the feature mask: dist._trunk's draws."""
+        if self._hip_tail(z):
+            z = z if z.stride(1) == 1 else z.contiguous()
+            p, keep, inv_keep = self.hidden_drop.p, None, 1.0
+            if p >= 1:
+                keep, inv_keep = torch.zeros(z.shape, dtype=torch.bool, device=z.device), 0.0
+            elif p > 0:
+                keep = torch.empty(z.shape, dtype=torch.float32, device=z.device).bernoulli_(1.0 - p, generator=generator).bool()
+                inv_keep = 1.0 / (1.0 - p)
+            bn = self.bn2
+            x = _TrunkTailFn.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, keep, inv_keep)
+            with torch.no_grad():
+                bn.num_batches_tracked += 1
+            self._tail_train_count = getattr(self, '_tail_train_count', 0) + 1
+            return x
+        x = _drawn_dropout(z, self.hidden_drop.p, generator) if drawn else self.hidden_drop(z)
+        return F.relu(self.bn2(x)).contiguous()
 
     def trunk(self, src_emb, rel_emb, generator=None):
         """x [B, O] of the queries. In training mode with params.conve_trunk_train == 'hip' (or MGCN_TRUNK_TRAIN=hip) the block
         up to fc runs on csrc/conve_train.hip, forward and backward; its two dropout masks are then drawn with bernoulli_
         from `generator` (None: the default generator), feature mask first -- the same masks dist._trunk's torch path draws
-        from the same generator state, but not the stream F.dropout itself would consume. `generator` is not used otherwise."""
+        from the same generator state, but not the stream F.dropout itself would consume. With params.query_path_train == 'hip'
+        (or MGCN_QUERY_TRAIN=hip) the tail hidden_drop -> bn2 -> relu runs on csrc/query_train.hip after either conv block, and its
+        hidden mask is drawn the same way, bernoulli_ on a [B, O] tensor from `generator`: after the torch conv block (whose
+        feature_drop is still F.dropout) that is again not the stream F.dropout would consume. `generator` is not used otherwise."""
         if self._hip_trunk_train(src_emb, rel_emb):
             return self._trunk_train(src_emb, rel_emb, generator)
         if self._hip_trunk(src_emb, rel_emb) and src_emb.dim() == 2 and src_emb.shape == rel_emb.shape \
@@ -428,8 +524,7 @@ class ConvE(nn.Module):
         stack = torch.cat([src_emb.view(-1, 1, o), rel_emb.view(-1, 1, o)], dim=1)
         stack = stack.transpose(2, 1).reshape(-1, 1, 2 * self.params.k_w, self.params.k_h)
         x = self.feature_drop(F.relu(self.bn1(self.conv_e(self.bn0(stack)))))
-        x = self.hidden_drop(self.fc(x.view(-1, self.flat_sz)))
-        return F.relu(self.bn2(x)).contiguous()
+        return self._tail(self.fc(x.view(-1, self.flat_sz)), generator, False)
 
     def trunk_indexed(self, all_ent, src, all_rel, rel):
         """trunk(all_ent[src], all_rel[rel]); on the HIP trunk the rows are gathered inside the kernel."""
@@ -700,7 +795,7 @@ class MGCN(nn.Module):
     # -- reference surface -----------------------------------------------------------------------
     def forward(self, src, rel, data):
         all_ent, all_rel = self.encode(data)
-        src_emb, rel_emb = torch.index_select(all_ent, 0, src), torch.index_select(all_rel, 0, rel)
+        src_emb, rel_emb = query_rows(self, all_ent, src), query_rows(self, all_rel, rel)
         return self.conv2(src_emb, rel_emb, all_ent)
 
     def loss(self, pred, label):
@@ -712,7 +807,7 @@ class MGCN(nn.Module):
         elsewhere, smoothed as data_loader.py:41-43. Falls back to the two-step form for batch sizes the fused launch
         does not take (B % 4 != 0)."""
         all_ent, all_rel = self.encode(data)
-        x = self.conv2.trunk(torch.index_select(all_ent, 0, src), torch.index_select(all_rel, 0, rel))
+        x = self.conv2.trunk(query_rows(self, all_ent, src), query_rows(self, all_rel, rel))
         n_ent = all_ent.size(0)
         keys = index.query_keys(src, rel)
         ent = all_ent.contiguous()
