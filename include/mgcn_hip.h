@@ -120,6 +120,24 @@ int mgcn_csr_build_host(int64_t num_nodes, int64_t num_edges_half, int64_t num_r
                         int32_t *slot_dst_host, int32_t *mirror_host, int32_t *typeptr_host,
                         int32_t *typeslots_host);
 
+/* (1v) The LIVE VIEW of the slot layout — host side, graph-static, additive (the canonical arrays above stay as they are).
+ * The degrees behind `norm` are counted by SOURCE within a half (Q2), so norm is exactly 0.0f for every slot whose
+ * destination never occurs as a source in the same half (leaf entities): a source has degree >= 1, so a destination's
+ * run is dead as a whole or live as a whole. Such slots add m * 0 to their sum; the view leaves them out, and the
+ * fused forward launched on it (2b, "Live view") never loads their rows.
+ *   rowptr_host [2, N+1], rec_host: the canonical arrays of (1) (only the non-hub slots rowptr covers are read).
+ *   *num_live_host / *num_dead_host: non-hub slots with norm != 0.0f / == 0.0f. With no dead slot nothing else is
+ *     written (the outputs may be NULL): the canonical layout is its own live view, callers build none.
+ *   live_rowptr_host [2, N+1] int32: ABSOLUTE positions into live_rec_host, contiguous runs, in-half then out-half
+ *     (monotone from 0 to *num_live_host; a hub's run is empty as in rowptr_host);
+ *   live_rec_host [max_live >= *num_live_host]: the slots with norm != 0.0f in canonical order, {src, type, norm, row}:
+ *     the fourth word is the slot's canonical (absolute) slot index — the row of the slot-ordered per-edge table, minus
+ *     the shard offset ee_sub of (2b) — where the canonical record carries the reference edge id.
+ * Call with the outputs NULL to size live_rec_host, or pass max_live = the non-hub slot count. */
+int mgcn_csr_live_view_host(int64_t num_nodes, const int32_t *rowptr_host, const mgcn_edge_rec *rec_host,
+                            int32_t *live_rowptr_host, mgcn_edge_rec *live_rec_host, int64_t max_live,
+                            int64_t *num_live_host, int64_t *num_dead_host);
+
 /* ---------------------------------------------------------------------------------------------
  * (2) Aggregation forward. Replaces the gather / message / scatter-add of the three `propagate`
  * calls, model.py:99-101 + 111-118 (+ the identity gathers model.py:29-30), with the weight
@@ -280,7 +298,16 @@ int mgcn_dense_bn_tanh_fwd(int64_t num_nodes, int32_t dim_in, int32_t dim_out, c
  * status_dev (optional, one zero-initialised uint32 in device memory): generation 3 couples its roles through LDS counters
  * with BOUNDED spins; a spin that runs out (a wave parked for ~0.1 s by a debugger, a preemption, or a protocol error)
  * lets its wave go on, the rows of that tile are then garbage, and bit 0 of *status_dev is set: callers check the word at
- * their next synchronisation point (kgc-gcn_amd/_native.py check_fused_status). Generations 2 and 4 have no spins. */
+ * their next synchronisation point (kgc-gcn_amd/_native.py check_fused_status). Generations 2 and 4 have no spins.
+ * Live view. mgcn_layer_fwd_fused_live is the same launch with the main slot walk of generations 2 and 3 on the live view
+ * of (1v): live_rowptr_dev / live_rec_dev take the place of rowptr_dev / rec_dev for the partition, the record chunks and
+ * the runs, and a slot's per-edge row is its record's fourth word - ee_sub_{region}; rec_dev stays the CANONICAL record
+ * array, which the hub pre-pass reads through chunks_dev as before (dead hub slots are still walked there). Same
+ * dispatcher, same generation choice, same row bounds, ranges and shards (the row word is an absolute slot index);
+ * generation 4 forced through `tune` is refused. CONTRACT: for finite inputs the rows are bit-identical to the
+ * canonical launch's (s + m * 0 == s, and a run of dead slots only is +0 either way). A non-finite value in an x row or
+ * per-edge row that ONLY dead slots read no longer reaches the output: the canonical launch (and the reference) give
+ * NaN for that destination, this launch gives the row of the finite terms. */
 /* The kernel a launch of (2b) over num_rows destinations takes with `tune` bits 10-11 = 0: 2 (layer_fused2.hip) or 3
  * (layer_fused3.hip). Informational (profiles, benchmarks name the kernel they measured). */
 int mgcn_fused_kernel_generation(int32_t dim_in, int32_t dim_out, int64_t num_rows, int32_t with_row_bounds);
@@ -295,6 +322,18 @@ int mgcn_layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_
                          const int32_t *chunks_dev, int64_t chunk_begin, int64_t chunk_end, float *partial_dev,
                          const float *rels_weight_dev, float *rel_out_dev, const int32_t *row_bounds_dev,
                          int32_t num_row_bounds, int32_t tune, uint32_t *status_dev, void *stream);
+int mgcn_layer_fwd_fused_live(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out,
+                              int32_t num_rel_rows, const int32_t *live_rowptr_dev, const mgcn_edge_rec *live_rec_dev,
+                              const mgcn_edge_rec *rec_dev, const float *x_dev, int64_t ldx, const float *rel_dev,
+                              const float *loop_rel_dev, const float *ee_dev, int32_t ee_in_slot_order,
+                              const float *loop_edge_dev, const float *wp_dev, const float *bias_dev,
+                              const float *bn_mean_dev, const float *bn_var_dev, const float *bn_gamma_dev,
+                              const float *bn_beta_dev, float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin,
+                              int64_t node_end, int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub,
+                              const int32_t *hubinfo_dev, const int32_t *chunks_dev, int64_t chunk_begin,
+                              int64_t chunk_end, float *partial_dev, const float *rels_weight_dev, float *rel_out_dev,
+                              const int32_t *row_bounds_dev, int32_t num_row_bounds, int32_t tune, uint32_t *status_dev,
+                              void *stream);
 int mgcn_pack_weights(int32_t dim_in, int32_t dim_out, const float *w_dev, float *wp_dev, size_t wp_bytes, void *stream);
 size_t mgcn_packed_weights_bytes(int32_t dim_in, int32_t dim_out);
 int mgcn_pack_weights_gen(int32_t generation, int32_t dim_in, int32_t dim_out, const float *w_dev, float *wp_dev,

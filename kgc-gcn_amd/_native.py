@@ -40,6 +40,11 @@ _SIGNATURES = {
                                             _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i64, _i64, _i64,
                                             _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr,
                                             _ptr]),
+    'mgcn_layer_fwd_fused_live': (ctypes.c_int, [_i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
+                                                 _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i64, _i64, _i64,
+                                                 _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr,
+                                                 _ptr]),
+    'mgcn_csr_live_view_host': (ctypes.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     'mgcn_pack_weights': (ctypes.c_int, [_i32, _i32, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_packed_weights_bytes': (ctypes.c_size_t, [_i32, _i32]),
     'mgcn_pack_weights_gen': (ctypes.c_int, [_i32, _i32, _i32, _ptr, _ptr, ctypes.c_size_t, _ptr]),
@@ -195,6 +200,34 @@ def csr_build_host(num_nodes, num_rel_rows, edge_index, edge_type, with_backward
     out['num_chunks'] = int(nch.value)
     out['chunks'] = out['chunks'][:max(int(nch.value), 1)].contiguous()
     return out
+
+
+def csr_live_view_host(rowptr, rec):
+    """(1v) The live view of a canonical layout (host tensors rowptr [2, N+1] int32, rec [2E, 4] int32): the non-hub slots
+    whose norm is not exactly zero. Returns None when no slot is dead (nothing is built), else a dict of HOST tensors:
+    live_rowptr [2, N+1] int32, live_rec [L, 4] int32 (fourth word: the canonical slot index), num_live, num_dead."""
+    if rowptr.dim() != 2 or rowptr.size(0) != 2 or rowptr.size(1) < 1 or rowptr.dtype != torch.int32 or rowptr.is_cuda or \
+            not rowptr.is_contiguous() or rec.dtype != torch.int32 or rec.is_cuda or not rec.is_contiguous() or \
+            (rec.numel() and (rec.dim() != 2 or rec.size(1) != 4)):
+        raise NativeError('csr_live_view: rowptr must be a contiguous host int32 [2, N+1], rec a contiguous host int32 [2E, 4]')
+    N = rowptr.size(1) - 1
+    if int(rowptr[1, N]) > rec.size(0) or int(rowptr[0, 0]) < 0:
+        raise NativeError('csr_live_view: rowptr points past the records')
+    live, dead = ctypes.c_int64(0), ctypes.c_int64(0)
+    call = lambda lrp, lrec, cap: _check(lib().mgcn_csr_live_view_host(
+        N, rowptr.data_ptr(), rec.data_ptr(), lrp, lrec, cap, ctypes.byref(live), ctypes.byref(dead)), 'mgcn_csr_live_view_host')
+    L = int(rowptr[1, N]) - int(rowptr[0, 0])                     # capacity: every non-hub slot
+    out = dict(live_rowptr=torch.empty((2, N + 1), dtype=torch.int32), live_rec=torch.empty((max(L, 1), 4), dtype=torch.int32))
+    call(out['live_rowptr'].data_ptr(), out['live_rec'].data_ptr(), L)
+    if dead.value == 0:
+        return None
+    out['live_rec'] = out['live_rec'][:max(int(live.value), 1)].contiguous()   # (never empty: the launch wants a valid pointer)
+    out['num_live'], out['num_dead'] = int(live.value), int(dead.value)
+    return out
+
+
+# MGCN_LIVE_SLOTS=0: fused launches walk the canonical layout even where the graph has a live view (A/B runs). Read once at import.
+LIVE_SLOTS = os.environ.get('MGCN_LIVE_SLOTS', '1') != '0'
 
 
 def _hub_args(csr, d, device, n0, n1):
@@ -472,13 +505,16 @@ def pack_weights(w_cat, out=None, generation=None):
 
 def layer_fwd_fused(csr, x, rel, loop_rel, ee, ee_in_slot_order, loop_edge, w_packed, d_out, bias, bn_mean, bn_var,
                     bn_gamma, bn_beta, eps, out, node_range=None, ee_sub=(0, 0, 0), rels_weight=None, rel_out=None,
-                    tune=None, balance=True):
+                    tune=None, balance=True, live=None):
     """(2)+(4) in one launch: out = tanh(BN_eval((aggregates @ W) / 3 + bias)), aggregates kept in LDS.
     `w_packed` = pack_weights(stacked [3D, O] weights). With `node_range` = (n0, n1) only those destinations are
     computed and `out` is [n1 - n0, O]; `ee` may then be this range's shard of the slot-ordered table (see
     graph.GraphCSR.edge_table_shard) with `ee_sub` its three slot offsets (in-half, out-half, hub region).
     `balance`: hand the launch the graph's work-balanced per-workgroup row runs (GraphCSR.workgroup_bounds, one run per
-    CU, None when equal runs are balanced already); results do not depend on it."""
+    CU, None when equal runs are balanced already); results do not depend on it.
+    `live`: walk the graph's live view (GraphCSR.live_rowptr / live_rec: zero-norm slots left out; bit-identical rows for
+    finite inputs). None = whenever the graph has one and MGCN_LIVE_SLOTS is not 0; False = the canonical launch; True raises
+    where there is no view to walk."""
     N, E, D, O = csr.num_nodes, csr.num_edges_half, x.size(1), int(d_out)
     n0, n1 = (0, N) if node_range is None else (int(node_range[0]), int(node_range[1]))
     if not 0 <= n0 <= n1 <= N:
@@ -517,8 +553,18 @@ def layer_fwd_fused(csr, x, rel, loop_rel, ee, ee_in_slot_order, loop_edge, w_pa
         ee = x.new_zeros((1, D))                     # a valid (never read) table pointer
     hub_info, hub_chunks, hub_c0, hub_c1, hub_partial = _hub_args(csr, D, x.device, n0, n1)
     bounds = csr.workgroup_bounds(n0, n1, _cu_count(x.device)) if balance and n1 > n0 else None
-    rc = lib().mgcn_layer_fwd_fused(
-        N, E, D, O, csr.num_rel_rows, _dev(csr.rowptr, torch.int32, 'rowptr'), _dev(csr.rec, torch.int32, 'rec'),
+    # the graph's live view (zero-norm slots left out) whenever it has one: same rows for finite inputs, fewer row loads
+    has_view = getattr(csr, 'live_rowptr', None) is not None and tune_generation(tune) != 4
+    if live and not has_view:
+        raise NativeError('layer_fwd_fused: live=True, but this graph has no live view (no dead slot) or tune forces generation 4')
+    live = has_view and (LIVE_SLOTS if live is None else bool(live))
+    if live:
+        fn, head = lib().mgcn_layer_fwd_fused_live, (_dev(csr.live_rowptr, torch.int32, 'live_rowptr'),
+                                                     _dev(csr.live_rec, torch.int32, 'live_rec'), _dev(csr.rec, torch.int32, 'rec'))
+    else:
+        fn, head = lib().mgcn_layer_fwd_fused, (_dev(csr.rowptr, torch.int32, 'rowptr'), _dev(csr.rec, torch.int32, 'rec'))
+    rc = fn(
+        N, E, D, O, csr.num_rel_rows, *head,
         _dev(x, torch.float32, 'x'), _ld(x), _dev(rel, torch.float32, 'rel'), _dev(loop_rel, torch.float32, 'loop_rel'),
         _dev(ee, torch.float32, 'ee', True), int(bool(ee_in_slot_order)), _dev(loop_edge, torch.float32, 'loop_edge'),
         _dev(w_packed, torch.float32, 'w_packed'), _dev(bias, torch.float32, 'bias', True),

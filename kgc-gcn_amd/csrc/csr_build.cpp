@@ -137,3 +137,42 @@ extern "C" int mgcn_csr_build_host(int64_t num_nodes, int64_t num_edges_half, in
   }
   return MGCN_OK;
 }
+
+// The live view of the slot layout (include/mgcn_hip.h (1v)): the non-hub slots whose folded norm is not exactly 0, in
+// canonical order, each carrying its canonical slot index where the canonical record carries the edge id.
+extern "C" int mgcn_csr_live_view_host(int64_t num_nodes, const int32_t *rowptr_host, const mgcn_edge_rec *rec_host,
+                                       int32_t *live_rowptr_host, mgcn_edge_rec *live_rec_host, int64_t max_live,
+                                       int64_t *num_live_host, int64_t *num_dead_host) {
+  const int64_t N = num_nodes;
+  MGCN_REQUIRE(N >= 0 && rowptr_host && num_live_host && num_dead_host, "csr_live_view: bad arguments");
+  int64_t live = 0, dead = 0;
+  for (int64_t i = 0; i < 2 * N + 1; ++i)   // the two halves' pointers are one non-decreasing sequence (in-half, then out-half)
+    MGCN_REQUIRE(rowptr_host[i] >= 0 && rowptr_host[i] <= rowptr_host[i + 1], "csr_live_view: rowptr decreases at entry %lld",
+                 (long long)i);
+  for (int h = 0; h < 2; ++h) {
+    const int32_t *rowptr = rowptr_host + h * (N + 1);
+    MGCN_REQUIRE(rowptr[N] == rowptr[0] || rec_host, "csr_live_view: null records");
+    for (int64_t s = rowptr[0]; s < rowptr[N]; ++s) (rec_host[s].norm != 0.0f ? live : dead)++;
+  }
+  *num_live_host = live;
+  *num_dead_host = dead;
+  if (dead == 0) return MGCN_OK;   // nothing to leave out: the canonical layout is its own live view, none is built
+  MGCN_REQUIRE(live_rowptr_host && (live == 0 || live_rec_host) && max_live >= live,
+               "csr_live_view: outputs missing or too small for %lld live slots", (long long)live);
+  int64_t pos = 0;
+  for (int h = 0; h < 2; ++h) {
+    const int32_t *rowptr = rowptr_host + h * (N + 1);
+    int32_t *lrp = live_rowptr_host + h * (N + 1);
+    for (int64_t n = 0; n < N; ++n) {
+      lrp[n] = int32_t(pos);
+      for (int64_t s = rowptr[n]; s < rowptr[n + 1]; ++s) {
+        if (rec_host[s].norm == 0.0f) continue;
+        mgcn_edge_rec r = rec_host[s];
+        r.eid = int32_t(s);   // the slot's canonical index: the row of the slot-ordered per-edge table (+ ee_sub)
+        live_rec_host[pos++] = r;
+      }
+    }
+    lrp[N] = int32_t(pos);
+  }
+  return MGCN_OK;
+}

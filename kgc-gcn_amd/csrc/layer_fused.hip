@@ -67,18 +67,19 @@ extern "C" int mgcn_fused_kernel_generation(int32_t dim_in, int32_t dim_out, int
   return (with_row_bounds && few_tiles && dim_out > 128) ? 3 : 2;
 }
 
-extern "C" int mgcn_layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out,
-                                    int32_t num_rel_rows, const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev,
-                                    const float *x_dev, int64_t ldx, const float *rel_dev, const float *loop_rel_dev,
-                                    const float *ee_dev, int32_t ee_in_slot_order, const float *loop_edge_dev,
-                                    const float *wp_dev, const float *bias_dev, const float *bn_mean_dev,
-                                    const float *bn_var_dev, const float *bn_gamma_dev, const float *bn_beta_dev,
-                                    float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin, int64_t node_end,
-                                    int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub,
-                                    const int32_t *hubinfo_dev, const int32_t *chunks_dev, int64_t chunk_begin,
-                                    int64_t chunk_end, float *partial_dev, const float *rels_weight_dev,
-                                    float *rel_out_dev, const int32_t *row_bounds_dev, int32_t num_row_bounds,
-                                    int32_t tune, uint32_t *status_dev, void *stream) {
+namespace {
+// Both entry points. live_rowptr_dev / live_rec_dev: the live view the main walk takes (null: the canonical layout); the hub
+// pre-pass reads the canonical records either way.
+int layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out, int32_t num_rel_rows,
+                    const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev, const int32_t *live_rowptr_dev,
+                    const mgcn_edge_rec *live_rec_dev, const float *x_dev, int64_t ldx, const float *rel_dev,
+                    const float *loop_rel_dev, const float *ee_dev, int32_t ee_in_slot_order, const float *loop_edge_dev,
+                    const float *wp_dev, const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev,
+                    const float *bn_gamma_dev, const float *bn_beta_dev, float bn_eps, float *out_dev, int64_t ldo,
+                    int64_t node_begin, int64_t node_end, int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub,
+                    const int32_t *hubinfo_dev, const int32_t *chunks_dev, int64_t chunk_begin, int64_t chunk_end,
+                    float *partial_dev, const float *rels_weight_dev, float *rel_out_dev, const int32_t *row_bounds_dev,
+                    int32_t num_row_bounds, int32_t tune, uint32_t *status_dev, void *stream) {
   MGCN_REQUIRE(num_nodes >= 0 && num_edges_half >= 0 && dim_in > 0 && dim_out > 0 && num_rel_rows > 0,
                "layer_fwd_fused: bad sizes");
   MGCN_REQUIRE(node_begin >= 0 && node_begin <= node_end && node_end <= num_nodes, "layer_fwd_fused: bad node range");
@@ -117,12 +118,56 @@ extern "C" int mgcn_layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, i
                dim_in, dim_out);
   MGCN_REQUIRE(num_row_bounds >= 0 && num_row_bounds <= 4096 && (num_row_bounds == 0 || row_bounds_dev),
                "layer_fwd_fused: bad row bounds");
-  const mgcn::FusedLaunch a = {num_nodes, dim_in, dim_out, num_rel_rows, rowptr_dev, rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev,
+  const bool live = live_rowptr_dev != nullptr;
+  MGCN_REQUIRE(!live || gen != 4, "layer_fwd_fused: tune %d: generation 4 does not walk a live view", tune);
+  const mgcn::FusedLaunch a = {num_nodes, dim_in, dim_out, num_rel_rows, live ? live_rowptr_dev : rowptr_dev,
+                               live ? live_rec_dev : rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev,
                                loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev, bn_gamma_dev, bn_beta_dev, bn_eps, out_dev, ldo,
                                node_begin, node_end, ee_sub_in, ee_sub_out, num_chunks > 0 ? hubinfo_dev : nullptr, chunk_begin,
                                partial_dev, want_rel ? rels_weight_dev : nullptr, want_rel ? rel_out_dev : nullptr, row_bounds_dev,
-                               num_row_bounds, tune, status_dev, stream};
+                               num_row_bounds, tune, status_dev, stream, live};
   if (gen == 4) return mgcn::fused4_launch(a);
   if (gen == 2) return mgcn::fused2_launch(a);
   return mgcn::fused3_launch(a);
+}
+}  // namespace
+
+extern "C" int mgcn_layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out,
+                                    int32_t num_rel_rows, const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev,
+                                    const float *x_dev, int64_t ldx, const float *rel_dev, const float *loop_rel_dev,
+                                    const float *ee_dev, int32_t ee_in_slot_order, const float *loop_edge_dev,
+                                    const float *wp_dev, const float *bias_dev, const float *bn_mean_dev,
+                                    const float *bn_var_dev, const float *bn_gamma_dev, const float *bn_beta_dev,
+                                    float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin, int64_t node_end,
+                                    int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub,
+                                    const int32_t *hubinfo_dev, const int32_t *chunks_dev, int64_t chunk_begin,
+                                    int64_t chunk_end, float *partial_dev, const float *rels_weight_dev,
+                                    float *rel_out_dev, const int32_t *row_bounds_dev, int32_t num_row_bounds,
+                                    int32_t tune, uint32_t *status_dev, void *stream) {
+  return layer_fwd_fused(num_nodes, num_edges_half, dim_in, dim_out, num_rel_rows, rowptr_dev, rec_dev, nullptr, nullptr, x_dev, ldx,
+                         rel_dev, loop_rel_dev, ee_dev, ee_in_slot_order, loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev,
+                         bn_gamma_dev, bn_beta_dev, bn_eps, out_dev, ldo, node_begin, node_end, ee_sub_in, ee_sub_out, ee_sub_hub,
+                         hubinfo_dev, chunks_dev, chunk_begin, chunk_end, partial_dev, rels_weight_dev, rel_out_dev, row_bounds_dev,
+                         num_row_bounds, tune, status_dev, stream);
+}
+
+// The same launch on the graph's live view (include/mgcn_hip.h (2b), "Live view")
+extern "C" int mgcn_layer_fwd_fused_live(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out,
+                                         int32_t num_rel_rows, const int32_t *live_rowptr_dev,
+                                         const mgcn_edge_rec *live_rec_dev, const mgcn_edge_rec *rec_dev, const float *x_dev,
+                                         int64_t ldx, const float *rel_dev, const float *loop_rel_dev, const float *ee_dev,
+                                         int32_t ee_in_slot_order, const float *loop_edge_dev, const float *wp_dev,
+                                         const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev,
+                                         const float *bn_gamma_dev, const float *bn_beta_dev, float bn_eps, float *out_dev,
+                                         int64_t ldo, int64_t node_begin, int64_t node_end, int64_t ee_sub_in,
+                                         int64_t ee_sub_out, int64_t ee_sub_hub, const int32_t *hubinfo_dev,
+                                         const int32_t *chunks_dev, int64_t chunk_begin, int64_t chunk_end, float *partial_dev,
+                                         const float *rels_weight_dev, float *rel_out_dev, const int32_t *row_bounds_dev,
+                                         int32_t num_row_bounds, int32_t tune, uint32_t *status_dev, void *stream) {
+  MGCN_REQUIRE(live_rowptr_dev && live_rec_dev, "layer_fwd_fused_live: null live view");
+  return layer_fwd_fused(num_nodes, num_edges_half, dim_in, dim_out, num_rel_rows, live_rowptr_dev, rec_dev, live_rowptr_dev,
+                         live_rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev, ee_in_slot_order, loop_edge_dev, wp_dev, bias_dev,
+                         bn_mean_dev, bn_var_dev, bn_gamma_dev, bn_beta_dev, bn_eps, out_dev, ldo, node_begin, node_end, ee_sub_in,
+                         ee_sub_out, ee_sub_hub, hubinfo_dev, chunks_dev, chunk_begin, chunk_end, partial_dev, rels_weight_dev,
+                         rel_out_dev, row_bounds_dev, num_row_bounds, tune, status_dev, stream);
 }

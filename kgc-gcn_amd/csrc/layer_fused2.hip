@@ -53,7 +53,9 @@ struct Args2 : LayerArgs {   // wp: [G][NT][3][64]
 constexpr int EPI_FLOATS = 2 * 208;
 constexpr int REL_LDS_MAX_BYTES = 32 * 1024;
 
-template <int NT, int NRT, bool RELLDS, bool HUBS>
+// LIVE: rowptr / rec are the graph's live view (include/mgcn_hip.h (1v)): zero-norm slots are left out, and a record's fourth
+// word is its canonical slot index — the per-edge row, where the canonical walk takes the slot position itself.
+template <int NT, int NRT, bool RELLDS, bool HUBS, bool LIVE>
 __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
   constexpr int BM = NRT * 16;
   constexpr int PIECE = 16 * BM * 16;   // bytes of one bf16 piece of a stage image: 16 chunk columns x BM rows x 16 B
@@ -234,7 +236,8 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
                 if (MGCN_ABLATE(16)) rsrc[u] = 0;    // (diagnostics: every row load hits the same cached lines)
                 xv[u] = *reinterpret_cast<const float4 *>(xb + uint64_t(uint32_t(rsrc[u])) * ldx32);
                 if (!RELLDS) rv[u] = *reinterpret_cast<const float4 *>(relb + uint64_t(uint32_t(rtyp[u])) * d32);
-                const uint32_t erow = MGCN_ABLATE(16) ? 0u : uint32_t(((s + u < end) ? s + u : end - 1) - ee_sub_mode);
+                const int pos = (s + u < end) ? s + u : end - 1;   // the per-edge row: the slot itself, or (LIVE) the record's fourth word
+                const uint32_t erow = MGCN_ABLATE(16) ? 0u : uint32_t((LIVE ? __shfl(myrec.w, glane0 + (pos - cbase)) : pos) - ee_sub_mode);
                 ev[u] = *reinterpret_cast<const float4 *>(eeb + uint64_t(erow) * d32);
               }
 #ifdef MGCN_DIAG
@@ -511,19 +514,36 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
   }
 }
 
-template <int NT, int NRT, bool RELLDS, bool HUBS>
+template <int NT, int NRT, bool RELLDS, bool HUBS, bool LIVE>
 int launch2(const Args2 &p, int grid, hipStream_t st) {
   constexpr size_t lds_bytes = size_t(2) * 3 * 16 * (NRT * 16) * 16 + EPI_FLOATS * 4 + (RELLDS ? REL_LDS_MAX_BYTES : 0);
   // (the attribute is sticky per device and setting it costs microseconds: done on every launch, no state kept)
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused2_kernel<NT, NRT, RELLDS, HUBS>),
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused2_kernel<NT, NRT, RELLDS, HUBS, LIVE>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)) != hipSuccess)
     return mgcn::fail(MGCN_ELAUNCH, "layer_fused2: cannot reserve %zu bytes of LDS", lds_bytes);
-  hipLaunchKernelGGL((layer_fused2_kernel<NT, NRT, RELLDS, HUBS>), dim3(unsigned(grid)), dim3(T2), lds_bytes, st, p);
+  hipLaunchKernelGGL((layer_fused2_kernel<NT, NRT, RELLDS, HUBS, LIVE>), dim3(unsigned(grid)), dim3(T2), lds_bytes, st, p);
   MGCN_CHECK_LAUNCH("layer_fused2_kernel");
   return MGCN_OK;
 }
 
 int pick_nt2(int o) { return o <= 32 ? 2 : o <= 64 ? 4 : o <= 128 ? 8 : 13; }
+
+// NT = 13 (the 200-wide layers) has all variants; narrower outputs take the general one
+template <bool LIVE>
+int pick2(const Args2 &p, int dim_out, int nrt, int grid, int grid5, bool rel_lds, bool hubs, hipStream_t st) {
+  switch (pick_nt2(dim_out)) {
+    case 2: return launch2<2, 5, false, true, LIVE>(p, grid5, st);
+    case 4: return launch2<4, 5, false, true, LIVE>(p, grid5, st);
+    case 8: return launch2<8, 5, false, true, LIVE>(p, grid5, st);
+    default:
+      if (nrt == 4) {
+        if (rel_lds) return hubs ? launch2<13, 4, true, true, LIVE>(p, grid, st) : launch2<13, 4, true, false, LIVE>(p, grid, st);
+        return hubs ? launch2<13, 4, false, true, LIVE>(p, grid, st) : launch2<13, 4, false, false, LIVE>(p, grid, st);
+      }
+      if (rel_lds) return hubs ? launch2<13, 5, true, true, LIVE>(p, grid, st) : launch2<13, 5, true, false, LIVE>(p, grid, st);
+      return hubs ? launch2<13, 5, false, true, LIVE>(p, grid, st) : launch2<13, 5, false, false, LIVE>(p, grid, st);
+  }
+}
 
 struct Shape2 {
   int nch, nkb_last, kbm, G;
@@ -598,20 +618,9 @@ int fused2_launch(const FusedLaunch &a) {
   hipStream_t st = static_cast<hipStream_t>(a.stream);
   // the relation table rides in LDS when it fits beside the stage images (a third of the gather's row loads)
   const bool rel_lds = a.rel && size_t(a.num_rel_rows - 1) * dim_in * 4 <= size_t(REL_LDS_MAX_BYTES);
-  // NT = 13 (the 200-wide layers) has all variants; narrower outputs take the general one
   const bool hubs = a.hubinfo != nullptr;
-  switch (pick_nt2(dim_out)) {
-    case 2: return launch2<2, 5, false, true>(p, grid_for(5), st);
-    case 4: return launch2<4, 5, false, true>(p, grid_for(5), st);
-    case 8: return launch2<8, 5, false, true>(p, grid_for(5), st);
-    default:
-      if (nrt == 4) {
-        if (rel_lds) return hubs ? launch2<13, 4, true, true>(p, grid, st) : launch2<13, 4, true, false>(p, grid, st);
-        return hubs ? launch2<13, 4, false, true>(p, grid, st) : launch2<13, 4, false, false>(p, grid, st);
-      }
-      if (rel_lds) return hubs ? launch2<13, 5, true, true>(p, grid, st) : launch2<13, 5, true, false>(p, grid, st);
-      return hubs ? launch2<13, 5, false, true>(p, grid, st) : launch2<13, 5, false, false>(p, grid, st);
-  }
+  return a.live ? pick2<true>(p, dim_out, nrt, grid, grid_for(5), rel_lds, hubs, st)
+                : pick2<false>(p, dim_out, nrt, grid, grid_for(5), rel_lds, hubs, st);
 }
 
 }  // namespace mgcn

@@ -72,7 +72,9 @@ __device__ __forceinline__ void signal_add(uint32_t *c, int lane) {
   asm volatile("" ::: "memory");
 }
 
-template <int NT, int NRT, int NCH, bool RELLDS>
+// LIVE: rowptr / rec are the graph's live view (include/mgcn_hip.h (1v)): zero-norm slots are left out, and a record's fourth
+// word is its canonical slot index — the per-edge row, where the canonical walk takes the slot position itself.
+template <int NT, int NRT, int NCH, bool RELLDS, bool LIVE>
 __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
   constexpr int BM = NRT * 16;
   constexpr int UB = 4 / NCH;           // slots per gather batch: 8 row loads of 16 B per lane in flight either way
@@ -302,7 +304,8 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
               float4 xv[UB][NCH], rv[UB][NCH], ev[UB][NCH];
 #pragma unroll
               for (int u = 0; u < UB; ++u) {
-                const uint32_t erow = uint32_t(((s + u < end) ? s + u : end - 1) - ee_sub_mode);
+                const int pos = (s + u < end) ? s + u : end - 1;   // the per-edge row: the slot itself, or (LIVE) the record's fourth word
+                const uint32_t erow = uint32_t((LIVE ? __shfl(myrec.w, glane0 + (pos - cbase)) : pos) - ee_sub_mode);
 #pragma unroll
                 for (int j = 0; j < NCH; ++j) {
                   xv[u][j] = *reinterpret_cast<const float4 *>(p.x + coff[j] + uint64_t(uint32_t(rsrc[u])) * ldx32);
@@ -657,28 +660,32 @@ size_t lds_bytes3(const Shape3 &s, int nrt, int nimg, int nt, size_t rel_bytes) 
   return size_t(3) * s.ncc * (nrt * 16) * 16 + size_t(nimg) * (nrt * 16) * s.ncc * 32 + 64 + size_t(2) * nt * 16 * 4 + rel_bytes;
 }
 
-template <int NT, int NRT, int NCH, bool RELLDS>
+template <int NT, int NRT, int NCH, bool RELLDS, bool LIVE>
 int launch3(const Args3 &p, int grid, size_t lds, hipStream_t st) {
   // (the attribute is sticky per device and raising it costs a few microseconds: set on every launch, no state kept)
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused3_kernel<NT, NRT, NCH, RELLDS>),
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused3_kernel<NT, NRT, NCH, RELLDS, LIVE>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, int(LDS_MAX)) != hipSuccess)
     return mgcn::fail(MGCN_ELAUNCH, "layer_fused3: cannot reserve %zu bytes of LDS", LDS_MAX);
-  hipLaunchKernelGGL((layer_fused3_kernel<NT, NRT, NCH, RELLDS>), dim3(unsigned(grid)), dim3(T3), lds, st, p);
+  hipLaunchKernelGGL((layer_fused3_kernel<NT, NRT, NCH, RELLDS, LIVE>), dim3(unsigned(grid)), dim3(T3), lds, st, p);
   MGCN_CHECK_LAUNCH("layer_fused3_kernel");
   return MGCN_OK;
 }
 
 template <int NT, int NRT, int NCH>
-int launch3_rel(const Args3 &p, int grid, size_t lds, bool rel_lds, hipStream_t st) {
-  if (rel_lds) return launch3<NT, NRT, NCH, true>(p, grid, lds, st);
-  return launch3<NT, NRT, NCH, false>(p, grid, lds, st);
+int launch3_rel(const Args3 &p, int grid, size_t lds, bool rel_lds, bool live, hipStream_t st) {
+  if (live) {
+    if (rel_lds) return launch3<NT, NRT, NCH, true, true>(p, grid, lds, st);
+    return launch3<NT, NRT, NCH, false, true>(p, grid, lds, st);
+  }
+  if (rel_lds) return launch3<NT, NRT, NCH, true, false>(p, grid, lds, st);
+  return launch3<NT, NRT, NCH, false, false>(p, grid, lds, st);
 }
 
 template <int NT, int NCH>
-int launch3_nrt(const Args3 &p, int nrt, int grid, size_t lds, bool rel_lds, hipStream_t st) {
-  if (nrt == 3) return launch3_rel<NT, 3, NCH>(p, grid, lds, rel_lds, st);
-  if (nrt == 4) return launch3_rel<NT, 4, NCH>(p, grid, lds, rel_lds, st);
-  return launch3_rel<NT, 5, NCH>(p, grid, lds, rel_lds, st);
+int launch3_nrt(const Args3 &p, int nrt, int grid, size_t lds, bool rel_lds, bool live, hipStream_t st) {
+  if (nrt == 3) return launch3_rel<NT, 3, NCH>(p, grid, lds, rel_lds, live, st);
+  if (nrt == 4) return launch3_rel<NT, 4, NCH>(p, grid, lds, rel_lds, live, st);
+  return launch3_rel<NT, 5, NCH>(p, grid, lds, rel_lds, live, st);
 }
 
 }  // namespace
@@ -765,11 +772,11 @@ int fused3_launch(const FusedLaunch &a) {
   const size_t lds = lds_bytes3(s, nrt, nimg, nt, rel_lds ? rel_bytes : 0);
   hipStream_t st = static_cast<hipStream_t>(a.stream);
   if (nt == 32) {
-    if (s.nch == 1) return launch3_rel<32, 3, 1>(p, grid, lds, rel_lds, st);
-    return launch3_rel<32, 3, 2>(p, grid, lds, rel_lds, st);
+    if (s.nch == 1) return launch3_rel<32, 3, 1>(p, grid, lds, rel_lds, a.live, st);
+    return launch3_rel<32, 3, 2>(p, grid, lds, rel_lds, a.live, st);
   }
-  if (s.nch == 1) return launch3_nrt<13, 1>(p, nrt, grid, lds, rel_lds, st);
-  return launch3_nrt<13, 2>(p, nrt, grid, lds, rel_lds, st);
+  if (s.nch == 1) return launch3_nrt<13, 1>(p, nrt, grid, lds, rel_lds, a.live, st);
+  return launch3_nrt<13, 2>(p, nrt, grid, lds, rel_lds, a.live, st);
 }
 
 }  // namespace mgcn

@@ -60,6 +60,7 @@ struct FusedLaunch {
   int32_t tune;
   uint32_t *status;            // generation 3
   void *stream;
+  bool live;                   // rowptr / rec are the live view (include/mgcn_hip.h (1v)): generations 2 and 3
 };
 
 // fused layer, lockstep generation (layer_fused2.hip): D <= 256 and O <= 208 (the shapes whose alternating layers keep

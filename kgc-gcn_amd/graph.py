@@ -13,12 +13,18 @@ from . import _native
 class GraphCSR(object):
     """Device-resident slot arrays produced by mgcn_csr_build_host (include/mgcn_hip.h (1))."""
 
-    _FIELDS = ('rowptr', 'rec', 'perm', 'hubinfo', 'chunks', 'slot_dst', 'mirror', 'typeptr', 'typeslots')
+    _FIELDS = ('rowptr', 'rec', 'perm', 'hubinfo', 'chunks', 'slot_dst', 'mirror', 'typeptr', 'typeslots', 'live_rowptr', 'live_rec')
 
     def __init__(self, num_nodes, num_rel_rows, edge_index, edge_type, device, with_backward=True, hub_threshold=None,
                  hub_chunk=None):
         host = _native.csr_build_host(num_nodes, num_rel_rows, edge_index, edge_type, with_backward, hub_threshold,
                                       hub_chunk)
+        # the live view (include/mgcn_hip.h (1v)): the slots with a non-zero norm, built once per graph and kept resident for
+        # the fused forward; absent (None) when no slot is dead
+        live = _native.csr_live_view_host(host['rowptr'], host['rec'])
+        if live is not None:
+            host.update(live_rowptr=live['live_rowptr'], live_rec=live['live_rec'])
+        self.num_dead_slots = live['num_dead'] if live is not None else 0
         self.num_chunks = host['num_chunks']                     # hub chunks (0: no destination is a hub)
         self.num_nodes = int(num_nodes)
         self.num_edges_half = int(edge_index.size(1)) // 2
