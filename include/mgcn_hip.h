@@ -691,6 +691,59 @@ int mgcn_conve_tail_bwd(int32_t batch, int32_t dim, const float *z_dev, int64_t 
                         const float *gamma_dev, const float *gx_dev, int64_t ldg, float *gz_dev, int64_t ldgz,
                         float *d_gamma_dev, float *d_beta_dev, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (12) Counter-based dropout (csrc/dropout.hip): the keep bit of an element is a pure function of the seed, the
+ * step, the site, the GLOBAL row (an entity id, or a batch row in the trunk) and the column, so a mask does not depend on the
+ * launch geometry, on the rank count or on which rank owns the row; the backward recomputes it instead of loading a saved mask.
+ *
+ * The bit definition. Let sm(x) be one SplitMix64 step (^ is XOR, >> an unsigned shift, all arithmetic mod 2^64):
+ *     x += 0x9E3779B97F4A7C15
+ *     z = x
+ *     z = (z ^ z>>30) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ z>>27) * 0x94D049BB133111EB
+ *     return z ^ z>>31
+ * Then:
+ *   - key(seed, step, site) = sm(sm(sm(seed) ^ step) ^ site). The host computes it once per call and passes it by value as a
+ *     64-bit kernel argument.
+ *   - Words = Philox4x32-10 (the generator of the Random123 library), using that library's standard constants. The multipliers
+ *     are 0xD2511F53 and 0xCD9E8D57. The key increments are 0x9E3779B9 and 0xBB67AE85.
+ *       Key words are (key & 0xffffffff, key >> 32).
+ *       The counter is (row_lo, row_hi, col >> 2, 0), where row is the 64-bit global row row0 + r.
+ *       Element (row, col) uses output word col & 3.
+ *   - An element is kept iff word < T, where T = min(2^32 - 1, floor((1 - p) * 2^32)), computed in Python doubles.
+ *     inv_keep = 1 / (1 - p) is passed as an f32.
+ *   - A kept element becomes x * inv_keep (one f32 multiply). A dropped element becomes +0.0f whatever x holds. The backward is
+ *     the same operation applied to the gradient.
+ *   - Sites with p <= 0 launch nothing. Sites with p >= 1 produce zeros (T = 0 keeps nothing; the caller passes inv_keep = 0).
+ *   - Site ids: layer li: 4 li + 0 (in), 4 li + 1 (out), 4 li + 2 (gcn_drop); trunk: 0x1000 (feature, row = batch row, flat_sz
+ *     columns) and 0x1001 (hidden, O columns).
+ *
+ * mgcn_dropout_apply: out [rows, cols] (rows ldo floats apart) = dropout of x [rows, cols] (rows ldx apart) under `key`, row r of
+ *   the block being global row row0 + r. out may be x itself (same pointer, same leading dimension); any other overlap is the
+ *   caller's error. Columns cols .. ld of a padded row are not touched.
+ * mgcn_dropout_apply_pair: the same for two sites over one block in one launch -- the layer's in / out pair: out_a from x_a under
+ *   key_a, out_b from x_b under key_b, one row0, threshold and inv_keep. x_a and x_b may be one matrix (the backward reads the
+ *   incoming gradient once); each output may be either input as the same matrix; the two outputs are distinct.
+ * mgcn_dropout_mask: the keep bytes (1 / 0) [rows, cols], rows ldm bytes apart: the bool masks (9) and (11) take.
+ * mgcn_dropout_mask_host: the same bytes on the CPU from the SAME inline function the kernels call. Test infrastructure, like
+ *   mgcn_csr_build_host's role for the layout; no model path calls it.
+ * One lane serves four columns with one Philox call; 16-byte accesses when every base pointer is 16-byte aligned and every leading
+ * dimension a multiple of 4 (mask: 4-byte stores under the same rule for 4 bytes), the element-wise path with the same bits
+ * otherwise. At most 2048 workgroups of 256 threads stride over the block; index arithmetic is 64-bit; no atomics, no LDS.
+ * MGCN_EINVAL, nothing launched: a null pointer, rows < 0 or > 2^40, cols < 1, a leading dimension below cols, rows x ld above
+ * 2^60, an inv_keep that is negative or not finite, an output aliasing an input with another leading dimension, out_a == out_b.
+ * rows == 0 launches nothing.
+ */
+int mgcn_dropout_apply(int64_t rows, int32_t cols, const float *x_dev, int64_t ldx, float *out_dev, int64_t ldo, uint64_t key,
+                       uint64_t row0, uint32_t threshold, float inv_keep, void *stream);
+int mgcn_dropout_apply_pair(int64_t rows, int32_t cols, const float *xa_dev, int64_t ldxa, float *outa_dev, int64_t ldoa,
+                            uint64_t key_a, const float *xb_dev, int64_t ldxb, float *outb_dev, int64_t ldob, uint64_t key_b,
+                            uint64_t row0, uint32_t threshold, float inv_keep, void *stream);
+int mgcn_dropout_mask(int64_t rows, int32_t cols, uint8_t *mask_dev, int64_t ldm, uint64_t key, uint64_t row0, uint32_t threshold,
+                      void *stream);
+int mgcn_dropout_mask_host(int64_t rows, int32_t cols, uint8_t *mask_host, int64_t ldm, uint64_t key, uint64_t row0,
+                           uint32_t threshold);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ There is deliberately NO fallback: if the library is missing or a tensor is not 
 call raises. torch is used here for device memory and the current HIP stream only.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -15,6 +16,7 @@ ABI_VERSION = 4
 _lib = None
 
 _i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+_u32, _u64 = ctypes.c_uint32, ctypes.c_uint64
 _ptr = ctypes.c_void_p
 
 _SIGNATURES = {
@@ -92,6 +94,11 @@ _SIGNATURES = {
                                            _i64, _ptr]),
     'mgcn_conve_tail_bwd': (ctypes.c_int, [_i32, _i32, _ptr, _i64, _ptr, _i64, _f32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64,
                                            _ptr, _ptr, _ptr]),
+    'mgcn_dropout_apply': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _i64, _u64, _u64, _u32, _f32, _ptr]),
+    'mgcn_dropout_apply_pair': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _i64, _u64, _ptr, _i64, _ptr, _i64, _u64, _u64, _u32, _f32,
+                                               _ptr]),
+    'mgcn_dropout_mask': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _u64, _u64, _u32, _ptr]),
+    'mgcn_dropout_mask_host': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _u64, _u64, _u32]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
     'mgcn_ingest_count': (_i64, [_ptr, _i32]),
@@ -1218,6 +1225,118 @@ def adam_step(grads, params, exp_avgs, exp_avg_sqs, coef, step_size, bc2_sqrt, b
     _check(lib().mgcn_adam_step(n, _ptr_array(grads), _ptr_array(params), _ptr_array(exp_avgs), _ptr_array(exp_avg_sqs), numel,
                                 _dev(coef, torch.float32, 'coef', True), float(step_size), float(bc2_sqrt), float(beta1),
                                 float(beta2), float(eps), float(weight_decay), _stream(params[0])), 'mgcn_adam_step')
+
+
+# ------------------------------------------------------------------------------------------------
+# (12) counter-based dropout (csrc/dropout.hip)
+_M64 = (1 << 64) - 1
+DROPOUT_SITE_FEATURE, DROPOUT_SITE_HIDDEN = 0x1000, 0x1001
+
+
+def _splitmix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    z = x
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def dropout_key(seed, step, site):
+    """key(seed, step, site) = sm(sm(sm(seed) ^ step) ^ site), sm = one SplitMix64 step: the 64-bit key of one site's masks."""
+    return _splitmix64(_splitmix64(_splitmix64(int(seed) & _M64) ^ (int(step) & _M64)) ^ (int(site) & _M64))
+
+
+def dropout_layer_site(li, which):
+    """Site id of layer `li`: which = 0 (in), 1 (out), 2 (gcn_drop)."""
+    return 4 * int(li) + int(which)
+
+
+def dropout_threshold(p):
+    """T = min(2^32 - 1, floor((1 - p) * 2^32)) in Python doubles: an element is kept iff its 32-bit word is below T."""
+    return max(0, min((1 << 32) - 1, int(math.floor((1.0 - float(p)) * 4294967296.0))))
+
+
+def dropout_scale(p):
+    """(threshold, inv_keep) of a site with 0 < p: p >= 1 keeps nothing (T = 0) and scales by 0, as F.dropout(p=1) gives zeros."""
+    return (0, 0.0) if p >= 1 else (dropout_threshold(p), 1.0 / (1.0 - p))
+
+
+def dropout_supported(*tensors):
+    """f32 GPU matrices (1-D or 2-D, last dimension contiguous, rows at least cols apart) the dropout kernels take."""
+    for t in tensors:
+        if t is None or not t.is_cuda or t.dtype != torch.float32 or t.dim() not in (1, 2) or t.numel() == 0:
+            return False
+        if t.size(-1) >= (1 << 31) or (t.size(-1) > 1 and t.stride(-1) != 1) or (t.dim() == 2 and t.size(0) > 1 and t.stride(0) < t.size(1)):
+            return False
+    return True
+
+
+def _drop_block(t, what):
+    if t.dim() not in (1, 2) or (t.dim() == 2 and t.size(0) > 1 and t.stride(0) < t.size(1)):
+        raise NativeError('%s: a matrix [rows, cols] with rows at least cols apart is required, got %s strides %s'
+                          % (what, tuple(t.shape), t.stride()))
+    return (1, t.size(0)) if t.dim() == 1 else (t.size(0), t.size(1))
+
+
+def dropout_apply(x, key, row0, p, out=None):
+    """(12) Dropout of x [rows, cols] under `key` with global first row `row0`; `out`: the tensor to write (x itself = in place;
+    None = a fresh one). p in (0, 1]; p >= 1 gives zeros."""
+    rows, cols = _drop_block(x, 'dropout_apply')
+    if out is None:
+        out = torch.empty((rows, cols) if x.dim() == 2 else (cols,), dtype=torch.float32, device=x.device)
+    _same_device(x, out)
+    if _drop_block(out, 'dropout_apply') != (rows, cols):
+        raise NativeError('dropout_apply: out %s does not match x %s' % (tuple(out.shape), tuple(x.shape)))
+    if rows == 0 or cols == 0:
+        return out
+    thr, inv_keep = dropout_scale(p)
+    _check(lib().mgcn_dropout_apply(rows, cols, _dev(x, torch.float32, 'x'), _ld(x), _dev(out, torch.float32, 'out'), _ld(out),
+                                    int(key) & _M64, int(row0) & _M64, thr, inv_keep, _stream(x)), 'mgcn_dropout_apply')
+    return out
+
+
+def dropout_apply_pair(xa, key_a, xb, key_b, row0, p, out_a=None, out_b=None):
+    """(12) Two sites over one block in one launch (the layer's in / out pair). xa and xb may be one tensor; an output may be its
+    input (in place); None = a fresh tensor. Returns (out_a, out_b)."""
+    rows, cols = _drop_block(xa, 'dropout_apply_pair')
+    new = lambda: torch.empty((rows, cols), dtype=torch.float32, device=xa.device)
+    out_a, out_b = new() if out_a is None else out_a, new() if out_b is None else out_b
+    _same_device(xa, xb, out_a, out_b)
+    if any(t.dim() != 2 or _drop_block(t, 'dropout_apply_pair') != (rows, cols) for t in (xa, xb, out_a, out_b)):
+        raise NativeError('dropout_apply_pair: the four matrices must be [%d, %d]' % (rows, cols))
+    if rows == 0 or cols == 0:
+        return out_a, out_b
+    thr, inv_keep = dropout_scale(p)
+    _check(lib().mgcn_dropout_apply_pair(
+        rows, cols, _dev(xa, torch.float32, 'x_a'), _ld(xa), _dev(out_a, torch.float32, 'out_a'), _ld(out_a), int(key_a) & _M64,
+        _dev(xb, torch.float32, 'x_b'), _ld(xb), _dev(out_b, torch.float32, 'out_b'), _ld(out_b), int(key_b) & _M64,
+        int(row0) & _M64, thr, inv_keep, _stream(xa)), 'mgcn_dropout_apply_pair')
+    return out_a, out_b
+
+
+def dropout_mask(rows, cols, key, row0, p, device=None, out=None):
+    """(12) The bool keep-mask [rows, cols] of a site: what (9) and (11) take in place of a bernoulli_ draw. `out`: a bool or uint8
+    matrix to write (may be a padded view)."""
+    if out is None:
+        out = torch.empty((int(rows), int(cols)), dtype=torch.bool, device=device)
+    if out.dtype not in (torch.bool, torch.uint8) or out.dim() != 2 or tuple(out.shape) != (int(rows), int(cols)):
+        raise NativeError('dropout_mask: out must be a bool / uint8 [%d, %d]' % (rows, cols))
+    _drop_block(out, 'dropout_mask')
+    if out.numel() == 0:
+        return out
+    _check(lib().mgcn_dropout_mask(int(rows), int(cols), _dev(out, out.dtype, 'mask'), _ld(out), int(key) & _M64, int(row0) & _M64,
+                                   dropout_scale(p)[0], _stream(out)), 'mgcn_dropout_mask')
+    return out
+
+
+def dropout_mask_host(rows, cols, key, row0, p):
+    """(12) dropout_mask on the CPU (uint8 host tensor), from the same inline function the kernels call: test infrastructure."""
+    out = torch.empty((int(rows), int(cols)), dtype=torch.uint8)
+    if out.numel() == 0:
+        return out
+    _check(lib().mgcn_dropout_mask_host(int(rows), int(cols), out.data_ptr(), int(cols),
+                                        int(key) & _M64, int(row0) & _M64, dropout_scale(p)[0]), 'mgcn_dropout_mask_host')
+    return out
 
 
 class IngestUnsupported(NativeError):

@@ -1,0 +1,247 @@
+// Counter-based dropout (include/mgcn_hip.h (12)): the keep bit of element (row, col) of a site is a pure function of
+// (key, global row, col) -- Philox4x32-10 keyed by a SplitMix64 mix of (seed, step, site) that the host computes -- so a mask does
+// not depend on the launch geometry, on the rank count or on which rank owns the row, and the backward recomputes it instead of
+// loading a saved one. Streaming kernels: one Philox call serves four columns, one lane moves one 16-byte group when base pointers
+// and leading dimensions allow it and takes the element-wise path otherwise (same bits). No atomics, no LDS, no inline assembly;
+// all index arithmetic is 64-bit.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "mgcn_common.h"
+
+namespace {
+
+constexpr int TPB = 256;            // four waves
+constexpr int64_t MAX_BLOCKS = 2048;   // 256 CUs x 8 workgroups; the rest is strided over
+constexpr int64_t MAX_ROWS = int64_t(1) << 40;
+
+// The four 32-bit words of column block `cb` (columns 4 cb .. 4 cb + 3) of global row `row` under `key`: Philox4x32-10 with the
+// Random123 constants, key words (key & 0xffffffff, key >> 32), counter (row_lo, row_hi, cb, 0). Element (row, col) uses word col & 3.
+// The ONE definition: the kernels and mgcn_dropout_mask_host both call it.
+__host__ __device__ inline void dropout_words(uint64_t key, uint64_t row, uint32_t cb, uint32_t w[4]) {
+  uint32_t k0 = uint32_t(key), k1 = uint32_t(key >> 32);
+  uint32_t c0 = uint32_t(row), c1 = uint32_t(row >> 32), c2 = cb, c3 = 0u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    if (r) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const uint64_t p0 = uint64_t(0xD2511F53u) * c0, p1 = uint64_t(0xCD9E8D57u) * c2;
+    const uint32_t n0 = uint32_t(p1 >> 32) ^ c1 ^ k0, n2 = uint32_t(p0 >> 32) ^ c3 ^ k1;
+    c1 = uint32_t(p1);
+    c3 = uint32_t(p0);
+    c0 = n0;
+    c2 = n2;
+  }
+  w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
+}
+
+// kept: one f32 multiply; dropped: +0.0f whatever x holds (inf and NaN included)
+__device__ inline float dropped(float x, bool keep, float inv_keep) { return keep ? x * inv_keep : 0.f; }
+
+// work unit u -> (row, column block); the 32-bit division where u allows it
+__device__ inline void unit_of(int64_t u, int32_t ncb, int64_t &r, int32_t &cb) {
+  if (u <= int64_t(0xffffffffu)) {
+    const uint32_t q = uint32_t(u) / uint32_t(ncb);
+    r = q;
+    cb = int32_t(uint32_t(u) - q * uint32_t(ncb));
+  } else {
+    r = u / ncb;
+    cb = int32_t(u - r * ncb);
+  }
+}
+
+struct Site {
+  const float *x;
+  int64_t ldx;
+  float *out;
+  int64_t ldo;
+  uint64_t key;
+};
+
+// NS sites (1: apply, 2: the layer's in / out pair) over the same [rows, cols] block; VEC: every base pointer is 16-byte aligned and
+// every leading dimension a multiple of four floats, so a whole column block is one 16-byte access. A lane reads its elements of
+// every site before it writes any, and no lane touches another's elements: an output may be its own input, and the two inputs of a
+// pair may be one tensor.
+template <int NS, bool VEC>
+__global__ __launch_bounds__(TPB) void apply_kernel(int64_t rows, int32_t cols, int32_t ncb, Site s0, Site s1, uint64_t row0,
+                                                    uint32_t threshold, float inv_keep) {
+  const int64_t units = rows * ncb, stride = int64_t(gridDim.x) * TPB;
+  for (int64_t u = int64_t(blockIdx.x) * TPB + threadIdx.x; u < units; u += stride) {
+    int64_t r;
+    int32_t cb;
+    unit_of(u, ncb, r, cb);
+    const int32_t c = cb * 4, n = cols - c < 4 ? cols - c : 4;
+    const Site site[2] = {s0, s1};
+    float v[NS][4];
+    if (VEC && n == 4) {
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const float4 t = *reinterpret_cast<const float4 *>(site[i].x + r * site[i].ldx + c);
+        v[i][0] = t.x, v[i][1] = t.y, v[i][2] = t.z, v[i][3] = t.w;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NS; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[i][j] = j < n ? site[i].x[r * site[i].ldx + c + j] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      uint32_t w[4];
+      dropout_words(site[i].key, row0 + uint64_t(r), uint32_t(cb), w);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[i][j] = dropped(v[i][j], w[j] < threshold, inv_keep);
+    }
+    if (VEC && n == 4) {
+#pragma unroll
+      for (int i = 0; i < NS; ++i)
+        *reinterpret_cast<float4 *>(site[i].out + r * site[i].ldo + c) = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NS; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < n) site[i].out[r * site[i].ldo + c + j] = v[i][j];
+    }
+  }
+}
+
+// keep bytes (1 / 0); VEC: base 4-byte aligned and ldm a multiple of four, so a whole column block is one 32-bit store
+template <bool VEC>
+__global__ __launch_bounds__(TPB) void mask_kernel(int64_t rows, int32_t cols, int32_t ncb, uint8_t *mask, int64_t ldm, uint64_t key,
+                                                   uint64_t row0, uint32_t threshold) {
+  const int64_t units = rows * ncb, stride = int64_t(gridDim.x) * TPB;
+  for (int64_t u = int64_t(blockIdx.x) * TPB + threadIdx.x; u < units; u += stride) {
+    int64_t r;
+    int32_t cb;
+    unit_of(u, ncb, r, cb);
+    const int32_t c = cb * 4, n = cols - c < 4 ? cols - c : 4;
+    uint32_t w[4];
+    dropout_words(key, row0 + uint64_t(r), uint32_t(cb), w);
+    uint8_t *dst = mask + r * ldm + c;
+    if (VEC && n == 4) {
+      const uint32_t packed = (w[0] < threshold ? 1u : 0u) | (w[1] < threshold ? 0x100u : 0u) | (w[2] < threshold ? 0x10000u : 0u) |
+                              (w[3] < threshold ? 0x1000000u : 0u);      // little-endian: byte j = column c + j
+      *reinterpret_cast<uint32_t *>(dst) = packed;
+    } else {
+      for (int j = 0; j < n; ++j) dst[j] = w[j] < threshold ? 1 : 0;
+    }
+  }
+}
+
+inline unsigned grid_for(int64_t units) {
+  const int64_t blocks = (units + TPB - 1) / TPB;
+  return unsigned(blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS);
+}
+
+// what every entry checks of the block's shape; MGCN_OK, or the code with the message set
+int check_block(const char *what, int64_t rows, int32_t cols) {
+  MGCN_REQUIRE(rows >= 0 && cols >= 1, "%s: bad sizes (rows = %lld, cols = %d)", what, (long long)rows, cols);
+  MGCN_REQUIRE(rows <= MAX_ROWS, "%s: more than 2^40 rows", what);      // (rows x column blocks: bounded by check_matrix's rows x ld)
+  return MGCN_OK;
+}
+
+// a matrix of the block: non-null, ld >= cols, and rows x ld elements addressable in 64-bit arithmetic with room to spare
+int check_matrix(const char *what, const char *name, const void *p, int64_t ld, int64_t rows, int32_t cols) {
+  MGCN_REQUIRE(p, "%s: null pointer (%s)", what, name);
+  MGCN_REQUIRE(ld >= cols, "%s: leading dimension of %s (%lld) smaller than cols = %d", what, name, (long long)ld, cols);
+  MGCN_REQUIRE(ld <= (int64_t(1) << 60) / (rows > 0 ? rows : 1), "%s: rows x leading dimension of %s exceeds 2^60 elements", what, name);
+  return MGCN_OK;
+}
+
+// an output may be its own input only as the same matrix: same pointer, same leading dimension
+int check_alias(const char *what, const float *x, int64_t ldx, const float *out, int64_t ldo) {
+  MGCN_REQUIRE(x != out || ldx == ldo, "%s: in place needs the same leading dimension (%lld, %lld)", what, (long long)ldx, (long long)ldo);
+  return MGCN_OK;
+}
+
+inline bool vec_ok(const void *p, int64_t ld) { return mgcn::aligned16(p) && ld % 4 == 0; }
+
+}  // namespace
+
+extern "C" int mgcn_dropout_apply(int64_t rows, int32_t cols, const float *x_dev, int64_t ldx, float *out_dev, int64_t ldo, uint64_t key,
+                                  uint64_t row0, uint32_t threshold, float inv_keep, void *stream) {
+  const char *what = "mgcn_dropout_apply";
+  if (int rc = check_block(what, rows, cols)) return rc;
+  if (int rc = check_matrix(what, "x", x_dev, ldx, rows, cols)) return rc;
+  if (int rc = check_matrix(what, "out", out_dev, ldo, rows, cols)) return rc;
+  if (int rc = check_alias(what, x_dev, ldx, out_dev, ldo)) return rc;
+  MGCN_REQUIRE(std::isfinite(inv_keep) && inv_keep >= 0.f, "%s: inv_keep must be a finite number >= 0", what);
+  if (rows == 0) return MGCN_OK;
+  const int32_t ncb = (cols + 3) / 4;
+  const Site s = {x_dev, ldx, out_dev, ldo, key};
+  const dim3 grid(grid_for(rows * ncb)), block(TPB);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (vec_ok(x_dev, ldx) && vec_ok(out_dev, ldo))
+    apply_kernel<1, true><<<grid, block, 0, st>>>(rows, cols, ncb, s, s, row0, threshold, inv_keep);
+  else
+    apply_kernel<1, false><<<grid, block, 0, st>>>(rows, cols, ncb, s, s, row0, threshold, inv_keep);
+  MGCN_CHECK_LAUNCH(what);
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_dropout_apply_pair(int64_t rows, int32_t cols, const float *xa_dev, int64_t ldxa, float *outa_dev, int64_t ldoa,
+                                       uint64_t key_a, const float *xb_dev, int64_t ldxb, float *outb_dev, int64_t ldob, uint64_t key_b,
+                                       uint64_t row0, uint32_t threshold, float inv_keep, void *stream) {
+  const char *what = "mgcn_dropout_apply_pair";
+  if (int rc = check_block(what, rows, cols)) return rc;
+  if (int rc = check_matrix(what, "x_a", xa_dev, ldxa, rows, cols)) return rc;
+  if (int rc = check_matrix(what, "out_a", outa_dev, ldoa, rows, cols)) return rc;
+  if (int rc = check_matrix(what, "x_b", xb_dev, ldxb, rows, cols)) return rc;
+  if (int rc = check_matrix(what, "out_b", outb_dev, ldob, rows, cols)) return rc;
+  if (int rc = check_alias(what, xa_dev, ldxa, outa_dev, ldoa)) return rc;
+  if (int rc = check_alias(what, xb_dev, ldxb, outb_dev, ldob)) return rc;
+  MGCN_REQUIRE(outa_dev != outb_dev, "%s: the two outputs are the same matrix", what);
+  // an output that is the OTHER site's input is read by the lane that writes it (reads come first), but only as the same matrix
+  if (int rc = check_alias(what, xa_dev, ldxa, outb_dev, ldob)) return rc;
+  if (int rc = check_alias(what, xb_dev, ldxb, outa_dev, ldoa)) return rc;
+  MGCN_REQUIRE(std::isfinite(inv_keep) && inv_keep >= 0.f, "%s: inv_keep must be a finite number >= 0", what);
+  if (rows == 0) return MGCN_OK;
+  const int32_t ncb = (cols + 3) / 4;
+  const Site a = {xa_dev, ldxa, outa_dev, ldoa, key_a}, b = {xb_dev, ldxb, outb_dev, ldob, key_b};
+  const dim3 grid(grid_for(rows * ncb)), block(TPB);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (vec_ok(xa_dev, ldxa) && vec_ok(outa_dev, ldoa) && vec_ok(xb_dev, ldxb) && vec_ok(outb_dev, ldob))
+    apply_kernel<2, true><<<grid, block, 0, st>>>(rows, cols, ncb, a, b, row0, threshold, inv_keep);
+  else
+    apply_kernel<2, false><<<grid, block, 0, st>>>(rows, cols, ncb, a, b, row0, threshold, inv_keep);
+  MGCN_CHECK_LAUNCH(what);
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_dropout_mask(int64_t rows, int32_t cols, uint8_t *mask_dev, int64_t ldm, uint64_t key, uint64_t row0,
+                                 uint32_t threshold, void *stream) {
+  const char *what = "mgcn_dropout_mask";
+  if (int rc = check_block(what, rows, cols)) return rc;
+  if (int rc = check_matrix(what, "mask", mask_dev, ldm, rows, cols)) return rc;
+  if (rows == 0) return MGCN_OK;
+  const int32_t ncb = (cols + 3) / 4;
+  const dim3 grid(grid_for(rows * ncb)), block(TPB);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if ((reinterpret_cast<uintptr_t>(mask_dev) & 3u) == 0 && ldm % 4 == 0)
+    mask_kernel<true><<<grid, block, 0, st>>>(rows, cols, ncb, mask_dev, ldm, key, row0, threshold);
+  else
+    mask_kernel<false><<<grid, block, 0, st>>>(rows, cols, ncb, mask_dev, ldm, key, row0, threshold);
+  MGCN_CHECK_LAUNCH(what);
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_dropout_mask_host(int64_t rows, int32_t cols, uint8_t *mask_host, int64_t ldm, uint64_t key, uint64_t row0,
+                                      uint32_t threshold) {
+  const char *what = "mgcn_dropout_mask_host";
+  if (int rc = check_block(what, rows, cols)) return rc;
+  if (int rc = check_matrix(what, "mask", mask_host, ldm, rows, cols)) return rc;
+  const int32_t ncb = (cols + 3) / 4;
+  for (int64_t r = 0; r < rows; ++r)
+    for (int32_t cb = 0; cb < ncb; ++cb) {
+      uint32_t w[4];
+      dropout_words(key, row0 + uint64_t(r), uint32_t(cb), w);
+      const int32_t c = cb * 4, n = cols - c < 4 ? cols - c : 4;
+      for (int j = 0; j < n; ++j) mask_host[r * ldm + c + j] = w[j] < threshold ? 1 : 0;
+    }
+  return MGCN_OK;
+}

@@ -488,16 +488,23 @@ class _ShardAggregateFn(torch.autograd.Function):
 class _ShardLayerTrainFn(torch.autograd.Function):
     """model._LayerTrainFn on this rank's rows with GLOBAL batch statistics: the BN reductions run in the split stages of
     csrc/train_layer.hip (4s) and every rank's per-block partials are all-gathered between them (forward: column sums, then
-    centred sums; backward: the g_pre / g_pre * xhat sums). Dropout keep-masks are the rank's own for its rows."""
+    centred sums; backward: the g_pre / g_pre * xhat sums). Dropout keep-masks are the rank's own for its rows, or, with
+    `drop_keys` = (key_in, key_out, row0 = n0), the counter-based ones of csrc/dropout.hip: the bits of the GLOBAL rows, the same
+    on any partition, recomputed in the backward instead of saved."""
 
     @staticmethod
-    def forward(ctx, agg, a_loop, w_in, w_out, w_loop, bias, gamma, beta, running_mean, running_var, momentum, eps, p_drop, ex):
+    def forward(ctx, agg, a_loop, w_in, w_out, w_loop, bias, gamma, beta, running_mean, running_var, momentum, eps, p_drop, ex,
+                drop_keys=None):
         d = w_in.size(0)
         u_in, u_out = _mm(agg[:, :d], w_in.contiguous()), _mm(agg[:, d:], w_out.contiguous())
         u_loop = _mm(a_loop.contiguous(), w_loop.contiguous())
         m_in = m_out = None
         ctx.inv_keep = 1.0
-        if p_drop >= 1.0:
+        ctx.drop = None
+        if drop_keys is not None and p_drop > 0:
+            ctx.drop = (int(drop_keys[0]), int(drop_keys[1]), int(drop_keys[2]), float(p_drop))
+            _native.dropout_apply_pair(u_in, ctx.drop[0], u_out, ctx.drop[1], ctx.drop[2], ctx.drop[3], out_a=u_in, out_b=u_out)
+        elif p_drop >= 1.0:
             m_in = torch.zeros(u_in.shape, dtype=torch.bool, device=u_in.device)
             m_out, ctx.inv_keep = m_in, 0.0
             u_in, u_out = torch.zeros_like(u_in), torch.zeros_like(u_out)
@@ -522,8 +529,11 @@ class _ShardLayerTrainFn(torch.autograd.Function):
         gy = gy.contiguous()
         parts = ctx.ex.gather_blocks(_native.bn_train_bwd_stage_sums(z, y, gy, mean, rstd))
         gz, gu, ggamma, gbeta = _native.bn_train_bwd_stage_apply(z, y, gy, mean, rstd, gamma, parts[0], parts[1], ctx.ex.total)
-        g_in = (gu * m_in).mul_(ctx.inv_keep) if m_in is not None else gu
-        g_out = (gu * m_out).mul_(ctx.inv_keep) if m_out is not None else gu
+        if ctx.drop is not None:
+            g_in, g_out = _native.dropout_apply_pair(gu, ctx.drop[0], gu, ctx.drop[1], ctx.drop[2], ctx.drop[3])
+        else:
+            g_in = (gu * m_in).mul_(ctx.inv_keep) if m_in is not None else gu
+            g_out = (gu * m_out).mul_(ctx.inv_keep) if m_out is not None else gu
         need = ctx.needs_input_grad
         g_agg = g_loop = g_win = g_wout = g_wloop = None
         if need[0]:
@@ -537,7 +547,7 @@ class _ShardLayerTrainFn(torch.autograd.Function):
         if need[4]:
             g_wloop = _mm_tn(a_loop.contiguous(), gu)
         g_bias = gz.sum(0) if (ctx.has_bias and need[5]) else None
-        return g_agg, g_loop, g_win, g_wout, g_wloop, g_bias, ggamma, gbeta, None, None, None, None, None, None
+        return g_agg, g_loop, g_win, g_wout, g_wloop, g_bias, ggamma, gbeta, None, None, None, None, None, None, None
 
 
 class _GatherRowsFn(torch.autograd.Function):
@@ -766,10 +776,19 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
     GLOBAL batch statistics, applies its own dropout masks to its rows and all-gathers the rows; every rank runs the ConvE trunk
     on the whole batch and scores its own entities (global mean); the backward reduces each gradient once — the trunk's input
     gradient and every inner layer output's by all-reduce inside the backward, all replicated parameters in one flat bucket
-    after it; the table shards' gradients stay local. The trunk's dropout masks must be the same on every rank: they come from
-    `generator` (a torch.Generator on the device, seeded identically on every rank) or, without one at W > 1, from a per-step
-    generator seeded from a fresh seed the group agrees on. With one rank the step computes what forward_loss + backward +
-    clip_grad_norm_ + step compute, bit for bit (dropout 0). Returns the global loss (0-dim tensor, detached)."""
+    after it; the table shards' gradients stay local.
+
+    Dropout. By default (params.dropout = 'torch') the layer masks are each rank's own draws for its rows, and the trunk's masks,
+    which must be the same on every rank, come from `generator` (a torch.Generator on the device, seeded identically on every
+    rank) or, without one at W > 1, from a per-step generator seeded from a fresh seed the group agrees on; with one rank the
+    step then computes what forward_loss + backward + clip_grad_norm_ + step compute bit for bit only at dropout 0.
+    With params.dropout = 'counter' (or MGCN_DROPOUT=counter) every keep bit is a pure function of (model.dropout_seed,
+    model.dropout_step, site, global row, column): the rank's layer rows and gcn_drop take row0 = n0, every rank
+    derives the same trunk keys, so no generator is read and no seed is exchanged (`generator` is ignored), and the masks do not
+    depend on the partition. The call uses the current step for all its sites and then increments it, as one training-mode
+    MGCN.encode does; every rank must hold the same (dropout_seed, dropout_step). With one rank the step then equals
+    forward_loss + backward + clip_grad_norm_ + step bit for bit AT ANY DROPOUT.
+    Returns the global loss (0-dim tensor, detached)."""
     import torch.nn.functional as F
     csr, ex = _sharded_setup(model, graph, group, 'train_step_sharded')
     n0, n1, W = ex.n0, ex.n1, ex.world
@@ -783,6 +802,7 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
                 _native.matmul_tn_supported(layer.in_channels, layer.out_channels)):
             raise _native.NativeError('train_step_sharded: layer %s is outside the HIP training path' % (layer,))
     x, rel_e = model.entity_embedding, model.relation_embedding
+    drop_ctx = model._begin_dropout_step()       # (seed, step) with the counter-based dropout on, else None
     for li, (layer, table) in enumerate(zip(layers, tables)):
         last = li == len(layers) - 1
         bn = layer.ent_bn
@@ -791,14 +811,22 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
         x_own = x if (n0, n1) == (0, x.size(0)) else x[n0:n1]
         a_loop = (x_own * rels[-1]) * layer.loop_edge
         y = _ShardLayerTrainFn.apply(agg, a_loop, layer.in_weight, layer.out_weight, layer.loop_weight, layer.bias, bn.weight,
-                                     bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, layer.drop.p, ex)
+                                     bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, layer.drop.p, ex,
+                                     None if drop_ctx is None else
+                                     tuple(_native.dropout_key(drop_ctx[0], drop_ctx[1], _native.dropout_layer_site(li, w)) for w in (0, 1)) + (n0,))
         with torch.no_grad():
             bn.num_batches_tracked += 1
         rel_e = torch.matmul(_RankZeroGradFn.apply(rels, ex) if (last and W > 1) else rels, layer.rels_weight)[:-1]
-        y = F.dropout(y, p=model.params.gcn_drop, training=True)
+        if drop_ctx is not None:
+            from .model import counter_dropout
+            y = counter_dropout(y, model.params.gcn_drop, drop_ctx[0], drop_ctx[1], _native.dropout_layer_site(li, 2), row0=n0)
+        else:
+            y = F.dropout(y, p=model.params.gcn_drop, training=True)
         x = _GatherRowsFn.apply(y, ex, not last) if W > 1 else y
     ent = y.contiguous()
-    if W > 1 and generator is None and (model.conv2.feature_drop.p > 0 or model.conv2.hidden_drop.p > 0):
+    if drop_ctx is not None:
+        generator = None         # the trunk finds (seed, step) in conv2._drop_ctx: the same keys on every rank
+    elif W > 1 and generator is None and (model.conv2.feature_drop.p > 0 or model.conv2.hidden_drop.p > 0):
         generator = torch.Generator(device=ent.device)
         generator.manual_seed(_agreed_seed(group, ent.device))
     from .model import query_rows

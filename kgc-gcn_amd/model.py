@@ -8,7 +8,8 @@ What runs where
   * eval-mode layer (model.py:99-107): ONE launch, aggregation + dense step (six bf16-split MFMA products, f32-faithful)
     + /3, bias, BN, tanh (csrc/layer_fused3.hip); shapes it does not take: aggregation launch + exact-f32 MFMA dense
     launch (csrc/dense.hip). In training mode (batch statistics, dropout) the products, the BN reductions, tanh and
-    their backward run on csrc/train_layer.hip kernels behind torch.autograd.Function (only the dropout masks are torch's);
+    their backward run on csrc/train_layer.hip kernels behind torch.autograd.Function (the dropout masks are torch's, or, with
+    params.dropout = 'counter' (or MGCN_DROPOUT=counter), the counter-based ones of csrc/dropout.hip at all five sites of the step);
   * full-graph scoring (model.py:177-179) and the filtered rank counts (main.py:122-126): HIP;
   * the ConvE conv trunk (model.py:161-175): stock torch modules (MIOpen / rocBLAS) by default; with
     params.conve_trunk = 'hip' (or MGCN_TRUNK=hip) the eval-mode trunk is ONE HIP launch from the two tables to x (csrc/conve_trunk.hip);
@@ -58,17 +59,24 @@ class _LayerTrainFn(torch.autograd.Function):
     y = tanh(BN_batch((drop(A_in W_in) + drop(A_out W_out) + A_loop W_loop) / 3 (+ bias))). Products on the f32 MFMA
     kernels (forward A W, backward g W^T and the split-K A^T g), batch statistics / normalisation / tanh and their
     backward on the two-stage reduction kernels of csrc/train_layer.hip; the running statistics are updated in place.
-    Dropout masks come from torch's generator (Bernoulli keep-masks scaled by 1 / keep, as F.dropout)."""
+    Dropout masks come from torch's generator (Bernoulli keep-masks scaled by 1 / keep, as F.dropout), or, with `drop_keys` =
+    (key_in, key_out, row0), from the counter-based definition of csrc/dropout.hip: one pair launch in place on the
+    two products, no mask saved, and one pair launch in the backward that forms both gradients from gu."""
 
     @staticmethod
-    def forward(ctx, agg, a_loop, w_in, w_out, w_loop, bias, gamma, beta, running_mean, running_var, momentum, eps, p_drop):
+    def forward(ctx, agg, a_loop, w_in, w_out, w_loop, bias, gamma, beta, running_mean, running_var, momentum, eps, p_drop,
+                drop_keys=None):
         d = w_in.size(0)
         u_in, u_out = _native.matmul(agg[:, :d], w_in.contiguous()), _native.matmul(agg[:, d:], w_out.contiguous())
         u_loop = _native.matmul(a_loop.contiguous(), w_loop.contiguous())
         # dropout keep-masks are saved as bool (1 byte per element, not a scaled f32 copy) and scaled by 1 / keep at use
         m_in = m_out = None
         ctx.inv_keep = 1.0
-        if p_drop >= 1.0:                       # F.dropout(p=1) is all zeros (1 / keep would be 0 / 0)
+        ctx.drop = None
+        if drop_keys is not None and p_drop > 0:      # counter-based: the bits are recomputed in the backward, nothing is saved
+            ctx.drop = (int(drop_keys[0]), int(drop_keys[1]), int(drop_keys[2]), float(p_drop))
+            _native.dropout_apply_pair(u_in, ctx.drop[0], u_out, ctx.drop[1], ctx.drop[2], ctx.drop[3], out_a=u_in, out_b=u_out)
+        elif p_drop >= 1.0:                       # F.dropout(p=1) is all zeros (1 / keep would be 0 / 0)
             m_in = torch.zeros(u_in.shape, dtype=torch.bool, device=u_in.device)
             m_out, ctx.inv_keep = m_in, 0.0
             u_in, u_out = torch.zeros_like(u_in), torch.zeros_like(u_out)
@@ -89,8 +97,11 @@ class _LayerTrainFn(torch.autograd.Function):
         agg, a_loop, w_in, w_out, w_loop, gamma, z, y, mean, rstd, m_in, m_out = ctx.saved_tensors
         d = w_in.size(0)
         gz, gu, ggamma, gbeta = _native.bn_tanh_train_bwd(z, y, gy, mean, rstd, gamma)
-        g_in = (gu * m_in).mul_(ctx.inv_keep) if m_in is not None else gu
-        g_out = (gu * m_out).mul_(ctx.inv_keep) if m_out is not None else gu
+        if ctx.drop is not None:
+            g_in, g_out = _native.dropout_apply_pair(gu, ctx.drop[0], gu, ctx.drop[1], ctx.drop[2], ctx.drop[3])
+        else:
+            g_in = (gu * m_in).mul_(ctx.inv_keep) if m_in is not None else gu
+            g_out = (gu * m_out).mul_(ctx.inv_keep) if m_out is not None else gu
         need = ctx.needs_input_grad
         g_agg = g_loop = g_win = g_wout = g_wloop = None
         if need[0]:
@@ -104,7 +115,7 @@ class _LayerTrainFn(torch.autograd.Function):
         if need[4]:
             g_wloop = _native.matmul_tn(a_loop.contiguous(), gu)
         g_bias = gz.sum(0) if (ctx.has_bias and need[5]) else None
-        return g_agg, g_loop, g_win, g_wout, g_wloop, g_bias, ggamma, gbeta, None, None, None, None, None
+        return g_agg, g_loop, g_win, g_wout, g_wloop, g_bias, ggamma, gbeta, None, None, None, None, None, None
 
 
 class _TrunkTrainFn(torch.autograd.Function):
@@ -197,6 +208,35 @@ def _drawn_dropout(x, p, generator):
         return x * 0.0
     keep = 1.0 - p
     return x * torch.empty_like(x).bernoulli_(keep, generator=generator) * (1.0 / keep)
+
+
+def _counter_dropout_wanted(params):
+    """The switch of the counter-based dropout: params.dropout == 'counter', overridden in both directions by the environment
+    variable MGCN_DROPOUT ('counter' or 'torch')."""
+    return (os.environ.get('MGCN_DROPOUT') or getattr(params, 'dropout', 'torch')) == 'counter'
+
+
+class _CounterDropoutFn(torch.autograd.Function):
+    """Dropout of a matrix [rows, cols] whose keep bits are the counter-based ones of csrc/dropout.hip: a pure
+    function of (key, row0 + row, col). Forward and backward are the same launch; nothing is saved but the scalars."""
+
+    @staticmethod
+    def forward(ctx, x, key, row0, p):
+        ctx.args = (int(key), int(row0), float(p))
+        x = x if _native.dropout_supported(x) else x.contiguous()
+        return _native.dropout_apply(x, *ctx.args)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g if _native.dropout_supported(g) else g.contiguous()
+        return _native.dropout_apply(g, *ctx.args), None, None, None
+
+
+def counter_dropout(x, p, seed, step, site, row0=0):
+    """x [rows, cols] through the counter-based dropout of site `site` at (seed, step); p <= 0 launches nothing."""
+    if p <= 0 or x.numel() == 0:
+        return x
+    return _CounterDropoutFn.apply(x, _native.dropout_key(seed, step, site), row0, p)
 
 
 class _ScoreFn(torch.autograd.Function):
@@ -304,10 +344,12 @@ class MGCNConv(nn.Module):
         return inv[row] * inv[col]
 
     def forward(self, x, edge_index, edge_type, edge_norm, edge_embs, rels_embs, size=None, csr=None,
-                ee_in_slot_order=False):
+                ee_in_slot_order=False, drop_keys=None):
         """Returns (all_ent [N, O], all_rel [2R, O]). `edge_norm` is ignored, as in the reference (Q1).
         `csr` / `ee_in_slot_order` are the fast-path hand-over from MGCN.forward: the graph's cached CSR and a
-        per-edge table already laid out in slot order."""
+        per-edge table already laid out in slot order. `drop_keys` = (key_in, key_out, row0), handed over by MGCN with the
+        counter-based dropout on: the training-mode masks of in_res / out_res are then those of csrc/dropout.hip; without it
+        (a layer used on its own) they are torch's."""
         num_ent = x.size(0)
         if csr is None:
             csr = csr_for_tensors(num_ent, rels_embs.size(0) + 1, edge_index, edge_type)
@@ -351,14 +393,19 @@ class MGCNConv(nn.Module):
             a_loop = (x * rels[-1]) * self.loop_edge
             all_ent = _LayerTrainFn.apply(agg, a_loop, self.in_weight, self.out_weight, self.loop_weight, self.bias, bn.weight,
                                           bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
-                                          self.drop.p if self.training else 0.0)
+                                          self.drop.p if self.training else 0.0, drop_keys if self.training else None)
             with torch.no_grad():
                 bn.num_batches_tracked += 1
             return all_ent, torch.matmul(rels, self.rels_weight)[:-1]
         in_res = agg[:, :d] @ self.in_weight
         out_res = agg[:, d:] @ self.out_weight
         loop_res = ((x * rels[-1]) * self.loop_edge) @ self.loop_weight
-        out = (self.drop(in_res) + self.drop(out_res) + loop_res) / 3
+        if drop_keys is not None and self.training and self.drop.p > 0:
+            in_res = _CounterDropoutFn.apply(in_res, drop_keys[0], drop_keys[2], self.drop.p)
+            out_res = _CounterDropoutFn.apply(out_res, drop_keys[1], drop_keys[2], self.drop.p)
+            out = (in_res + out_res + loop_res) / 3
+        else:
+            out = (self.drop(in_res) + self.drop(out_res) + loop_res) / 3
         if self.bias is not None:
             out = out + self.bias
         all_ent = self.act(self.ent_bn(out))
@@ -449,13 +496,21 @@ class ConvE(nn.Module):
             return False
         return _native.conve_train_supported(src_emb.size(0), self._geometry())
 
-    def _trunk_train(self, src_emb, rel_emb, generator):
+    def _counter_keep(self, drop_ctx, site, shape, p, device):
+        """(bool keep-mask, inv_keep) of a trunk site from the counter-based definition (row = batch row): what the kernels of
+        csrc/conve_train.hip and csrc/query_train.hip take in place of a bernoulli_ draw."""
+        key = _native.dropout_key(drop_ctx[0], drop_ctx[1], site)
+        return _native.dropout_mask(shape[0], shape[1], key, 0, p, device=device), _native.dropout_scale(p)[1]
+
+    def _trunk_train(self, src_emb, rel_emb, generator, drop_ctx=None):
         src_emb = src_emb if src_emb.stride(1) == 1 else src_emb.contiguous()
         rel_emb = rel_emb if rel_emb.stride(1) == 1 else rel_emb.contiguous()
         # the feature mask is drawn first, then the hidden one: dist._dropout's draws, on tensors of the activations' shapes
         p, keep, inv_keep = self.feature_drop.p, None, 1.0
         shape = (src_emb.size(0), self.flat_sz)
-        if p >= 1:
+        if drop_ctx is not None and p > 0:
+            keep, inv_keep = self._counter_keep(drop_ctx, _native.DROPOUT_SITE_FEATURE, shape, p, src_emb.device)
+        elif p >= 1:
             keep, inv_keep = torch.zeros(shape, dtype=torch.bool, device=src_emb.device), 0.0
         elif p > 0:
             keep = torch.empty(shape, dtype=torch.float32, device=src_emb.device).bernoulli_(1.0 - p, generator=generator).bool()
@@ -468,7 +523,7 @@ class ConvE(nn.Module):
             bn0.num_batches_tracked += 1
             bn1.num_batches_tracked += 1
         self._trunk_train_count = getattr(self, '_trunk_train_count', 0) + 1
-        return self._tail(z, generator, True)
+        return self._tail(z, generator, True, drop_ctx)
 
     def _hip_tail(self, z):
         """Whether this call takes the HIP tail: the switch (params.query_path_train == 'hip', overridden in both directions by
@@ -484,14 +539,17 @@ class ConvE(nn.Module):
             return False
         return _native.conve_tail_supported(z.size(0), z.size(1))
 
-    def _tail(self, z, generator, drawn):
+    def _tail(self, z, generator, drawn, drop_ctx=None):
         """relu(bn2(hidden_drop(z))), the trunk after fc whichever conv block ran. `drawn`: the torch path draws its mask with
         bernoulli_ from `generator` (_drawn_dropout) instead of calling hidden_drop. On the HIP tail the mask is always drawn with
-        bernoulli_(1 - p, generator=generator) on an f32 [B, O] tensor, after the feature mask: dist._trunk's draws."""
+        bernoulli_(1 - p, generator=generator) on an f32 [B, O] tensor, after the feature mask: dist._trunk's draws. With
+        `drop_ctx` = (seed, step) the hidden mask is the counter-based one of site 0x1001 on either path, and no generator is read."""
         if self._hip_tail(z):
             z = z if z.stride(1) == 1 else z.contiguous()
             p, keep, inv_keep = self.hidden_drop.p, None, 1.0
-            if p >= 1:
+            if drop_ctx is not None and p > 0:
+                keep, inv_keep = self._counter_keep(drop_ctx, _native.DROPOUT_SITE_HIDDEN, tuple(z.shape), p, z.device)
+            elif p >= 1:
                 keep, inv_keep = torch.zeros(z.shape, dtype=torch.bool, device=z.device), 0.0
             elif p > 0:
                 keep = torch.empty(z.shape, dtype=torch.float32, device=z.device).bernoulli_(1.0 - p, generator=generator).bool()
@@ -502,7 +560,10 @@ class ConvE(nn.Module):
                 bn.num_batches_tracked += 1
             self._tail_train_count = getattr(self, '_tail_train_count', 0) + 1
             return x
-        x = _drawn_dropout(z, self.hidden_drop.p, generator) if drawn else self.hidden_drop(z)
+        if drop_ctx is not None:
+            x = counter_dropout(z, self.hidden_drop.p, drop_ctx[0], drop_ctx[1], _native.DROPOUT_SITE_HIDDEN)
+        else:
+            x = _drawn_dropout(z, self.hidden_drop.p, generator) if drawn else self.hidden_drop(z)
         return F.relu(self.bn2(x)).contiguous()
 
     def trunk(self, src_emb, rel_emb, generator=None):
@@ -512,9 +573,15 @@ class ConvE(nn.Module):
         from the same generator state, but not the stream F.dropout itself would consume. With params.query_path_train == 'hip'
         (or MGCN_QUERY_TRAIN=hip) the tail hidden_drop -> bn2 -> relu runs on csrc/query_train.hip after either conv block, and its
         hidden mask is drawn the same way, bernoulli_ on a [B, O] tensor from `generator`: after the torch conv block (whose
-        feature_drop is still F.dropout) that is again not the stream F.dropout would consume. `generator` is not used otherwise."""
+        feature_drop is still F.dropout) that is again not the stream F.dropout would consume. `generator` is not used otherwise.
+        With the counter-based dropout on, MGCN leaves (seed, step) in `_drop_ctx` for the one training-mode call that follows its
+        encoder: both masks are then those of csrc/dropout.hip (sites 0x1000 and 0x1001, row = batch row) on every path, and no
+        generator is read. A ConvE used on its own has no such context and keeps the paths above."""
+        drop_ctx, self._drop_ctx = getattr(self, '_drop_ctx', None), None
+        if not self.training or not src_emb.is_cuda:
+            drop_ctx = None
         if self._hip_trunk_train(src_emb, rel_emb):
-            return self._trunk_train(src_emb, rel_emb, generator)
+            return self._trunk_train(src_emb, rel_emb, generator, drop_ctx)
         if self._hip_trunk(src_emb, rel_emb) and src_emb.dim() == 2 and src_emb.shape == rel_emb.shape \
                 and src_emb.size(1) == self.params.gcn_out_dim:
             src_emb = src_emb if src_emb.stride(1) == 1 else src_emb.contiguous()
@@ -523,8 +590,12 @@ class ConvE(nn.Module):
         o = self.params.gcn_out_dim
         stack = torch.cat([src_emb.view(-1, 1, o), rel_emb.view(-1, 1, o)], dim=1)
         stack = stack.transpose(2, 1).reshape(-1, 1, 2 * self.params.k_w, self.params.k_h)
-        x = self.feature_drop(F.relu(self.bn1(self.conv_e(self.bn0(stack)))))
-        return self._tail(self.fc(x.view(-1, self.flat_sz)), generator, False)
+        x = F.relu(self.bn1(self.conv_e(self.bn0(stack))))
+        if drop_ctx is not None:      # the feature site's row is the batch row, its columns the flat_sz features of that row
+            x = counter_dropout(x.reshape(-1, self.flat_sz), self.feature_drop.p, drop_ctx[0], drop_ctx[1], _native.DROPOUT_SITE_FEATURE)
+        else:
+            x = self.feature_drop(x)
+        return self._tail(self.fc(x.view(-1, self.flat_sz)), generator, False, drop_ctx)
 
     def trunk_indexed(self, all_ent, src, all_rel, rel):
         """trunk(all_ent[src], all_rel[rel]); on the HIP trunk the rows are gathered inside the kernel."""
@@ -565,6 +636,10 @@ class MGCN(nn.Module):
         self.conv1_extra = nn.ModuleList(
             [MGCNConv(params.gcn_out_dim, params.gcn_out_dim, num_relations * 2) for _ in range(extra)])
         self.edge_embeddings_extra = nn.ParameterList([table(params.gcn_out_dim) for _ in range(extra)])
+        # counter-based dropout (params.dropout = 'counter'): plain Python ints, NOT buffers (the state dict's key set is
+        # the reference's); dropout_state() / load_dropout_state() carry them in a checkpoint
+        self.dropout_seed = int(getattr(params, 'dropout_seed', 0))
+        self.dropout_step = 0
         self._optimizers = weakref.WeakSet()   # optimizers whose per-row state follows the tables' layout (attach_optimizer)
         self._edge_shard = None    # (csr, n0, n1) once dist.shard_model_tables has filled a partial table
         self._slot_csr = None      # per-edge tables are stored in this CSR's slot order (None = reference order)
@@ -689,6 +764,26 @@ class MGCN(nn.Module):
                         if torch.is_tensor(v) and v.dim() > 0 and v.size(0) == p.size(0):
                             st[k] = v.index_select(0, perm.to(v.device)).contiguous()
 
+    # -- counter-based dropout -----------------------------------------------------------------
+    def dropout_state(self):
+        """What a checkpoint stores beside state_dict() so that a resumed run draws the masks the uninterrupted run would."""
+        return {'dropout_seed': int(self.dropout_seed), 'dropout_step': int(self.dropout_step)}
+
+    def load_dropout_state(self, d):
+        self.dropout_seed, self.dropout_step = int(d['dropout_seed']), int(d['dropout_step'])
+
+    def _begin_dropout_step(self):
+        """(seed, step) for ONE training-mode encode / train_step_sharded call with the counter-based dropout on, else None: every
+        site of the call, the trunk's included, uses this step; the step counter then advances. The ConvE trunk finds the pair in
+        conv2._drop_ctx and consumes it."""
+        if not self.training or not _counter_dropout_wanted(self.params) or not self.entity_embedding.is_cuda:
+            self.conv2._drop_ctx = None
+            return None
+        ctx = (self.dropout_seed, self.dropout_step)
+        self.dropout_step += 1
+        self.conv2._drop_ctx = ctx
+        return ctx
+
     # -- encoder ---------------------------------------------------------------------------------
     def _graph_facts(self, data):
         facts = getattr(data, '_mgcn_facts', None)
@@ -726,7 +821,7 @@ class MGCN(nn.Module):
 
         frozen = not self.training and not torch.is_grad_enabled()
         if not frozen:
-            return self._encode_layers(data, csr, ent_identity, edge_identity)
+            return self._encode_layers(data, csr, ent_identity, edge_identity, self._begin_dropout_step())
 
         tensors = self._encoder_tensors()
         use_cache = getattr(self.params, 'cache_encoder', True)
@@ -741,17 +836,23 @@ class MGCN(nn.Module):
             self._enc_cache = (stamp, out[0], out[1])
         return out
 
-    def _encode_layers(self, data, csr, ent_identity, edge_identity):
+    def _encode_layers(self, data, csr, ent_identity, edge_identity, drop_ctx=None):
         edge_type, edge_ids = data.edge_attr
         x = self.entity_embedding if ent_identity else torch.index_select(self.entity_embedding, 0, data.entity)
         rel = self.relation_embedding
         layers = [self.conv1] + list(self.conv1_extra)
         tables = [self.edge_embeddings] + list(self.edge_embeddings_extra)
-        for layer, table in zip(layers, tables):
+        for li, (layer, table) in enumerate(zip(layers, tables)):
             ee = table if edge_identity else torch.index_select(table, 0, edge_ids)
+            keys = None
+            if drop_ctx is not None:      # counter-based masks: rows are entity ids, the whole graph starts at row 0
+                keys = tuple(_native.dropout_key(drop_ctx[0], drop_ctx[1], _native.dropout_layer_site(li, w)) for w in (0, 1)) + (0,)
             x, rel = layer(x, data.edge_index, edge_type, getattr(data, 'edge_norm', None), ee, rel, csr=csr,
-                           ee_in_slot_order=edge_identity)
-            x = F.dropout(x, p=self.params.gcn_drop, training=self.training)
+                           ee_in_slot_order=edge_identity, drop_keys=keys)
+            if drop_ctx is not None:
+                x = counter_dropout(x, self.params.gcn_drop, drop_ctx[0], drop_ctx[1], _native.dropout_layer_site(li, 2))
+            else:
+                x = F.dropout(x, p=self.params.gcn_drop, training=self.training)
         return x, rel
 
     def _encode_replay(self, data, csr, ent_identity, edge_identity, tensors):

@@ -109,5 +109,7 @@ def load_checkpoint(checkpoint, model, optimizer=None):
             loader(optimizer, ckpt['optim_dict'])
         else:
             optimizer.load_state_dict(ckpt['optim_dict'])
+    if 'dropout_state' in ckpt and hasattr(model, 'load_dropout_state'):     # MGCN.dropout_state(): seed and step of the counter-based dropout
+        model.load_dropout_state(ckpt['dropout_state'])
     measure = ckpt.get('measure', None)
     return float(measure) if measure is not None else None
