@@ -626,6 +626,12 @@ int mgcn_conve_train_bwd(int32_t batch, int32_t k_w, int32_t k_h, int32_t kernel
  *   with step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) formed by the caller in double; coef is read from
  *   coef_dev (out_dev + 1 of the call above), NULL = 1. Gradients are read, never written. 16-byte accesses when the four
  *   bases of a tensor are 16-byte aligned, scalar accesses otherwise and for the last numel % 4 elements.
+ * mgcn_adam_step_dev: mgcn_adam_step with the two scalars that change from step to step read on the device: hyper_dev points to
+ *   two floats, step_size and bc2_sqrt (4-byte aligned), which every workgroup loads before it forms -step_size. With the same two
+ *   float values in memory every output bit equals mgcn_adam_step's. For a launch that is captured into a hipGraph once and
+ *   replayed: the host writes each step's pair (still formed in double and rounded to float) into that memory ahead of the
+ *   replay. Pointers, lengths, betas, eps and weight_decay still travel by value; the values in memory are not checked
+ *   (MGCN_EINVAL for a NULL or misaligned hyper_dev).
  * All checks precede the first launch and write nothing: MGCN_EINVAL for n < 0, a NULL array, a negative length, a live
  * tensor with a NULL p / m / v, a beta outside [0, 1), eps, weight_decay, max_norm or step_size (a negative lr) below 0 or
  * not a number, bc2_sqrt outside (0, 1], a NULL, misaligned or too small workspace; MGCN_EUNSUPPORTED for more than 2^31
@@ -640,6 +646,9 @@ int mgcn_adam_clip_coef(int64_t n, const float *sq_dev, float max_norm, float *o
 int mgcn_adam_step(int64_t n, const float *const *grad_host, float *const *param_host, float *const *exp_avg_host,
                    float *const *exp_avg_sq_host, const int64_t *numel_host, const float *coef_dev, float step_size,
                    float bc2_sqrt, double beta1, double beta2, double eps, double weight_decay, void *stream);
+int mgcn_adam_step_dev(int64_t n, const float *const *grad_host, float *const *param_host, float *const *exp_avg_host,
+                       float *const *exp_avg_sq_host, const int64_t *numel_host, const float *coef_dev, const float *hyper_dev,
+                       double beta1, double beta2, double eps, double weight_decay, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * (11) The training step's query path between the encoder and the scorer (csrc/query_train.hip): the backward of the two
@@ -727,6 +736,12 @@ int mgcn_conve_tail_bwd(int32_t batch, int32_t dim, const float *z_dev, int64_t 
  * mgcn_dropout_mask: the keep bytes (1 / 0) [rows, cols], rows ldm bytes apart: the bool masks (9) and (11) take.
  * mgcn_dropout_mask_host: the same bytes on the CPU from the SAME inline function the kernels call. Test infrastructure, like
  *   mgcn_csr_build_host's role for the layout; no model path calls it.
+ * mgcn_dropout_apply_dev, mgcn_dropout_apply_pair_dev, mgcn_dropout_mask_dev: the three device entry points above with the last
+ *   SplitMix64 step moved into the kernel: in place of each `key` they take the 64-bit site id, and step_key_dev points to ONE
+ *   64-bit word in device memory (8-byte aligned) that holds sm(sm(seed) ^ step); every lane forms key = sm(word ^ site). One
+ *   word serves all sites of a step. With the word of (seed, step) in memory every output bit equals the by-value entry point
+ *   called with key(seed, step, site). For launches captured into a hipGraph: the host rewrites the word ahead of each replay.
+ *   MGCN_EINVAL for a NULL or misaligned step_key_dev; everything else as the by-value forms.
  * One lane serves four columns with one Philox call; 16-byte accesses when every base pointer is 16-byte aligned and every leading
  * dimension a multiple of 4 (mask: 4-byte stores under the same rule for 4 bytes), the element-wise path with the same bits
  * otherwise. At most 2048 workgroups of 256 threads stride over the block; index arithmetic is 64-bit; no atomics, no LDS.
@@ -741,6 +756,13 @@ int mgcn_dropout_apply_pair(int64_t rows, int32_t cols, const float *xa_dev, int
                             uint64_t row0, uint32_t threshold, float inv_keep, void *stream);
 int mgcn_dropout_mask(int64_t rows, int32_t cols, uint8_t *mask_dev, int64_t ldm, uint64_t key, uint64_t row0, uint32_t threshold,
                       void *stream);
+int mgcn_dropout_apply_dev(int64_t rows, int32_t cols, const float *x_dev, int64_t ldx, float *out_dev, int64_t ldo,
+                           const uint64_t *step_key_dev, uint64_t site, uint64_t row0, uint32_t threshold, float inv_keep, void *stream);
+int mgcn_dropout_apply_pair_dev(int64_t rows, int32_t cols, const float *xa_dev, int64_t ldxa, float *outa_dev, int64_t ldoa,
+                                uint64_t site_a, const float *xb_dev, int64_t ldxb, float *outb_dev, int64_t ldob, uint64_t site_b,
+                                const uint64_t *step_key_dev, uint64_t row0, uint32_t threshold, float inv_keep, void *stream);
+int mgcn_dropout_mask_dev(int64_t rows, int32_t cols, uint8_t *mask_dev, int64_t ldm, const uint64_t *step_key_dev, uint64_t site,
+                          uint64_t row0, uint32_t threshold, void *stream);
 int mgcn_dropout_mask_host(int64_t rows, int32_t cols, uint8_t *mask_host, int64_t ldm, uint64_t key, uint64_t row0,
                            uint32_t threshold);
 

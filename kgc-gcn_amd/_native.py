@@ -88,6 +88,7 @@ _SIGNATURES = {
     'mgcn_adam_sq_norms': (ctypes.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_adam_clip_coef': (ctypes.c_int, [_i64, _ptr, _f32, _ptr, _ptr]),
     'mgcn_adam_step': (ctypes.c_int, [_i64] + [_ptr] * 6 + [_f32, _f32] + [ctypes.c_double] * 4 + [_ptr]),
+    'mgcn_adam_step_dev': (ctypes.c_int, [_i64] + [_ptr] * 7 + [ctypes.c_double] * 4 + [_ptr]),
     'mgcn_query_rows_bwd_workspace': (ctypes.c_size_t, [_i32]),
     'mgcn_query_rows_bwd': (ctypes.c_int, [_i32, _i64, _i32, _ptr, _ptr, _i64, _ptr, _i64, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_conve_tail_fwd': (ctypes.c_int, [_i32, _i32, _ptr, _i64, _ptr, _i64, _f32, _ptr, _ptr, _ptr, _ptr, _f32, _f32, _ptr, _i64, _ptr,
@@ -98,6 +99,10 @@ _SIGNATURES = {
     'mgcn_dropout_apply_pair': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _i64, _u64, _ptr, _i64, _ptr, _i64, _u64, _u64, _u32, _f32,
                                                _ptr]),
     'mgcn_dropout_mask': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _u64, _u64, _u32, _ptr]),
+    'mgcn_dropout_apply_dev': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _u64, _u64, _u32, _f32, _ptr]),
+    'mgcn_dropout_apply_pair_dev': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _i64, _u64, _ptr, _i64, _ptr, _i64, _u64, _ptr, _u64, _u32,
+                                                   _f32, _ptr]),
+    'mgcn_dropout_mask_dev': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _u64, _u64, _u32, _ptr]),
     'mgcn_dropout_mask_host': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _u64, _u64, _u32]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
@@ -1213,15 +1218,24 @@ def adam_clip_coef(sq, max_norm, out=None):
     return out
 
 
-def adam_step(grads, params, exp_avgs, exp_avg_sqs, coef, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay):
+def adam_step(grads, params, exp_avgs, exp_avg_sqs, coef, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, hyper_dev=None):
     """(10) One Adam update of the listed tensors in place; `coef`: a 1-element device tensor (None = no clipping). A None
-    or empty gradient skips its tensor."""
+    or empty gradient skips its tensor. `hyper_dev`: a contiguous f32 device tensor of two elements that holds (step_size,
+    bc2_sqrt); the kernels then read the pair from it when they RUN (mgcn_adam_step_dev: what a captured launch needs), and the two
+    by-value arguments are not used."""
     _adam_list('adam_step', [params, grads, exp_avgs, exp_avg_sqs])
-    _same_device(coef, *params)
+    _same_device(coef, hyper_dev, *params)
     n = len(params)
     if n == 0:
         return
     numel = (_i64 * n)(*[p.numel() for p in params])
+    if hyper_dev is not None:
+        if hyper_dev.numel() != 2 or not hyper_dev.is_contiguous():
+            raise NativeError('adam_step: hyper_dev must be a contiguous tensor of two floats (step_size, bc2_sqrt)')
+        _check(lib().mgcn_adam_step_dev(n, _ptr_array(grads), _ptr_array(params), _ptr_array(exp_avgs), _ptr_array(exp_avg_sqs), numel,
+                                        _dev(coef, torch.float32, 'coef', True), _dev(hyper_dev, torch.float32, 'hyper_dev'), float(beta1),
+                                        float(beta2), float(eps), float(weight_decay), _stream(params[0])), 'mgcn_adam_step_dev')
+        return
     _check(lib().mgcn_adam_step(n, _ptr_array(grads), _ptr_array(params), _ptr_array(exp_avgs), _ptr_array(exp_avg_sqs), numel,
                                 _dev(coef, torch.float32, 'coef', True), float(step_size), float(bc2_sqrt), float(beta1),
                                 float(beta2), float(eps), float(weight_decay), _stream(params[0])), 'mgcn_adam_step')
@@ -1244,6 +1258,24 @@ def _splitmix64(x):
 def dropout_key(seed, step, site):
     """key(seed, step, site) = sm(sm(sm(seed) ^ step) ^ site), sm = one SplitMix64 step: the 64-bit key of one site's masks."""
     return _splitmix64(_splitmix64(_splitmix64(int(seed) & _M64) ^ (int(step) & _M64)) ^ (int(site) & _M64))
+
+
+def dropout_step_key(seed, step):
+    """sm(sm(seed) ^ step): the 64-bit word of one step, all that the kernels' device-key form needs of (seed, step). Every site's
+    key follows from it: dropout_key(seed, step, site) == sm(dropout_step_key(seed, step) ^ site)."""
+    return _splitmix64(_splitmix64(int(seed) & _M64) ^ (int(step) & _M64))
+
+
+class DeviceKey(object):
+    """A site's key in the device form: `word` is a one-element int64 device tensor that holds dropout_step_key(seed, step) (the
+    64 bits, two's complement) at the time the kernel RUNS, `site` the site id. dropout_apply / dropout_apply_pair / dropout_mask
+    take one wherever they take an integer key and then launch the _dev entry points, whose lanes form sm(word ^ site)."""
+    __slots__ = ('word', 'site')
+
+    def __init__(self, word, site):
+        if not torch.is_tensor(word) or word.dtype != torch.int64 or word.numel() != 1 or not word.is_cuda:
+            raise NativeError('DeviceKey: the step word must be a one-element int64 tensor on a GPU')
+        self.word, self.site = word, int(site) & _M64
 
 
 def dropout_layer_site(li, which):
@@ -1290,6 +1322,12 @@ def dropout_apply(x, key, row0, p, out=None):
     if rows == 0 or cols == 0:
         return out
     thr, inv_keep = dropout_scale(p)
+    if isinstance(key, DeviceKey):
+        _same_device(x, key.word)
+        _check(lib().mgcn_dropout_apply_dev(rows, cols, _dev(x, torch.float32, 'x'), _ld(x), _dev(out, torch.float32, 'out'), _ld(out),
+                                            key.word.data_ptr(), key.site, int(row0) & _M64, thr, inv_keep, _stream(x)),
+               'mgcn_dropout_apply_dev')
+        return out
     _check(lib().mgcn_dropout_apply(rows, cols, _dev(x, torch.float32, 'x'), _ld(x), _dev(out, torch.float32, 'out'), _ld(out),
                                     int(key) & _M64, int(row0) & _M64, thr, inv_keep, _stream(x)), 'mgcn_dropout_apply')
     return out
@@ -1307,6 +1345,15 @@ def dropout_apply_pair(xa, key_a, xb, key_b, row0, p, out_a=None, out_b=None):
     if rows == 0 or cols == 0:
         return out_a, out_b
     thr, inv_keep = dropout_scale(p)
+    if isinstance(key_a, DeviceKey) or isinstance(key_b, DeviceKey):
+        if not (isinstance(key_a, DeviceKey) and isinstance(key_b, DeviceKey)) or key_a.word.data_ptr() != key_b.word.data_ptr():
+            raise NativeError('dropout_apply_pair: the two sites of a pair share one device step word')
+        _same_device(xa, key_a.word)
+        _check(lib().mgcn_dropout_apply_pair_dev(
+            rows, cols, _dev(xa, torch.float32, 'x_a'), _ld(xa), _dev(out_a, torch.float32, 'out_a'), _ld(out_a), key_a.site,
+            _dev(xb, torch.float32, 'x_b'), _ld(xb), _dev(out_b, torch.float32, 'out_b'), _ld(out_b), key_b.site,
+            key_a.word.data_ptr(), int(row0) & _M64, thr, inv_keep, _stream(xa)), 'mgcn_dropout_apply_pair_dev')
+        return out_a, out_b
     _check(lib().mgcn_dropout_apply_pair(
         rows, cols, _dev(xa, torch.float32, 'x_a'), _ld(xa), _dev(out_a, torch.float32, 'out_a'), _ld(out_a), int(key_a) & _M64,
         _dev(xb, torch.float32, 'x_b'), _ld(xb), _dev(out_b, torch.float32, 'out_b'), _ld(out_b), int(key_b) & _M64,
@@ -1323,6 +1370,11 @@ def dropout_mask(rows, cols, key, row0, p, device=None, out=None):
         raise NativeError('dropout_mask: out must be a bool / uint8 [%d, %d]' % (rows, cols))
     _drop_block(out, 'dropout_mask')
     if out.numel() == 0:
+        return out
+    if isinstance(key, DeviceKey):
+        _same_device(out, key.word)
+        _check(lib().mgcn_dropout_mask_dev(int(rows), int(cols), _dev(out, out.dtype, 'mask'), _ld(out), key.word.data_ptr(), key.site,
+                                           int(row0) & _M64, dropout_scale(p)[0], _stream(out)), 'mgcn_dropout_mask_dev')
         return out
     _check(lib().mgcn_dropout_mask(int(rows), int(cols), _dev(out, out.dtype, 'mask'), _ld(out), int(key) & _M64, int(row0) & _M64,
                                    dropout_scale(p)[0], _stream(out)), 'mgcn_dropout_mask')

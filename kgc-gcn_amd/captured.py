@@ -1,0 +1,282 @@
+"""CapturedTrainStep: one training step of harness.train_device_labels (fused_loss=True) -- zero_grad, MGCN.forward_loss, backward,
+ClipAdam.clip_and_step -- captured once into a hipGraph (torch.cuda.CUDAGraph) and replayed, so that a step costs the host a check of the
+capture key, one small copy and one replay(), and never waits for the device.
+
+What makes the step capturable: the clip coefficient is formed on the device (optim.ClipAdam), the targets and the loss are built
+on the device (MGCN.forward_loss), the counter-based dropout has no generator, and the scalars that change from step to step are
+read from device memory by the captured launches: Adam's (step_size, bc2_sqrt) per parameter group (mgcn_adam_step_dev) and the
+dropout step word sm(sm(seed) ^ step) (mgcn_dropout_*_dev). Before every replay the wrapper writes the values the eager step would
+have passed by value into a pinned buffer and enqueues ONE host-to-device copy ahead of the replay; nothing is computed on the
+device that the host computes in the eager step, so the trajectory is the eager one bit for bit wherever the eager step is
+reproducible (the HIP trunk and query path). A scheduler's lr, load_dropout_state, a changed seed and model.load_state_dict (an
+in-place copy) take effect on the next replay without a new capture.
+
+Out of scope: dist.train_step_sharded (its collectives would sit inside the capture), harness.train (its label rows are built on
+the host) and torch-drawn dropout (a generator's state does not advance in a replay): the wrapper refuses a dropout site with
+p > 0 unless params.dropout is 'counter'.
+
+Counters. `captures`: graphs captured (1 + re-captures); `replays`: steps run from a graph; `eager_steps`: steps run without one
+(the warm-up, other batch sizes, everything after a failed capture); `disabled`: a capture raised and the wrapper went eager for
+good. model._query_rows_count, conv2._trunk_train_count and conv2._tail_train_count are advanced by Python code, which a replay does
+not run: under this wrapper they count eager steps and CAPTURES, not replays.
+
+After a replay every .grad is one of the graph's static tensors (contents unspecified, as after any clip_and_step); the graph's
+private pool keeps the step's activations, gradients and workspaces alive for as long as the wrapper lives.
+"""
+import logging
+import os
+import types
+
+import numpy as np
+import torch
+
+from . import _native
+from .model import _counter_dropout_wanted
+
+_ENV_SWITCHES = ('MGCN_QUERY_TRAIN', 'MGCN_TRUNK_TRAIN', 'MGCN_DROPOUT', 'MGCN_TRAIN_TORCH', 'MGCN_TRUNK')
+_PARAM_SWITCHES = ('query_path_train', 'conve_trunk_train', 'dropout', 'conve_trunk')
+_RING = 8      # pinned staging slots: the host may run this many replays ahead of the device before it waits for a copy
+
+
+class CapturedTrainStep(object):
+    """step = CapturedTrainStep(model, graph, index, optimizer, lbl_smooth=0.0, clip=None, warmup=2); loss = step(src, rel).
+
+    `loss` is a 0-dim device tensor; no call waits for the device, and the next call overwrites it (clone it to keep it). The
+    first `warmup` (>= 1) calls are ordinary eager steps on the real batches (they create the optimizer state whose addresses
+    the graph holds); the next call captures and replays at once. The model must be in training mode. A call with another
+    batch size than the captured one (an epoch's last batch) runs eagerly and does not re-capture. The wrapper re-captures
+    when something the captured launches hold by value or by address changed: the graph's CSR, the address of a parameter, a
+    buffer, an optimizer state tensor or an index tensor, the set of parameters that take a gradient, a dispatch switch or
+    its environment variable, a dropout probability, a BatchNorm momentum or eps, betas / eps / weight_decay of a group,
+    `lbl_smooth` or `clip` (both plain attributes). optimizer.load_state_dict replaces the state tensors and so re-captures;
+    model.load_state_dict copies in place and does not.
+
+    Raises NativeError, before anything is captured, for: a model on the CPU, in eval mode (the step is a training step: call
+    model.train() first) or holding a table shard; an optimizer without clip_and_step, without ClipAdam's device-hyper hooks, or
+    whose _hip_plan() is None; a parameter group whose parameters disagree on the step count; a dropout site with p > 0 while
+    params.dropout is not 'counter'; a batch the fused score + loss launch does not take.
+
+    Host cost of a call: besides the copy and the replay, every call re-forms the capture key in Python (addresses of all
+    parameters, buffers and optimizer state tensors, the switches): O(number of parameters), no device work, no wait. It is part
+    of every wall time tools/bench_train_captured.py reports."""
+
+    def __init__(self, model, graph, index, optimizer, lbl_smooth=0.0, clip=None, warmup=2):
+        self.model, self.graph, self.index, self.optimizer = model, graph, index, optimizer
+        self.lbl_smooth, self.clip, self.warmup = float(lbl_smooth), clip, max(1, int(warmup))
+        self.captures = self.replays = self.eager_steps = 0
+        self.disabled = False
+        self._hit = None
+        self._stage = None
+        self._warmed = False
+
+    # -- the step itself -------------------------------------------------------------------------
+    def _body(self, src, rel):
+        opt = self.optimizer
+        opt.zero_grad(set_to_none=True)
+        loss = self.model.forward_loss(src, rel, self.graph, self.index, lbl_smooth=self.lbl_smooth)
+        loss.backward()
+        opt.clip_and_step(self.clip)
+        return loss.detach()
+
+    def _eager(self, src, rel):
+        self.eager_steps += 1
+        return self._body(src, rel)
+
+    # -- what a capture depends on -----------------------------------------------------------------
+    def _layers(self):
+        m = self.model
+        return [m.conv1] + list(m.conv1_extra)
+
+    def _dropout_ps(self):
+        m = self.model
+        return tuple(float(layer.drop.p) for layer in self._layers()) + (
+            float(m.params.gcn_drop), float(m.conv2.hidden_drop.p), float(m.conv2.feature_drop.p))
+
+    def _refuse(self, src):
+        """The reasons not to capture at all: raised (NativeError) before anything is captured."""
+        m, opt = self.model, self.optimizer
+        if not m.entity_embedding.is_cuda:
+            raise _native.NativeError('CapturedTrainStep: the model is on the CPU; the training step runs on a GPU only')
+        if m._edge_shard is not None:
+            raise _native.NativeError('CapturedTrainStep: this model holds a shard of the per-edge tables; the sharded step '
+                                      '(dist.train_step_sharded) has collectives, which cannot sit inside a capture')
+        if not m.training:
+            raise _native.NativeError('CapturedTrainStep: the model is in eval mode; call model.train() first')
+        if not hasattr(opt, 'clip_and_step'):
+            raise _native.NativeError('CapturedTrainStep: the optimizer has no clip_and_step (optim.ClipAdam is required: a captured '
+                                      'Adam step reads its bias corrections from device memory)')
+        if not all(hasattr(opt, name) for name in ('begin_device_hyper', 'end_device_hyper', 'hyper_values', 'advance_steps', '_hip_plan')):
+            raise _native.NativeError('CapturedTrainStep: the optimizer has clip_and_step but not ClipAdam\'s device-hyper hooks '
+                                      '(begin_device_hyper, end_device_hyper, hyper_values, advance_steps)')
+        if opt._hip_plan() is None:
+            raise _native.NativeError('CapturedTrainStep: ClipAdam would take torch\'s own step for this optimizer (amsgrad, maximize, '
+                                      'capturable, a tensor lr, a parameter that is not contiguous f32 on one GPU, ...): only the HIP '
+                                      'kernels\' step is captured')
+        for gi, group in enumerate(opt.param_groups):
+            steps = {float(opt.state[p]['step']) for p in group['params'] if opt.state.get(p)}
+            if len(steps) > 1:
+                raise _native.NativeError('CapturedTrainStep: the parameters of group %d disagree on the step count (%s); one '
+                                          '(step_size, bc2_sqrt) pair per group is written per replay' % (gi, sorted(steps)))
+        if any(p > 0 for p in self._dropout_ps()) and not _counter_dropout_wanted(m.params):
+            raise _native.NativeError('CapturedTrainStep: a dropout site has p > 0 and params.dropout is not \'counter\': masks drawn '
+                                      'from a torch generator would be frozen into the graph')
+        B, O = int(src.numel()), int(m.params.gcn_out_dim)
+        probe = torch.empty((B, O), dtype=torch.float32, device=m.entity_embedding.device)
+        if B == 0 or not _native.score_bce_supported(probe, probe):
+            raise _native.NativeError('CapturedTrainStep: the fused score + loss launch does not take a batch of %d x %d (both must '
+                                      'be multiples of 4)' % (B, O))
+
+    def _key(self):
+        m, opt, g, ix = self.model, self.optimizer, self.graph, self.index
+        # the layout switch every encode begins with (after a load_state_dict the tables are back in reference order): a replay
+        # runs no Python of the step, so it happens here, in place, ahead of the replay
+        csr, ent_identity, edge_identity = m._layout_for(g)
+        key = [id(csr), ent_identity, edge_identity, g.edge_index.data_ptr(), g.edge_attr.data_ptr(), ix.keys.data_ptr(), ix.ptr.data_ptr(), ix.tails.data_ptr(),
+               ix.num_rel_ids, self.lbl_smooth, self.clip, self._dropout_ps(), int(getattr(m.params, 'gcn_layers', 1))]
+        key += [os.environ.get(name) for name in _ENV_SWITCHES] + [getattr(m.params, name, None) for name in _PARAM_SWITCHES]
+        key += [(p.data_ptr(), p.requires_grad) for p in m.parameters()] + [b.data_ptr() for b in m.buffers()]
+        key += [(bn.momentum, bn.eps) for bn in m.modules() if isinstance(bn, torch.nn.modules.batchnorm._BatchNorm)]
+        for group in opt.param_groups:
+            key.append((tuple(group['betas']), group['eps'], group['weight_decay'], len(group['params'])))
+            for p in group['params']:
+                st = opt.state.get(p)
+                key.append((p.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr()) if st else (p.data_ptr(),))
+        return tuple(key)
+
+    def _ready(self):
+        """Whether the optimizer state the graph will hold exists: an eager step has run since it was (re)built."""
+        opt = self.optimizer
+        with_grad = [p for group in opt.param_groups for p in group['params'] if p.grad is not None]
+        return bool(with_grad) and all(len(opt.state.get(p, ())) > 0 for p in with_grad)
+
+    # -- staging of the step scalars ---------------------------------------------------------------
+    def _staging(self, device, rows):
+        """The device buffer the captured launches read (8 bytes: the dropout step word; then `rows` float pairs: Adam's
+        step_size and bc2_sqrt per group) and a ring of pinned host images of it."""
+        st = self._stage
+        if st is None or st.device != device or st.rows != rows:
+            nbytes = 8 + 8 * rows
+            dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+            st = types.SimpleNamespace(device=device, rows=rows, dev=dev, word=dev[:8].view(torch.int64),
+                                       hyper=dev[8:].view(torch.float32).view(rows, 2), slots=[], next=0)
+            st.hyper.fill_(1.0)
+            for _ in range(_RING):
+                host = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+                image = host.numpy()
+                st.slots.append(types.SimpleNamespace(host=host, word=image[:8].view(np.uint64), hyper=image[8:].view(np.float32),
+                                                      event=torch.cuda.Event(), used=False))
+            self._stage = st
+        return st
+
+    def _upload(self, st, hit):
+        """The values the eager step would pass by value now, through one pinned image and one non-blocking copy on the
+        current stream."""
+        m = self.model
+        slot = st.slots[st.next]
+        st.next = (st.next + 1) % len(st.slots)
+        if slot.used:
+            slot.event.synchronize()                  # (its copy of _RING replays ago has long run: this returns at once)
+        slot.word[0] = _native.dropout_step_key(m.dropout_seed, m.dropout_step)
+        for k, (step_size, bc2_sqrt) in enumerate(self.optimizer.hyper_values(hit.rows)):
+            slot.hyper[2 * k], slot.hyper[2 * k + 1] = step_size, bc2_sqrt     # doubles rounded to float, as the by-value call
+        st.dev.copy_(slot.host, non_blocking=True)
+        slot.event.record()
+        slot.used = True
+
+    def _warm_kernels(self, st):
+        """One launch of the device-scalar entry points on scratch tensors, once per wrapper, outside the capture; leaves no
+        trace. A precaution of the same kind as the warm-up pass of MGCN._encode_replay: the runtime resolves a kernel (and
+        loads its code object) at its first launch, and the eager warm-up steps only ever launched the by-value forms, so
+        without this the _dev forms would meet that lazy work inside the capture. The shapes cover the vector and the element
+        path and both weight-decay variants; a form this list misses is merely first launched inside the capture."""
+        if self._warmed:
+            return
+        self._warmed = True
+        dev = st.device
+        k0, k1 = _native.DeviceKey(st.word, 0), _native.DeviceKey(st.word, 1)
+        for x in (torch.zeros((2, 8), device=dev), torch.zeros((2, 8), device=dev)[:, :7]):
+            _native.dropout_apply(x, k0, 0, 0.5)
+            _native.dropout_apply_pair(x, k0, x, k1, 0, 0.5)
+            _native.dropout_mask(2, x.size(1), k0, 0, 0.5, out=torch.zeros((2, 8), dtype=torch.uint8, device=dev)[:, :x.size(1)])
+        t = [torch.ones(4, device=dev) for _ in range(4)]
+        for wd in (0.0, 0.01):
+            _native.adam_step([t[0]], [t[1]], [t[2]], [t[3]], None, 0.0, 1.0, 0.9, 0.999, 1e-8, wd, hyper_dev=st.hyper[0])
+
+    # -- capture and replay ------------------------------------------------------------------------
+    def _capture(self, src, rel, key):
+        m, opt = self.model, self.optimizer
+        device = m.entity_embedding.device
+        st = self._staging(device, len(opt.param_groups))
+        B = int(src.numel())
+        s_src = torch.empty(B, dtype=torch.int64, device=device)
+        s_rel = torch.empty(B, dtype=torch.int64, device=device)
+        self._warm_kernels(st)
+        # capturing executes nothing on the device but runs the Python side effects: keep the host counters as they are
+        saved_drop = m.dropout_step
+        saved_steps = [(state, state['step'].clone()) for state in opt.state.values() if 'step' in state]
+        saved_opt = (opt._hip_step_count, getattr(opt, '_opt_called', False))
+        graph = torch.cuda.CUDAGraph()
+        m._step_key_dev = st.word
+        opt.begin_device_hyper(st.hyper)
+        rows, err = [], None
+        try:
+            # thread_local: as MGCN._encode_replay (other threads of the process must not invalidate this capture)
+            with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+                loss = self._body(s_src, s_rel)
+        except RuntimeError as e:
+            err = e
+        finally:
+            m._step_key_dev = None
+            m.conv2._drop_ctx = None
+            rows = opt.end_device_hyper()
+            advance = m.dropout_step - saved_drop
+            m.dropout_step = saved_drop
+            for state, step in saved_steps:
+                state['step'].copy_(step)
+            opt._hip_step_count, opt._opt_called = saved_opt
+        if err is not None:                              # capture refused: the same launches, without a graph, from now on
+            logging.warning('hipGraph capture of the training step failed (%s): running the step eagerly', err)
+            torch.cuda.synchronize()
+            self.disabled = True
+            return None
+        written = [p for p in m.parameters() if p.grad is not None]
+        for bn in m.modules():
+            if isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
+                written += [b for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked) if b is not None]
+        self.captures += 1
+        self._hit = types.SimpleNamespace(key=key, graph=graph, loss=loss, rows=rows, batch=B, src=s_src, rel=s_rel, written=written,
+                                          dropout_advance=advance)
+        return self._hit
+
+    def _replay(self, hit, src, rel):
+        m = self.model
+        self._upload(self._stage, hit)
+        hit.src.copy_(src.reshape(-1), non_blocking=True)
+        hit.rel.copy_(rel.reshape(-1), non_blocking=True)
+        hit.graph.replay()
+        # the host mirrors of what the eager step advances, and the version stamps of everything the graph wrote
+        m.dropout_step += hit.dropout_advance
+        self.optimizer.advance_steps(hit.rows)
+        torch.autograd.graph.increment_version(hit.written)
+        self.replays += 1
+        return hit.loss
+
+    def __call__(self, src, rel):
+        if self.disabled:
+            return self._eager(src, rel)
+        hit = self._hit
+        if hit is not None and int(src.numel()) != hit.batch:
+            return self._eager(src, rel)                # e.g. an epoch's last batch: no re-capture
+        if hit is None:
+            self._refuse(src)
+        key = self._key()
+        if hit is None or hit.key != key:
+            if hit is not None:
+                self._refuse(src)
+            if self.eager_steps < self.warmup or not self._ready():
+                return self._eager(src, rel)
+            self._hit = None                             # (releases the old graph and its pool before the new capture)
+            hit = self._capture(src, rel, key)
+            if hit is None:
+                return self._eager(src, rel)
+        return self._replay(hit, src, rel)

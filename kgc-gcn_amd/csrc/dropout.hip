@@ -39,6 +39,23 @@ __host__ __device__ inline void dropout_words(uint64_t key, uint64_t row, uint32
   w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
 }
 
+// One SplitMix64 step (include/mgcn_hip.h (12)), the ONE definition in C++: key(seed, step, site) = sm(sm(sm(seed) ^ step) ^ site).
+// The by-value entry points receive the finished key; the _dev ones receive the site id and a pointer to the step word
+// sm(sm(seed) ^ step), and every lane forms the last step itself (site_key below), so a captured launch follows the word in memory.
+__host__ __device__ inline uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  uint64_t z = x;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// the key of a site: `k` itself (KD false: it is the key), or sm(*step_key ^ k) (KD true: k is the site id)
+template <bool KD>
+__host__ __device__ inline uint64_t site_key(uint64_t k, const uint64_t *step_key) {
+  return KD ? splitmix64(*step_key ^ k) : k;
+}
+
 // kept: one f32 multiply; dropped: +0.0f whatever x holds (inf and NaN included)
 __device__ inline float dropped(float x, bool keep, float inv_keep) { return keep ? x * inv_keep : 0.f; }
 
@@ -59,17 +76,18 @@ struct Site {
   int64_t ldx;
   float *out;
   int64_t ldo;
-  uint64_t key;
+  uint64_t key;      // the site's key, or its site id in the _dev entry points
 };
 
 // NS sites (1: apply, 2: the layer's in / out pair) over the same [rows, cols] block; VEC: every base pointer is 16-byte aligned and
 // every leading dimension a multiple of four floats, so a whole column block is one 16-byte access. A lane reads its elements of
 // every site before it writes any, and no lane touches another's elements: an output may be its own input, and the two inputs of a
 // pair may be one tensor.
-template <int NS, bool VEC>
+template <int NS, bool VEC, bool KD>
 __global__ __launch_bounds__(TPB) void apply_kernel(int64_t rows, int32_t cols, int32_t ncb, Site s0, Site s1, uint64_t row0,
-                                                    uint32_t threshold, float inv_keep) {
+                                                    uint32_t threshold, float inv_keep, const uint64_t *__restrict__ step_key) {
   const int64_t units = rows * ncb, stride = int64_t(gridDim.x) * TPB;
+  const uint64_t keys[2] = {site_key<KD>(s0.key, step_key), site_key<KD>(s1.key, step_key)};
   for (int64_t u = int64_t(blockIdx.x) * TPB + threadIdx.x; u < units; u += stride) {
     int64_t r;
     int32_t cb;
@@ -92,7 +110,7 @@ __global__ __launch_bounds__(TPB) void apply_kernel(int64_t rows, int32_t cols, 
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       uint32_t w[4];
-      dropout_words(site[i].key, row0 + uint64_t(r), uint32_t(cb), w);
+      dropout_words(keys[i], row0 + uint64_t(r), uint32_t(cb), w);
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[i][j] = dropped(v[i][j], w[j] < threshold, inv_keep);
     }
@@ -111,10 +129,11 @@ __global__ __launch_bounds__(TPB) void apply_kernel(int64_t rows, int32_t cols, 
 }
 
 // keep bytes (1 / 0); VEC: base 4-byte aligned and ldm a multiple of four, so a whole column block is one 32-bit store
-template <bool VEC>
-__global__ __launch_bounds__(TPB) void mask_kernel(int64_t rows, int32_t cols, int32_t ncb, uint8_t *mask, int64_t ldm, uint64_t key,
-                                                   uint64_t row0, uint32_t threshold) {
+template <bool VEC, bool KD>
+__global__ __launch_bounds__(TPB) void mask_kernel(int64_t rows, int32_t cols, int32_t ncb, uint8_t *mask, int64_t ldm, uint64_t key_or_site,
+                                                   uint64_t row0, uint32_t threshold, const uint64_t *__restrict__ step_key) {
   const int64_t units = rows * ncb, stride = int64_t(gridDim.x) * TPB;
+  const uint64_t key = site_key<KD>(key_or_site, step_key);
   for (int64_t u = int64_t(blockIdx.x) * TPB + threadIdx.x; u < units; u += stride) {
     int64_t r;
     int32_t cb;
@@ -161,11 +180,15 @@ int check_alias(const char *what, const float *x, int64_t ldx, const float *out,
 
 inline bool vec_ok(const void *p, int64_t ld) { return mgcn::aligned16(p) && ld % 4 == 0; }
 
-}  // namespace
+// the step word of the _dev entry points: one 8-byte word in device memory
+int check_step_key(const char *what, const uint64_t *step_key_dev) {
+  MGCN_REQUIRE(step_key_dev && (reinterpret_cast<uintptr_t>(step_key_dev) & 7u) == 0, "%s: null or misaligned pointer (step_key: one 64-bit word)", what);
+  return MGCN_OK;
+}
 
-extern "C" int mgcn_dropout_apply(int64_t rows, int32_t cols, const float *x_dev, int64_t ldx, float *out_dev, int64_t ldo, uint64_t key,
-                                  uint64_t row0, uint32_t threshold, float inv_keep, void *stream) {
-  const char *what = "mgcn_dropout_apply";
+// The three entries, each in both forms. step_key_dev == nullptr: `key` arguments are keys (by value); otherwise they are site ids.
+int apply_launch(const char *what, int64_t rows, int32_t cols, const float *x_dev, int64_t ldx, float *out_dev, int64_t ldo, uint64_t key,
+                 const uint64_t *step_key_dev, uint64_t row0, uint32_t threshold, float inv_keep, void *stream) {
   if (int rc = check_block(what, rows, cols)) return rc;
   if (int rc = check_matrix(what, "x", x_dev, ldx, rows, cols)) return rc;
   if (int rc = check_matrix(what, "out", out_dev, ldo, rows, cols)) return rc;
@@ -176,18 +199,25 @@ extern "C" int mgcn_dropout_apply(int64_t rows, int32_t cols, const float *x_dev
   const Site s = {x_dev, ldx, out_dev, ldo, key};
   const dim3 grid(grid_for(rows * ncb)), block(TPB);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec_ok(x_dev, ldx) && vec_ok(out_dev, ldo))
-    apply_kernel<1, true><<<grid, block, 0, st>>>(rows, cols, ncb, s, s, row0, threshold, inv_keep);
-  else
-    apply_kernel<1, false><<<grid, block, 0, st>>>(rows, cols, ncb, s, s, row0, threshold, inv_keep);
+  const bool vec = vec_ok(x_dev, ldx) && vec_ok(out_dev, ldo);
+  if (step_key_dev) {
+    if (vec)
+      apply_kernel<1, true, true><<<grid, block, 0, st>>>(rows, cols, ncb, s, s, row0, threshold, inv_keep, step_key_dev);
+    else
+      apply_kernel<1, false, true><<<grid, block, 0, st>>>(rows, cols, ncb, s, s, row0, threshold, inv_keep, step_key_dev);
+  } else {
+    if (vec)
+      apply_kernel<1, true, false><<<grid, block, 0, st>>>(rows, cols, ncb, s, s, row0, threshold, inv_keep, nullptr);
+    else
+      apply_kernel<1, false, false><<<grid, block, 0, st>>>(rows, cols, ncb, s, s, row0, threshold, inv_keep, nullptr);
+  }
   MGCN_CHECK_LAUNCH(what);
   return MGCN_OK;
 }
 
-extern "C" int mgcn_dropout_apply_pair(int64_t rows, int32_t cols, const float *xa_dev, int64_t ldxa, float *outa_dev, int64_t ldoa,
-                                       uint64_t key_a, const float *xb_dev, int64_t ldxb, float *outb_dev, int64_t ldob, uint64_t key_b,
-                                       uint64_t row0, uint32_t threshold, float inv_keep, void *stream) {
-  const char *what = "mgcn_dropout_apply_pair";
+int pair_launch(const char *what, int64_t rows, int32_t cols, const float *xa_dev, int64_t ldxa, float *outa_dev, int64_t ldoa, uint64_t key_a,
+                const float *xb_dev, int64_t ldxb, float *outb_dev, int64_t ldob, uint64_t key_b, const uint64_t *step_key_dev, uint64_t row0,
+                uint32_t threshold, float inv_keep, void *stream) {
   if (int rc = check_block(what, rows, cols)) return rc;
   if (int rc = check_matrix(what, "x_a", xa_dev, ldxa, rows, cols)) return rc;
   if (int rc = check_matrix(what, "out_a", outa_dev, ldoa, rows, cols)) return rc;
@@ -205,29 +235,88 @@ extern "C" int mgcn_dropout_apply_pair(int64_t rows, int32_t cols, const float *
   const Site a = {xa_dev, ldxa, outa_dev, ldoa, key_a}, b = {xb_dev, ldxb, outb_dev, ldob, key_b};
   const dim3 grid(grid_for(rows * ncb)), block(TPB);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec_ok(xa_dev, ldxa) && vec_ok(outa_dev, ldoa) && vec_ok(xb_dev, ldxb) && vec_ok(outb_dev, ldob))
-    apply_kernel<2, true><<<grid, block, 0, st>>>(rows, cols, ncb, a, b, row0, threshold, inv_keep);
-  else
-    apply_kernel<2, false><<<grid, block, 0, st>>>(rows, cols, ncb, a, b, row0, threshold, inv_keep);
+  const bool vec = vec_ok(xa_dev, ldxa) && vec_ok(outa_dev, ldoa) && vec_ok(xb_dev, ldxb) && vec_ok(outb_dev, ldob);
+  if (step_key_dev) {
+    if (vec)
+      apply_kernel<2, true, true><<<grid, block, 0, st>>>(rows, cols, ncb, a, b, row0, threshold, inv_keep, step_key_dev);
+    else
+      apply_kernel<2, false, true><<<grid, block, 0, st>>>(rows, cols, ncb, a, b, row0, threshold, inv_keep, step_key_dev);
+  } else {
+    if (vec)
+      apply_kernel<2, true, false><<<grid, block, 0, st>>>(rows, cols, ncb, a, b, row0, threshold, inv_keep, nullptr);
+    else
+      apply_kernel<2, false, false><<<grid, block, 0, st>>>(rows, cols, ncb, a, b, row0, threshold, inv_keep, nullptr);
+  }
   MGCN_CHECK_LAUNCH(what);
   return MGCN_OK;
 }
 
-extern "C" int mgcn_dropout_mask(int64_t rows, int32_t cols, uint8_t *mask_dev, int64_t ldm, uint64_t key, uint64_t row0,
-                                 uint32_t threshold, void *stream) {
-  const char *what = "mgcn_dropout_mask";
+int mask_launch(const char *what, int64_t rows, int32_t cols, uint8_t *mask_dev, int64_t ldm, uint64_t key, const uint64_t *step_key_dev,
+                uint64_t row0, uint32_t threshold, void *stream) {
   if (int rc = check_block(what, rows, cols)) return rc;
   if (int rc = check_matrix(what, "mask", mask_dev, ldm, rows, cols)) return rc;
   if (rows == 0) return MGCN_OK;
   const int32_t ncb = (cols + 3) / 4;
   const dim3 grid(grid_for(rows * ncb)), block(TPB);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if ((reinterpret_cast<uintptr_t>(mask_dev) & 3u) == 0 && ldm % 4 == 0)
-    mask_kernel<true><<<grid, block, 0, st>>>(rows, cols, ncb, mask_dev, ldm, key, row0, threshold);
-  else
-    mask_kernel<false><<<grid, block, 0, st>>>(rows, cols, ncb, mask_dev, ldm, key, row0, threshold);
+  const bool vec = (reinterpret_cast<uintptr_t>(mask_dev) & 3u) == 0 && ldm % 4 == 0;
+  if (step_key_dev) {
+    if (vec)
+      mask_kernel<true, true><<<grid, block, 0, st>>>(rows, cols, ncb, mask_dev, ldm, key, row0, threshold, step_key_dev);
+    else
+      mask_kernel<false, true><<<grid, block, 0, st>>>(rows, cols, ncb, mask_dev, ldm, key, row0, threshold, step_key_dev);
+  } else {
+    if (vec)
+      mask_kernel<true, false><<<grid, block, 0, st>>>(rows, cols, ncb, mask_dev, ldm, key, row0, threshold, nullptr);
+    else
+      mask_kernel<false, false><<<grid, block, 0, st>>>(rows, cols, ncb, mask_dev, ldm, key, row0, threshold, nullptr);
+  }
   MGCN_CHECK_LAUNCH(what);
   return MGCN_OK;
+}
+
+}  // namespace
+
+extern "C" int mgcn_dropout_apply(int64_t rows, int32_t cols, const float *x_dev, int64_t ldx, float *out_dev, int64_t ldo, uint64_t key,
+                                  uint64_t row0, uint32_t threshold, float inv_keep, void *stream) {
+  return apply_launch("mgcn_dropout_apply", rows, cols, x_dev, ldx, out_dev, ldo, key, nullptr, row0, threshold, inv_keep, stream);
+}
+
+extern "C" int mgcn_dropout_apply_dev(int64_t rows, int32_t cols, const float *x_dev, int64_t ldx, float *out_dev, int64_t ldo,
+                                      const uint64_t *step_key_dev, uint64_t site, uint64_t row0, uint32_t threshold, float inv_keep,
+                                      void *stream) {
+  const char *what = "mgcn_dropout_apply_dev";
+  if (int rc = check_step_key(what, step_key_dev)) return rc;
+  return apply_launch(what, rows, cols, x_dev, ldx, out_dev, ldo, site, step_key_dev, row0, threshold, inv_keep, stream);
+}
+
+extern "C" int mgcn_dropout_apply_pair(int64_t rows, int32_t cols, const float *xa_dev, int64_t ldxa, float *outa_dev, int64_t ldoa,
+                                       uint64_t key_a, const float *xb_dev, int64_t ldxb, float *outb_dev, int64_t ldob, uint64_t key_b,
+                                       uint64_t row0, uint32_t threshold, float inv_keep, void *stream) {
+  return pair_launch("mgcn_dropout_apply_pair", rows, cols, xa_dev, ldxa, outa_dev, ldoa, key_a, xb_dev, ldxb, outb_dev, ldob, key_b, nullptr,
+                     row0, threshold, inv_keep, stream);
+}
+
+extern "C" int mgcn_dropout_apply_pair_dev(int64_t rows, int32_t cols, const float *xa_dev, int64_t ldxa, float *outa_dev, int64_t ldoa,
+                                           uint64_t site_a, const float *xb_dev, int64_t ldxb, float *outb_dev, int64_t ldob,
+                                           uint64_t site_b, const uint64_t *step_key_dev, uint64_t row0, uint32_t threshold,
+                                           float inv_keep, void *stream) {
+  const char *what = "mgcn_dropout_apply_pair_dev";
+  if (int rc = check_step_key(what, step_key_dev)) return rc;
+  return pair_launch(what, rows, cols, xa_dev, ldxa, outa_dev, ldoa, site_a, xb_dev, ldxb, outb_dev, ldob, site_b, step_key_dev, row0,
+                     threshold, inv_keep, stream);
+}
+
+extern "C" int mgcn_dropout_mask(int64_t rows, int32_t cols, uint8_t *mask_dev, int64_t ldm, uint64_t key, uint64_t row0,
+                                 uint32_t threshold, void *stream) {
+  return mask_launch("mgcn_dropout_mask", rows, cols, mask_dev, ldm, key, nullptr, row0, threshold, stream);
+}
+
+extern "C" int mgcn_dropout_mask_dev(int64_t rows, int32_t cols, uint8_t *mask_dev, int64_t ldm, const uint64_t *step_key_dev,
+                                     uint64_t site, uint64_t row0, uint32_t threshold, void *stream) {
+  const char *what = "mgcn_dropout_mask_dev";
+  if (int rc = check_step_key(what, step_key_dev)) return rc;
+  return mask_launch(what, rows, cols, mask_dev, ldm, site, step_key_dev, row0, threshold, stream);
 }
 
 extern "C" int mgcn_dropout_mask_host(int64_t rows, int32_t cols, uint8_t *mask_host, int64_t ldm, uint64_t key, uint64_t row0,

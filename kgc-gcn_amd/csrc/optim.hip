@@ -135,10 +135,17 @@ __device__ __forceinline__ void adam_one(float g, float &p, float &m, float &v, 
 }
 
 // (3) one chunk of one tensor per workgroup: 16-byte accesses when all four bases allow it, scalars otherwise and for the
-// last numel % 4 elements. g is read only.
-template <bool WD>
-__global__ __launch_bounds__(TPB) void adam_step_kernel(StepBatch b, Hyper h, const float *__restrict__ coef_dev) {
+// last numel % 4 elements. g is read only. HD: the two scalars that change from step to step, step_size and bc2_sqrt, are
+// loaded from hyper_dev[0 .. 2) instead of travelling in `h` (mgcn_adam_step_dev: a captured launch reads each replay's values);
+// everything after the load is the same code, so the same two floats give the same bits.
+template <bool WD, bool HD>
+__global__ __launch_bounds__(TPB) void adam_step_kernel(StepBatch b, Hyper h, const float *__restrict__ coef_dev,
+                                                        const float *__restrict__ hyper_dev) {
   const int wg = blockIdx.x, tid = threadIdx.x;
+  if (HD) {
+    h.neg_step = -hyper_dev[0];
+    h.bc2_sqrt = hyper_dev[1];
+  }
   const int t = tensor_of(b.map, wg);
   const int64_t e0 = int64_t(wg - b.map.chunk0[t]) * CHUNK;
   const int64_t left = b.n[t] - e0;
@@ -253,26 +260,32 @@ extern "C" int mgcn_adam_clip_coef(int64_t n, const float *sq_dev, float max_nor
   return MGCN_OK;
 }
 
-extern "C" int mgcn_adam_step(int64_t n, const float *const *grad_host, float *const *param_host, float *const *exp_avg_host,
-                              float *const *exp_avg_sq_host, const int64_t *numel_host, const float *coef_dev, float step_size,
-                              float bc2_sqrt, double beta1, double beta2, double eps, double weight_decay, void *stream) {
-  if (int rc = check_list("mgcn_adam_step", n, grad_host, numel_host)) return rc;
-  MGCN_REQUIRE(n == 0 || (param_host && exp_avg_host && exp_avg_sq_host), "mgcn_adam_step: null pointer (host array)");
-  MGCN_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "mgcn_adam_step: betas must lie in [0, 1)");
-  MGCN_REQUIRE(eps >= 0.0 && weight_decay >= 0.0, "mgcn_adam_step: eps and weight_decay must be numbers >= 0");
-  MGCN_REQUIRE(step_size >= 0.f && std::isfinite(step_size), "mgcn_adam_step: step_size (lr / (1 - beta1^t)) must be a finite number >= 0");
-  MGCN_REQUIRE(bc2_sqrt > 0.f && bc2_sqrt <= 1.f, "mgcn_adam_step: bc2_sqrt (sqrt(1 - beta2^t)) must lie in (0, 1]");
+namespace {
+
+// both forms of kernel (3). hyper_dev == nullptr: step_size and bc2_sqrt by value (mgcn_adam_step); otherwise they are read on
+// the device and the two by-value arguments are not used (mgcn_adam_step_dev).
+int adam_step_launch(const char *what, int64_t n, const float *const *grad_host, float *const *param_host, float *const *exp_avg_host,
+                     float *const *exp_avg_sq_host, const int64_t *numel_host, const float *coef_dev, const float *hyper_dev,
+                     float step_size, float bc2_sqrt, double beta1, double beta2, double eps, double weight_decay, void *stream) {
+  if (int rc = check_list(what, n, grad_host, numel_host)) return rc;
+  MGCN_REQUIRE(n == 0 || (param_host && exp_avg_host && exp_avg_sq_host), "%s: null pointer (host array)", what);
+  MGCN_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "%s: betas must lie in [0, 1)", what);
+  MGCN_REQUIRE(eps >= 0.0 && weight_decay >= 0.0, "%s: eps and weight_decay must be numbers >= 0", what);
+  if (!hyper_dev) {                                   // by value: checked here, in the order mgcn_adam_step has always checked
+    MGCN_REQUIRE(step_size >= 0.f && std::isfinite(step_size), "%s: step_size (lr / (1 - beta1^t)) must be a finite number >= 0", what);
+    MGCN_REQUIRE(bc2_sqrt > 0.f && bc2_sqrt <= 1.f, "%s: bc2_sqrt (sqrt(1 - beta2^t)) must lie in (0, 1]", what);
+  }
   int64_t live = 0;
   for (int64_t i = 0, c = 0; i < n; ++i) {
     if (!grad_host[i] || numel_host[i] == 0) continue;
-    MGCN_REQUIRE(param_host[i] && exp_avg_host[i] && exp_avg_sq_host[i], "mgcn_adam_step: null pointer (tensor %lld)", (long long)i);
+    MGCN_REQUIRE(param_host[i] && exp_avg_host[i] && exp_avg_sq_host[i], "%s: null pointer (tensor %lld)", what, (long long)i);
     if (live % BATCH == 0) c = 0;
     c += chunks_of(numel_host[i]);
-    if (c > INT32_MAX) return mgcn::fail(MGCN_EUNSUPPORTED, "mgcn_adam_step: more than 2^31 chunks in one launch");
+    if (c > INT32_MAX) return mgcn::fail(MGCN_EUNSUPPORTED, "%s: more than 2^31 chunks in one launch", what);
     ++live;
   }
   Hyper h;
-  h.neg_step = -step_size;
+  h.neg_step = -step_size;                            // (both overwritten on the device when hyper_dev is given)
   h.bc2_sqrt = bc2_sqrt;
   h.omb1 = float(1.0 - beta1);
   h.b2 = float(beta2);
@@ -304,11 +317,38 @@ extern "C" int mgcn_adam_step(int64_t n, const float *const *grad_host, float *c
     b.map.chunk0[BATCH] = c;
     b.map.count = count;
     live -= count;
-    if (h.wd != 0.f)
-      adam_step_kernel<true><<<dim3(c), dim3(TPB), 0, static_cast<hipStream_t>(stream)>>>(b, h, coef_dev);
-    else
-      adam_step_kernel<false><<<dim3(c), dim3(TPB), 0, static_cast<hipStream_t>(stream)>>>(b, h, coef_dev);
-    MGCN_CHECK_LAUNCH("mgcn_adam_step");
+    const dim3 grid(c), block(TPB);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hyper_dev) {
+      if (h.wd != 0.f)
+        adam_step_kernel<true, true><<<grid, block, 0, st>>>(b, h, coef_dev, hyper_dev);
+      else
+        adam_step_kernel<false, true><<<grid, block, 0, st>>>(b, h, coef_dev, hyper_dev);
+    } else {
+      if (h.wd != 0.f)
+        adam_step_kernel<true, false><<<grid, block, 0, st>>>(b, h, coef_dev, nullptr);
+      else
+        adam_step_kernel<false, false><<<grid, block, 0, st>>>(b, h, coef_dev, nullptr);
+    }
+    MGCN_CHECK_LAUNCH(what);
   }
   return MGCN_OK;
+}
+
+}  // namespace
+
+extern "C" int mgcn_adam_step(int64_t n, const float *const *grad_host, float *const *param_host, float *const *exp_avg_host,
+                              float *const *exp_avg_sq_host, const int64_t *numel_host, const float *coef_dev, float step_size,
+                              float bc2_sqrt, double beta1, double beta2, double eps, double weight_decay, void *stream) {
+  return adam_step_launch("mgcn_adam_step", n, grad_host, param_host, exp_avg_host, exp_avg_sq_host, numel_host, coef_dev, nullptr,
+                          step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, stream);
+}
+
+extern "C" int mgcn_adam_step_dev(int64_t n, const float *const *grad_host, float *const *param_host, float *const *exp_avg_host,
+                                  float *const *exp_avg_sq_host, const int64_t *numel_host, const float *coef_dev,
+                                  const float *hyper_dev, double beta1, double beta2, double eps, double weight_decay, void *stream) {
+  MGCN_REQUIRE(hyper_dev && (reinterpret_cast<uintptr_t>(hyper_dev) & 3u) == 0,
+               "mgcn_adam_step_dev: null or misaligned pointer (hyper: two floats, step_size and bc2_sqrt)");
+  return adam_step_launch("mgcn_adam_step_dev", n, grad_host, param_host, exp_avg_host, exp_avg_sq_host, numel_host, coef_dev, hyper_dev,
+                          0.f, 1.f, beta1, beta2, eps, weight_decay, stream);
 }

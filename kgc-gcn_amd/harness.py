@@ -36,11 +36,15 @@ def train(model, data_iter, graph, optimizer, params):
     return loss_avg()
 
 
-def train_device_labels(model, queries, index, graph, optimizer, params, batch_size, generator=None, fused_loss=True):
+def train_device_labels(model, queries, index, graph, optimizer, params, batch_size, generator=None, fused_loss=True, captured=None):
     """One epoch like `train`, but the label rows never exist on the host: `queries` [Q, 2] int64
     (DataLoader.train_queries()), `index` = DataLoader.train_index() on the device; per step only B keys are indexed
     and mgcn_label_rows writes the smoothed [B, N] targets next to the scores. Shuffles like the reference's loader
-    (data_loader.py:190) with `generator`. Same loss / clipping / optimizer calls as main.py:56-70."""
+    (data_loader.py:190) with `generator`. Same loss / clipping / optimizer calls as main.py:56-70.
+    `captured`: a captured.CapturedTrainStep built for this model, graph, index and optimizer (or True: one is built with
+    params.lbl_smooth / params.clip_grad and kept on the model for the following epochs). Every step is then one call of it (a
+    replay of the captured step once it is warm), the per-step losses stay on the device, and the epoch reads them ONCE at its
+    end into the same RunningAverage; needs fused_loss=True. None (the default): the loop below, unchanged."""
     from . import _native
     model.train()
     loss_avg = RunningAverage()
@@ -48,6 +52,18 @@ def train_device_labels(model, queries, index, graph, optimizer, params, batch_s
     queries = queries.to(dev)
     order = torch.randperm(queries.size(0), generator=generator).to(dev)
     n_ent = model.entity_embedding.size(0)
+    if captured is not None and captured is not False:
+        if not fused_loss:
+            raise _native.NativeError('train_device_labels: a captured step is the fused_loss=True step')
+        step = _captured_step(model, graph, index, optimizer, params) if captured is True else captured
+        starts = range(0, queries.size(0), batch_size)
+        losses = torch.empty(len(starts), dtype=torch.float32, device=dev)
+        for k, i in enumerate(starts):
+            q = queries.index_select(0, order[i:i + batch_size])
+            losses[k].copy_(step(q[:, 0], q[:, 1]))     # (the step's loss tensor is overwritten by the next call)
+        for v in losses.tolist():                        # the epoch's one host read
+            loss_avg.update(v)
+        return loss_avg()
     for i in range(0, queries.size(0), batch_size):
         q = queries.index_select(0, order[i:i + batch_size])
         optimizer.zero_grad()
@@ -65,6 +81,17 @@ def train_device_labels(model, queries, index, graph, optimizer, params, batch_s
             optimizer.step()
         loss_avg.update(loss.item())
     return loss_avg()
+
+
+def _captured_step(model, graph, index, optimizer, params):
+    """The CapturedTrainStep of train_device_labels(captured=True): built once per (graph, index, optimizer) and kept on the model."""
+    from .captured import CapturedTrainStep
+    hit = getattr(model, '_captured_train_step', None)
+    if hit is None or hit.graph is not graph or hit.index is not index or hit.optimizer is not optimizer:
+        hit = CapturedTrainStep(model, graph, index, optimizer)
+        object.__setattr__(model, '_captured_train_step', hit)
+    hit.lbl_smooth, hit.clip = float(params.lbl_smooth), params.clip_grad
+    return hit
 
 
 def ranks_from_scores(pred, label, obj):

@@ -35,6 +35,24 @@ def _capturing(t):
     return t.is_cuda and torch.cuda.is_current_stream_capturing()
 
 
+def _key_arg(k):
+    """A dropout key as the autograd functions keep it: a plain int, or the device form as it is."""
+    return k if isinstance(k, _native.DeviceKey) else int(k)
+
+
+def _site_key(drop_ctx, site):
+    """The key of `site` at drop_ctx = (seed, step): the 64-bit key by value. While a captured.CapturedTrainStep captures, the
+    context carries a third entry, the one-word device tensor that holds dropout_step_key(seed, step) before every replay: the
+    key is then the device form (_native.DeviceKey), which the kernels finish themselves, so a replay draws its own step's masks."""
+    if len(drop_ctx) > 2:
+        return _native.DeviceKey(drop_ctx[2], site)
+    return _native.dropout_key(drop_ctx[0], drop_ctx[1], site)
+
+
+def _word_of(drop_ctx):
+    return drop_ctx[2] if len(drop_ctx) > 2 else None
+
+
 class _AggregateFn(torch.autograd.Function):
     """A[:, :D] / A[:, D:2D] = in-/out-half aggregates; gradients by the HIP backward kernels."""
 
@@ -74,7 +92,7 @@ class _LayerTrainFn(torch.autograd.Function):
         ctx.inv_keep = 1.0
         ctx.drop = None
         if drop_keys is not None and p_drop > 0:      # counter-based: the bits are recomputed in the backward, nothing is saved
-            ctx.drop = (int(drop_keys[0]), int(drop_keys[1]), int(drop_keys[2]), float(p_drop))
+            ctx.drop = (_key_arg(drop_keys[0]), _key_arg(drop_keys[1]), int(drop_keys[2]), float(p_drop))
             _native.dropout_apply_pair(u_in, ctx.drop[0], u_out, ctx.drop[1], ctx.drop[2], ctx.drop[3], out_a=u_in, out_b=u_out)
         elif p_drop >= 1.0:                       # F.dropout(p=1) is all zeros (1 / keep would be 0 / 0)
             m_in = torch.zeros(u_in.shape, dtype=torch.bool, device=u_in.device)
@@ -222,7 +240,7 @@ class _CounterDropoutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, key, row0, p):
-        ctx.args = (int(key), int(row0), float(p))
+        ctx.args = (_key_arg(key), int(row0), float(p))
         x = x if _native.dropout_supported(x) else x.contiguous()
         return _native.dropout_apply(x, *ctx.args)
 
@@ -232,11 +250,13 @@ class _CounterDropoutFn(torch.autograd.Function):
         return _native.dropout_apply(g, *ctx.args), None, None, None
 
 
-def counter_dropout(x, p, seed, step, site, row0=0):
-    """x [rows, cols] through the counter-based dropout of site `site` at (seed, step); p <= 0 launches nothing."""
+def counter_dropout(x, p, seed, step, site, row0=0, step_key_dev=None):
+    """x [rows, cols] through the counter-based dropout of site `site` at (seed, step); p <= 0 launches nothing. `step_key_dev`
+    (a one-word int64 device tensor, see _site_key): the device-key form, which reads the step from that word when it runs."""
     if p <= 0 or x.numel() == 0:
         return x
-    return _CounterDropoutFn.apply(x, _native.dropout_key(seed, step, site), row0, p)
+    ctx = (seed, step) if step_key_dev is None else (seed, step, step_key_dev)
+    return _CounterDropoutFn.apply(x, _site_key(ctx, site), row0, p)
 
 
 class _ScoreFn(torch.autograd.Function):
@@ -499,7 +519,7 @@ class ConvE(nn.Module):
     def _counter_keep(self, drop_ctx, site, shape, p, device):
         """(bool keep-mask, inv_keep) of a trunk site from the counter-based definition (row = batch row): what the kernels of
         csrc/conve_train.hip and csrc/query_train.hip take in place of a bernoulli_ draw."""
-        key = _native.dropout_key(drop_ctx[0], drop_ctx[1], site)
+        key = _site_key(drop_ctx, site)
         return _native.dropout_mask(shape[0], shape[1], key, 0, p, device=device), _native.dropout_scale(p)[1]
 
     def _trunk_train(self, src_emb, rel_emb, generator, drop_ctx=None):
@@ -561,7 +581,7 @@ class ConvE(nn.Module):
             self._tail_train_count = getattr(self, '_tail_train_count', 0) + 1
             return x
         if drop_ctx is not None:
-            x = counter_dropout(z, self.hidden_drop.p, drop_ctx[0], drop_ctx[1], _native.DROPOUT_SITE_HIDDEN)
+            x = counter_dropout(z, self.hidden_drop.p, drop_ctx[0], drop_ctx[1], _native.DROPOUT_SITE_HIDDEN, step_key_dev=_word_of(drop_ctx))
         else:
             x = _drawn_dropout(z, self.hidden_drop.p, generator) if drawn else self.hidden_drop(z)
         return F.relu(self.bn2(x)).contiguous()
@@ -592,7 +612,8 @@ class ConvE(nn.Module):
         stack = stack.transpose(2, 1).reshape(-1, 1, 2 * self.params.k_w, self.params.k_h)
         x = F.relu(self.bn1(self.conv_e(self.bn0(stack))))
         if drop_ctx is not None:      # the feature site's row is the batch row, its columns the flat_sz features of that row
-            x = counter_dropout(x.reshape(-1, self.flat_sz), self.feature_drop.p, drop_ctx[0], drop_ctx[1], _native.DROPOUT_SITE_FEATURE)
+            x = counter_dropout(x.reshape(-1, self.flat_sz), self.feature_drop.p, drop_ctx[0], drop_ctx[1], _native.DROPOUT_SITE_FEATURE,
+                                step_key_dev=_word_of(drop_ctx))
         else:
             x = self.feature_drop(x)
         return self._tail(self.fc(x.view(-1, self.flat_sz)), generator, False, drop_ctx)
@@ -640,6 +661,7 @@ class MGCN(nn.Module):
         # the reference's); dropout_state() / load_dropout_state() carry them in a checkpoint
         self.dropout_seed = int(getattr(params, 'dropout_seed', 0))
         self.dropout_step = 0
+        self._step_key_dev = None  # set by captured.CapturedTrainStep for the duration of a capture only
         self._optimizers = weakref.WeakSet()   # optimizers whose per-row state follows the tables' layout (attach_optimizer)
         self._edge_shard = None    # (csr, n0, n1) once dist.shard_model_tables has filled a partial table
         self._slot_csr = None      # per-edge tables are stored in this CSR's slot order (None = reference order)
@@ -775,11 +797,13 @@ class MGCN(nn.Module):
     def _begin_dropout_step(self):
         """(seed, step) for ONE training-mode encode / train_step_sharded call with the counter-based dropout on, else None: every
         site of the call, the trunk's included, uses this step; the step counter then advances. The ConvE trunk finds the pair in
-        conv2._drop_ctx and consumes it."""
+        conv2._drop_ctx and consumes it. While a captured step is being captured the context is (seed, step, device step word)."""
         if not self.training or not _counter_dropout_wanted(self.params) or not self.entity_embedding.is_cuda:
             self.conv2._drop_ctx = None
             return None
         ctx = (self.dropout_seed, self.dropout_step)
+        if self._step_key_dev is not None:     # a CapturedTrainStep is capturing: every site takes the device-key form (_site_key)
+            ctx += (self._step_key_dev,)
         self.dropout_step += 1
         self.conv2._drop_ctx = ctx
         return ctx
@@ -799,13 +823,9 @@ class MGCN(nn.Module):
             data._mgcn_facts = facts
         return facts[1], facts[2]
 
-    def encode(self, data):
-        """model.py:25-34: (all_ent [N, O], all_rel [2R, O]) for the whole graph.
-
-        Eval mode without autograd ("frozen") adds two things the reference does not have, both result-neutral:
-        the whole layer stack is replayed from a captured hipGraph (the step is ~6 short launches, so host launch
-        cost would otherwise dominate), and — unless params.cache_encoder is False — the result is kept until a
-        parameter, a BN statistic or the graph changes (SURVEY N1: main.py:117-121 recomputes it per batch, Q4)."""
+    def _layout_for(self, data):
+        """(csr, ent_identity, edge_identity) of `data`, with the per-edge tables brought into the layout its layers read: what
+        every encode does first (captured.CapturedTrainStep does it before a replay, which runs no Python of the step)."""
         edge_type, edge_ids = data.edge_attr
         ent_identity, edge_identity = self._graph_facts(data)
         num_rel_rows = self.relation_embedding.size(0) + 1
@@ -818,7 +838,16 @@ class MGCN(nn.Module):
             self._use_slot_order(csr)
         elif self._slot_csr is not None:
             self._use_reference_order()      # this graph gathers rows by edge id: the tables must be in reference order
+        return csr, ent_identity, edge_identity
 
+    def encode(self, data):
+        """model.py:25-34: (all_ent [N, O], all_rel [2R, O]) for the whole graph.
+
+        Eval mode without autograd ("frozen") adds two things the reference does not have, both result-neutral:
+        the whole layer stack is replayed from a captured hipGraph (the step is ~6 short launches, so host launch
+        cost would otherwise dominate), and — unless params.cache_encoder is False — the result is kept until a
+        parameter, a BN statistic or the graph changes (SURVEY N1: main.py:117-121 recomputes it per batch, Q4)."""
+        csr, ent_identity, edge_identity = self._layout_for(data)
         frozen = not self.training and not torch.is_grad_enabled()
         if not frozen:
             return self._encode_layers(data, csr, ent_identity, edge_identity, self._begin_dropout_step())
@@ -846,11 +875,12 @@ class MGCN(nn.Module):
             ee = table if edge_identity else torch.index_select(table, 0, edge_ids)
             keys = None
             if drop_ctx is not None:      # counter-based masks: rows are entity ids, the whole graph starts at row 0
-                keys = tuple(_native.dropout_key(drop_ctx[0], drop_ctx[1], _native.dropout_layer_site(li, w)) for w in (0, 1)) + (0,)
+                keys = tuple(_site_key(drop_ctx, _native.dropout_layer_site(li, w)) for w in (0, 1)) + (0,)
             x, rel = layer(x, data.edge_index, edge_type, getattr(data, 'edge_norm', None), ee, rel, csr=csr,
                            ee_in_slot_order=edge_identity, drop_keys=keys)
             if drop_ctx is not None:
-                x = counter_dropout(x, self.params.gcn_drop, drop_ctx[0], drop_ctx[1], _native.dropout_layer_site(li, 2))
+                x = counter_dropout(x, self.params.gcn_drop, drop_ctx[0], drop_ctx[1], _native.dropout_layer_site(li, 2),
+                                    step_key_dev=_word_of(drop_ctx))
             else:
                 x = F.dropout(x, p=self.params.gcn_drop, training=self.training)
         return x, rel

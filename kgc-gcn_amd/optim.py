@@ -77,9 +77,21 @@ class ClipAdam(torch.optim.Adam):
             state['step'] = state['step'].cpu()       # the step on the host, where reading it waits for nothing)
         return state
 
+    @staticmethod
+    def _step_hyper(group, step):
+        """(step_size, bc2_sqrt) of `group` at step count `step`, in Python doubles as torch's single-tensor Adam forms them: the
+        two scalars of kernel (3) that change from step to step. The eager update passes them by value; a captured step writes
+        the same doubles, rounded to float, into the device buffer its launches read (hyper_values)."""
+        beta1, beta2 = group['betas']
+        step_size = group['lr'] / (1 - beta1 ** step)
+        bc2_sqrt = (1 - beta2 ** step) ** 0.5
+        return step_size, bc2_sqrt
+
     def _hip_update(self, plan, coef):
-        """Kernel (3) over the plan: one call per (group, step count), hyperparameters read from the group now."""
+        """Kernel (3) over the plan: one call per (group, step count), hyperparameters read from the group now. Between
+        begin_device_hyper and end_device_hyper the launches read (step_size, bc2_sqrt) from one row of the device buffer each."""
         touched = []
+        dev = self._device_hyper
         for group, ps in plan:
             beta1, beta2 = group['betas']
             by_step = {}
@@ -88,15 +100,51 @@ class ClipAdam(torch.optim.Adam):
                 state['step'] += 1
                 by_step.setdefault(float(state['step']), []).append((p, state))
             for step, items in by_step.items():
-                step_size = group['lr'] / (1 - beta1 ** step)           # in double, as torch's single-tensor Adam
-                bc2_sqrt = (1 - beta2 ** step) ** 0.5
+                step_size, bc2_sqrt = self._step_hyper(group, step)
+                row = None
+                if dev is not None:
+                    buf, rows = dev
+                    if len(rows) >= buf.size(0):
+                        raise _native.NativeError('ClipAdam: the device hyper buffer has %d rows, the step needs more (one per group '
+                                                  'and step count)' % buf.size(0))
+                    row = buf[len(rows)]
+                    rows.append((group, [s for _, s in items]))
                 _native.adam_step([p.grad for p, _ in items], [p for p, _ in items], [s['exp_avg'] for _, s in items],
                                   [s['exp_avg_sq'] for _, s in items], coef, step_size, bc2_sqrt, beta1, beta2, group['eps'],
-                                  group['weight_decay'])
+                                  group['weight_decay'], hyper_dev=row)
             touched += ps
         if touched:                                   # written through raw pointers: tell autograd and every (_version, ...) stamp
             torch.autograd.graph.increment_version(touched)
         self._hip_step_count += 1
+
+    # -- a captured step (captured.CapturedTrainStep) ------------------------------------------------
+    _device_hyper = None
+
+    def begin_device_hyper(self, buf):
+        """From now until end_device_hyper, clip_and_step / step launch the device form of kernel (3): call k (one per group and
+        step count, in the order _hip_update issues them) reads (step_size, bc2_sqrt) from row k of `buf`, a contiguous f32
+        [rows, 2] device tensor, when it RUNS. Meant for the one pass that is captured into a graph."""
+        if buf.dim() != 2 or buf.size(1) != 2 or buf.dtype != torch.float32 or not buf.is_cuda or not buf.is_contiguous():
+            raise _native.NativeError('ClipAdam.begin_device_hyper: a contiguous f32 [rows, 2] device tensor is required')
+        self._device_hyper = (buf, [])
+
+    def end_device_hyper(self):
+        """Back to by-value scalars. Returns the rows the launches in between were bound to: [(group, [state, ...])]."""
+        rows, self._device_hyper = ([] if self._device_hyper is None else self._device_hyper[1]), None
+        return rows
+
+    def hyper_values(self, rows):
+        """[(step_size, bc2_sqrt)] that the NEXT step's launches of `rows` must find in the buffer: _step_hyper at each row's step
+        count + 1, from the groups' hyperparameters as they are now (so a scheduler's lr takes effect)."""
+        return [self._step_hyper(group, float(states[0]['step']) + 1) for group, states in rows]
+
+    def advance_steps(self, rows):
+        """What one replayed step leaves on the host: every row's state['step'] + 1 and the kernel-path counter, no launch."""
+        for _, states in rows:
+            for state in states:
+                state['step'] += 1
+        self._hip_step_count += 1
+        self._opt_called = True
 
     # -- public ----------------------------------------------------------------------------------
     @torch.no_grad()
