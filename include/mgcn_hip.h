@@ -341,6 +341,51 @@ int mgcn_pack_weights_gen(int32_t generation, int32_t dim_in, int32_t dim_out, c
 size_t mgcn_packed_weights_bytes_gen(int32_t generation, int32_t dim_in, int32_t dim_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * (2e) The forward launches on a bf16 per-edge table — inference only, additive (MGCN_ABI_VERSION stays 4, as with the _dev
+ * entry points of (10) and (12)). ee_dev [2E, D] (or a destination range's shard) holds bf16 values as uint16_t, non-NULL;
+ * every other argument is that of the f32 sibling of (2) / (2b).
+ *   bf16(v)   = the f32 value v rounded to nearest even to 16 bits (torch: tensor.to(torch.bfloat16));
+ *   widen(h)  = the f32 whose bit pattern is uint32(h) << 16 (exact).
+ * CONTRACT: a launch given the bf16 table T computes exactly what its f32 sibling computes from the f32 table widen(T): the
+ * same products in the same order by the same instructions, bit-identical rows. Only the per-edge row's load differs: 2 bytes
+ * per element instead of 4, then a shift. Alignment: the vector paths want ee_dev 8-byte aligned (D % 4 == 0 makes every row
+ * so); mgcn_aggregate_fwd_ee16 takes a table that is only 2-byte aligned on its element-wise path (as the f32 launch takes a
+ * misaligned operand), the fused launches return MGCN_EUNSUPPORTED. Generations 2 and 3 read the bf16 table, on the
+ * canonical layout and on the live view; generation 4 forced through `tune` returns MGCN_EUNSUPPORTED. The hub pre-pass
+ * reads the same table. There is no backward: (3) and (3s) take f32 tables only (a bf16 table is a deployment form of a
+ * trained model). */
+int mgcn_aggregate_fwd_ee16(int64_t num_nodes, int64_t num_edges_half, int32_t dim, int32_t num_rel_rows,
+                            const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev, const float *x_dev, int64_t ldx,
+                            const float *rel_dev, const float *loop_rel_dev, const uint16_t *ee_dev,
+                            int32_t ee_in_slot_order, const float *loop_edge_dev, float *a_dev, int64_t lda,
+                            int64_t node_begin, int64_t node_end, const int32_t *hubinfo_dev, const int32_t *chunks_dev,
+                            int64_t chunk_begin, int64_t chunk_end, float *partial_dev, int64_t ee_sub_in,
+                            int64_t ee_sub_out, int64_t ee_sub_hub, void *stream);
+int mgcn_layer_fwd_fused_ee16(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out,
+                              int32_t num_rel_rows, const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev,
+                              const float *x_dev, int64_t ldx, const float *rel_dev, const float *loop_rel_dev,
+                              const uint16_t *ee_dev, int32_t ee_in_slot_order, const float *loop_edge_dev,
+                              const float *wp_dev, const float *bias_dev, const float *bn_mean_dev,
+                              const float *bn_var_dev, const float *bn_gamma_dev, const float *bn_beta_dev,
+                              float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin, int64_t node_end,
+                              int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub, const int32_t *hubinfo_dev,
+                              const int32_t *chunks_dev, int64_t chunk_begin, int64_t chunk_end, float *partial_dev,
+                              const float *rels_weight_dev, float *rel_out_dev, const int32_t *row_bounds_dev,
+                              int32_t num_row_bounds, int32_t tune, uint32_t *status_dev, void *stream);
+int mgcn_layer_fwd_fused_live_ee16(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out,
+                                   int32_t num_rel_rows, const int32_t *live_rowptr_dev,
+                                   const mgcn_edge_rec *live_rec_dev, const mgcn_edge_rec *rec_dev, const float *x_dev,
+                                   int64_t ldx, const float *rel_dev, const float *loop_rel_dev, const uint16_t *ee_dev,
+                                   int32_t ee_in_slot_order, const float *loop_edge_dev, const float *wp_dev,
+                                   const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev,
+                                   const float *bn_gamma_dev, const float *bn_beta_dev, float bn_eps, float *out_dev,
+                                   int64_t ldo, int64_t node_begin, int64_t node_end, int64_t ee_sub_in,
+                                   int64_t ee_sub_out, int64_t ee_sub_hub, const int32_t *hubinfo_dev,
+                                   const int32_t *chunks_dev, int64_t chunk_begin, int64_t chunk_end, float *partial_dev,
+                                   const float *rels_weight_dev, float *rel_out_dev, const int32_t *row_bounds_dev,
+                                   int32_t num_row_bounds, int32_t tune, uint32_t *status_dev, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (4t) The layer's epilogue in TRAINING mode and its backward (model.py:103-106 under .train(), driven by main.py:61-66):
  *   z = (u_in + u_out + u_loop) / 3 (+ bias)        u_* [N, O] = the three products of model.py:116, dropout already applied
  *   y = tanh((z - mean) * rstd * gamma + beta)      mean / rstd = BATCH statistics over the N rows (biased variance),

@@ -46,6 +46,16 @@ _SIGNATURES = {
                                                  _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i64, _i64, _i64,
                                                  _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr,
                                                  _ptr]),
+    'mgcn_aggregate_fwd_ee16': (ctypes.c_int, [_i64, _i64, _i32, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
+                                               _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr]),
+    'mgcn_layer_fwd_fused_ee16': (ctypes.c_int, [_i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
+                                                 _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i64, _i64, _i64,
+                                                 _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr,
+                                                 _ptr]),
+    'mgcn_layer_fwd_fused_live_ee16': (ctypes.c_int, [_i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
+                                                      _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i64, _i64, _i64,
+                                                      _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr,
+                                                      _ptr]),
     'mgcn_csr_live_view_host': (ctypes.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     'mgcn_pack_weights': (ctypes.c_int, [_i32, _i32, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_packed_weights_bytes': (ctypes.c_size_t, [_i32, _i32]),
@@ -176,6 +186,18 @@ def _same_device(*ts):
         raise NativeError('tensors on different devices: %s' % sorted(map(str, devs)))
 
 
+def is_ee16(ee):
+    """A per-edge table held in bf16 (include/mgcn_hip.h (2e)): the forward launches take their _ee16 entry points, which compute
+    what the f32 launch computes from ee.float(), bit for bit; there is no backward (inference only)."""
+    return ee is not None and ee.dtype == torch.bfloat16
+
+
+def _refuse_ee16(ee, what):
+    if is_ee16(ee):
+        raise NativeError('%s: the per-edge table is bf16, which is inference-only (include/mgcn_hip.h (2e)): the backward '
+                          'entry points take f32 tables' % what)
+
+
 # ------------------------------------------------------------------------------------------------
 # slots per (half, destination) above which it is a hub. 32: below a gather group's fair share of an FB15k-237 tile (~42 slots per
 # half and stage), so that no single row outlasts its stage; measured on that shape's step: 64 -> 0.323, 48 -> 0.311, 32 -> 0.303, 24 -> 0.314,
@@ -279,7 +301,8 @@ def aggregate_fwd(csr, x, rel, ee, ee_in_slot_order, loop_edge, out, loop_rel=No
     `loop_rel` [D] given separately, its first num_rel_rows-1 rows (no concatenation needed).
     With `node_range` = (n0, n1), `ee` may be that range's shard of the slot-ordered table
     (graph.GraphCSR.edge_table_shard) and `ee_sub` its three slot offsets (GraphCSR.shard_ee_sub). `out_row0`: `out`
-    holds rows [out_row0, out_row0 + out.size(0)) of the aggregate (the kernel indexes rows by global node id)."""
+    holds rows [out_row0, out_row0 + out.size(0)) of the aggregate (the kernel indexes rows by global node id).
+    A bf16 `ee` takes mgcn_aggregate_fwd_ee16: the rows of the f32 launch on ee.float(), bit for bit."""
     N, E, D = csr.num_nodes, csr.num_edges_half, x.size(1)
     _same_device(csr.rowptr, x, rel, ee, loop_edge, out, loop_rel)
     if loop_rel is None:
@@ -311,13 +334,14 @@ def aggregate_fwd(csr, x, rel, ee, ee_in_slot_order, loop_edge, out, loop_rel=No
                 ee_sub != csr.shard_ee_sub(n0, n1):
             raise NativeError('aggregate_fwd: per-edge shard does not match destinations [%d, %d)' % (n0, n1))
         if ee.numel() == 0:
-            ee = x.new_zeros((1, D))
+            ee = torch.zeros((1, D), dtype=ee.dtype, device=x.device)
     hub_info, hub_chunks, hub_c0, hub_c1, hub_partial = _hub_args(csr, D, x.device, n0, n1)
-    rc = lib().mgcn_aggregate_fwd(
+    ee16 = is_ee16(ee)
+    rc = (lib().mgcn_aggregate_fwd_ee16 if ee16 else lib().mgcn_aggregate_fwd)(
         N, E, D, csr.num_rel_rows, _dev(csr.rowptr, torch.int32, 'rowptr'), _dev(csr.rec, torch.int32, 'rec'),
         _dev(x, torch.float32, 'x'), _ld(x), _dev(rel, torch.float32, 'rel'), _dev(loop_rel, torch.float32, 'loop_rel'),
-        _dev(ee, torch.float32, 'ee', True), int(bool(ee_in_slot_order)), _dev(loop_edge, torch.float32, 'loop_edge', True),
-        _dev(out, torch.float32, 'out') - out_row0 * _ld(out) * 4, _ld(out), n0, n1, hub_info, hub_chunks, hub_c0, hub_c1,
+        _dev(ee, torch.bfloat16 if ee16 else torch.float32, 'ee', True), int(bool(ee_in_slot_order)),
+        _dev(loop_edge, torch.float32, 'loop_edge', True), _dev(out, torch.float32, 'out') - out_row0 * _ld(out) * 4, _ld(out), n0, n1, hub_info, hub_chunks, hub_c0, hub_c1,
         _dev(hub_partial, torch.float32, 'partial', True), ee_sub[0], ee_sub[1], ee_sub[2], _stream(x))
     if rc != 0 and hub_partial is not None:
         _hub_failed(csr, D, x.device, n0, n1)
@@ -342,6 +366,7 @@ def _bwd_out(out, i, want, shape, device, what):
 def aggregate_bwd(csr, x, rel, ee, g, want_gx=True, want_gee=True, want_grel=True, out=None):
     """(3) Gradients of aggregate_fwd's first 2D columns w.r.t. x, the per-edge table (slot order) and rel. `out` =
     (gx, gee, grel): tensors to write instead of fresh ones (contiguous, entries may be None)."""
+    _refuse_ee16(ee, 'aggregate_bwd')
     N, E, D = csr.num_nodes, csr.num_edges_half, x.size(1)
     _same_device(csr.rowptr, x, rel, ee, g)
     if not csr.has_backward:
@@ -384,6 +409,7 @@ def aggregate_bwd_shard(csr, x, rel, ee, g, node_range, want_gx=True, out=None):
     gee [shard rows, D] complete, grel [num_rel_rows, D] partial): summed over the ranks of a partition, gx / grel are
     aggregate_bwd's (bit-identical with one range covering the graph). `out` = (gx, gee, grel): tensors to write instead
     of fresh ones (contiguous, entries may be None)."""
+    _refuse_ee16(ee, 'aggregate_bwd_shard')
     N, E, D = csr.num_nodes, csr.num_edges_half, x.size(1)
     n0, n1 = int(node_range[0]), int(node_range[1])
     _same_device(csr.rowptr, x, rel, ee, g)
@@ -526,7 +552,9 @@ def layer_fwd_fused(csr, x, rel, loop_rel, ee, ee_in_slot_order, loop_edge, w_pa
     CU, None when equal runs are balanced already); results do not depend on it.
     `live`: walk the graph's live view (GraphCSR.live_rowptr / live_rec: zero-norm slots left out; bit-identical rows for
     finite inputs). None = whenever the graph has one and MGCN_LIVE_SLOTS is not 0; False = the canonical launch; True raises
-    where there is no view to walk."""
+    where there is no view to walk.
+    A bf16 `ee` takes the _ee16 entry points (generations 2 and 3): the rows of the f32 launch on ee.float(), bit for bit; a
+    forced generation 4 raises FusedUnsupported."""
     N, E, D, O = csr.num_nodes, csr.num_edges_half, x.size(1), int(d_out)
     n0, n1 = (0, N) if node_range is None else (int(node_range[0]), int(node_range[1]))
     if not 0 <= n0 <= n1 <= N:
@@ -562,7 +590,7 @@ def layer_fwd_fused(csr, x, rel, loop_rel, ee, ee_in_slot_order, loop_edge, w_pa
     if n1 == n0 and rel_out is None:
         return out                                   # an empty destination range: nothing to launch
     if ee is not None and ee.numel() == 0:           # a range whose destinations have no slots: the kernel still wants
-        ee = x.new_zeros((1, D))                     # a valid (never read) table pointer
+        ee = torch.zeros((1, D), dtype=ee.dtype, device=x.device)   # a valid (never read) table pointer
     hub_info, hub_chunks, hub_c0, hub_c1, hub_partial = _hub_args(csr, D, x.device, n0, n1)
     bounds = csr.workgroup_bounds(n0, n1, _cu_count(x.device)) if balance and n1 > n0 else None
     # the graph's live view (zero-norm slots left out) whenever it has one: same rows for finite inputs, fewer row loads
@@ -570,16 +598,19 @@ def layer_fwd_fused(csr, x, rel, loop_rel, ee, ee_in_slot_order, loop_edge, w_pa
     if live and not has_view:
         raise NativeError('layer_fwd_fused: live=True, but this graph has no live view (no dead slot) or tune forces generation 4')
     live = has_view and (LIVE_SLOTS if live is None else bool(live))
+    ee16 = is_ee16(ee)
     if live:
-        fn, head = lib().mgcn_layer_fwd_fused_live, (_dev(csr.live_rowptr, torch.int32, 'live_rowptr'),
-                                                     _dev(csr.live_rec, torch.int32, 'live_rec'), _dev(csr.rec, torch.int32, 'rec'))
+        fn = lib().mgcn_layer_fwd_fused_live_ee16 if ee16 else lib().mgcn_layer_fwd_fused_live
+        head = (_dev(csr.live_rowptr, torch.int32, 'live_rowptr'), _dev(csr.live_rec, torch.int32, 'live_rec'),
+                _dev(csr.rec, torch.int32, 'rec'))
     else:
-        fn, head = lib().mgcn_layer_fwd_fused, (_dev(csr.rowptr, torch.int32, 'rowptr'), _dev(csr.rec, torch.int32, 'rec'))
+        fn = lib().mgcn_layer_fwd_fused_ee16 if ee16 else lib().mgcn_layer_fwd_fused
+        head = (_dev(csr.rowptr, torch.int32, 'rowptr'), _dev(csr.rec, torch.int32, 'rec'))
     rc = fn(
         N, E, D, O, csr.num_rel_rows, *head,
         _dev(x, torch.float32, 'x'), _ld(x), _dev(rel, torch.float32, 'rel'), _dev(loop_rel, torch.float32, 'loop_rel'),
-        _dev(ee, torch.float32, 'ee', True), int(bool(ee_in_slot_order)), _dev(loop_edge, torch.float32, 'loop_edge'),
-        _dev(w_packed, torch.float32, 'w_packed'), _dev(bias, torch.float32, 'bias', True),
+        _dev(ee, torch.bfloat16 if ee16 else torch.float32, 'ee', True), int(bool(ee_in_slot_order)),
+        _dev(loop_edge, torch.float32, 'loop_edge'), _dev(w_packed, torch.float32, 'w_packed'), _dev(bias, torch.float32, 'bias', True),
         _dev(bn_mean, torch.float32, 'bn_mean'), _dev(bn_var, torch.float32, 'bn_var'),
         _dev(bn_gamma, torch.float32, 'bn_gamma'), _dev(bn_beta, torch.float32, 'bn_beta'), float(eps),
         _dev(out, torch.float32, 'out'), _ld(out), n0, n1, int(ee_sub[0]), int(ee_sub[1]), int(ee_sub[2]),

@@ -95,6 +95,9 @@ class CapturedTrainStep(object):
     def _refuse(self, src):
         """The reasons not to capture at all: raised (NativeError) before anything is captured."""
         m, opt = self.model, self.optimizer
+        if _native.is_ee16(m.edge_embeddings):
+            raise _native.NativeError('CapturedTrainStep: this model holds its per-edge tables in bf16 (params.edge_table_dtype), '
+                                      'which is inference-only')
         if not m.entity_embedding.is_cuda:
             raise _native.NativeError('CapturedTrainStep: the model is on the CPU; the training step runs on a GPU only')
         if m._edge_shard is not None:

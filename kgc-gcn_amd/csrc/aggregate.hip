@@ -10,6 +10,8 @@
 // HBM-bound integer/float streaming work: nothing here is reshaped into a GEMM.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "mgcn_common.h"
 
 namespace {
@@ -21,6 +23,12 @@ struct Vec<4> {
   using type = float4;
   static __device__ __forceinline__ float4 zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
   static __device__ __forceinline__ float4 load(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+  // four bf16 values (one 8-byte load), each widened exactly: the f32 whose bits are uint32(h) << 16
+  static __device__ __forceinline__ float4 load(const uint16_t *p) {
+    const uint2 h = *reinterpret_cast<const uint2 *>(p);
+    return make_float4(__uint_as_float(h.x << 16), __uint_as_float(h.x & 0xffff0000u), __uint_as_float(h.y << 16),
+                       __uint_as_float(h.y & 0xffff0000u));
+  }
   static __device__ __forceinline__ void store(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
   // agent-scope accesses (write-through / cache-bypassing: coherent across the XCDs' L2s inside a launch)
   static __device__ __forceinline__ float4 load_agent(const float *p) {
@@ -46,6 +54,7 @@ struct Vec<1> {
   using type = float;
   static __device__ __forceinline__ float zero() { return 0.f; }
   static __device__ __forceinline__ float load(const float *p) { return *p; }
+  static __device__ __forceinline__ float load(const uint16_t *p) { return __uint_as_float(uint32_t(*p) << 16); }
   static __device__ __forceinline__ void store(float *p, float v) { *p = v; }
   static __device__ __forceinline__ float load_agent(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   static __device__ __forceinline__ void store_agent(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -60,7 +69,7 @@ struct AggArgs {
   const float *x;
   const float *rel;       // rows [0, rel_rows-1)
   const float *loop_rel;  // row rel_rows-1
-  const float *ee;        // may be null
+  const float *ee;        // may be null; a bf16 table (the EE16 kernels) rides in the same field
   const float *loop_edge;
   float *a;
   int64_t ldx, lda;
@@ -80,14 +89,17 @@ struct AggArgs {
 // batch b + 1 are in flight while batch b is added up (two register sets). The loop body is free of branches around loads (slot index
 // clamped to the run's last slot, column clamped to the row's last chunk, the relation / self-loop row chosen by offset; only the adds
 // are predicated), so the compiler counts the outstanding loads (`vmcnt(N)`) instead of draining them at every merge of two paths.
-template <int VEC, int CPL, int U, bool ROLL>
+// EE16: the per-edge table holds bf16 (include/mgcn_hip.h (2e)): the row's load is 2 bytes per element and a shift, the value that
+// enters the product is the exactly widened one, and everything else is the f32 walk's.
+template <int VEC, int CPL, int U, bool ROLL, bool EE16>
 __device__ __forceinline__ void walk_slots(const AggArgs &p, int first, int end, int64_t ee_sub, const int (&col)[CPL],
                                            int lane_in_group, int gs, typename Vec<VEC>::type (&acc)[CPL]) {
   using V = Vec<VEC>;
   using T = typename V::type;
   const int last = end - 1;
   const int64_t loop_off = p.loop_rel - p.rel;    // the self-loop row as an offset from the relation table
-  const float *ee = p.ee ? p.ee : p.x;            // no per-edge table: a valid address, the value is not used
+  using ET = typename std::conditional<EE16, uint16_t, float>::type;
+  const ET *ee = reinterpret_cast<const ET *>(p.ee ? p.ee : p.x);   // no per-edge table: a valid address, the value is not used
   const bool has_ee = p.ee != nullptr;
   for (int beg = first; beg < end; beg += 2 * gs) {
     const int stop = min(beg + 2 * gs, end);
@@ -107,7 +119,7 @@ __device__ __forceinline__ void walk_slots(const AggArgs &p, int first, int end,
         wt[u] = __int_as_float(r.z);
         const float *xr = p.x + int64_t(r.x) * p.ldx;
         const float *rr = p.rel + ((r.y < p.rel_rows - 1) ? int64_t(r.y) * p.d : loop_off);
-        const float *er = ee + (has_ee ? (p.ee_slot_order ? int64_t(s) - ee_sub : int64_t(r.w)) * p.d : int64_t(0));
+        const ET *er = ee + (has_ee ? (p.ee_slot_order ? int64_t(s) - ee_sub : int64_t(r.w)) * p.d : int64_t(0));
 #pragma unroll
         for (int c = 0; c < CPL; ++c) {
           xv[u][c] = V::load(xr + col[c]);
@@ -149,7 +161,7 @@ __device__ __forceinline__ void walk_slots(const AggArgs &p, int first, int end,
 // GS lanes per group (power of two <= 64), CPL column chunks per lane, U slots per batch (two batches in flight per group): one group
 // per (mode, destination); a short run (WN18RR: 2.1 slots on average) costs three dependent memory round trips in total — row
 // pointers, records, rows.
-template <int VEC, int CPL, int U, bool ROLL = false>
+template <int VEC, int CPL, int U, bool ROLL = false, bool EE16 = false>
 __global__ __launch_bounds__(256) void agg_fwd_kernel(AggArgs p, int gs_log2) {
   using V = Vec<VEC>;
   using T = typename V::type;
@@ -180,7 +192,7 @@ __global__ __launch_bounds__(256) void agg_fwd_kernel(AggArgs p, int gs_log2) {
 #pragma unroll
   for (int c = 0; c < CPL; ++c) acc[c] = V::zero();
   const int32_t *rp = p.rowptr + int64_t(mode) * (p.n + 1);   // absolute slot positions
-  walk_slots<VEC, CPL, U, ROLL>(p, rp[node], rp[node + 1], p.ee_sub[mode], col, lane_in_group, gs, acc);
+  walk_slots<VEC, CPL, U, ROLL, EE16>(p, rp[node], rp[node + 1], p.ee_sub[mode], col, lane_in_group, gs, acc);
   if (p.hubinfo) {  // a hub's own segment above is empty: its total was folded into the row of its first chunk
     const int2 hi = p.hubinfo[int64_t(mode) * p.n + node];
     if (hi.y > 0) {
@@ -251,7 +263,7 @@ __device__ __forceinline__ void hub_fold_rows(float *rows, int count, int64_t rs
 // Hub pre-pass: one lane group per chunk of a hub destination's slots; same arithmetic and slot order (walk_slots). There are few
 // groups (~4 waves per CU on the FB15k-237 shape), each a chain of dependent round trips kept short by the walk's record windows and
 // its rolling prefetch.
-template <int VEC, int CPL, int U, int OCC = 1>
+template <int VEC, int CPL, int U, int OCC = 1, bool EE16 = false>
 __global__ __launch_bounds__(256, OCC) void agg_hub_kernel(AggArgs p, int gs_log2) {
   using V = Vec<VEC>;
   using T = typename V::type;
@@ -267,7 +279,7 @@ __global__ __launch_bounds__(256, OCC) void agg_hub_kernel(AggArgs p, int gs_log
   T acc[CPL];
 #pragma unroll
   for (int c = 0; c < CPL; ++c) acc[c] = V::zero();
-  walk_slots<VEC, CPL, U, true>(p, range.x, range.y, p.ee_sub_hub, col, lane_in_group, gs, acc);
+  walk_slots<VEC, CPL, U, true, EE16>(p, range.x, range.y, p.ee_sub_hub, col, lane_in_group, gs, acc);
 #pragma unroll
   for (int c = 0; c < CPL; ++c) {
     const int ch = lane_in_group + c * gs;
@@ -956,17 +968,18 @@ void launch_fold(const Geometry &g, const int4 *chunks, float *partial, int32_t 
 
 int mgcn::launch_hub_partials(int64_t num_nodes, int32_t dim, int32_t num_rel_rows, const mgcn_edge_rec *rec_dev,
                               const float *x_dev, int64_t ldx, const float *rel_dev, const float *loop_rel_dev,
-                              const float *ee_dev, int32_t ee_in_slot_order, int64_t ee_sub_hub,
+                              const void *ee_dev, int32_t ee_in_slot_order, int64_t ee_sub_hub,
                               const int32_t *chunks_dev, int64_t chunk_begin, int64_t chunk_end, float *partial_dev,
-                              void *stream) {
+                              void *stream, bool ee16) {
   const int64_t num_chunks = chunk_end - chunk_begin;
   const bool aligned = mgcn::aligned16(x_dev) && mgcn::aligned16(rel_dev) && mgcn::aligned16(loop_rel_dev) &&
-                       mgcn::aligned16(partial_dev) && (!ee_dev || mgcn::aligned16(ee_dev)) && ldx % 4 == 0;
+                       mgcn::aligned16(partial_dev) && (!ee_dev || (ee16 ? mgcn::aligned8(ee_dev) : mgcn::aligned16(ee_dev))) &&
+                       ldx % 4 == 0;
   Geometry g;
   if (!pick_geometry(dim, aligned, &g)) return mgcn::fail(MGCN_EUNSUPPORTED, "hub partials: dim %d too wide", dim);
   AggArgs p = {};
   p.rec = reinterpret_cast<const int4 *>(rec_dev);
-  p.x = x_dev; p.rel = rel_dev; p.loop_rel = loop_rel_dev; p.ee = ee_dev;
+  p.x = x_dev; p.rel = rel_dev; p.loop_rel = loop_rel_dev; p.ee = static_cast<const float *>(ee_dev);
   p.ldx = ldx; p.n = int32_t(num_nodes); p.d = dim; p.rel_rows = num_rel_rows; p.ee_slot_order = ee_in_slot_order;
   p.chunks = reinterpret_cast<const int4 *>(chunks_dev);
   p.partial = partial_dev;
@@ -977,7 +990,11 @@ int mgcn::launch_hub_partials(int64_t num_nodes, int32_t dim, int32_t num_rel_ro
   const int64_t threads = num_chunks << g.gs_log2;
   const unsigned grid = unsigned((threads + 255) / 256);
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define MGCN_HUB_CASE(V_, C_, U_) hipLaunchKernelGGL((agg_hub_kernel<V_, C_, U_>), dim3(grid), dim3(256), 0, st, p, g.gs_log2)
+#define MGCN_HUB_CASE(V_, C_, U_)                                                                                   \
+  do {                                                                                                              \
+    if (ee16) hipLaunchKernelGGL((agg_hub_kernel<V_, C_, U_, 1, true>), dim3(grid), dim3(256), 0, st, p, g.gs_log2); \
+    else hipLaunchKernelGGL((agg_hub_kernel<V_, C_, U_>), dim3(grid), dim3(256), 0, st, p, g.gs_log2);              \
+  } while (0)
   if (g.vec == 4) {
     switch (g.cpl) {
       case 1: MGCN_HUB_CASE(4, 1, 4); break;
@@ -1002,13 +1019,13 @@ extern "C" int64_t mgcn_hub_partial_floats(int64_t num_chunks, int32_t dim) {
   return num_chunks > 0 && dim > 0 ? num_chunks * dim + 2 * num_chunks : 0;
 }
 
-extern "C" int mgcn_aggregate_fwd(int64_t num_nodes, int64_t num_edges_half, int32_t dim, int32_t num_rel_rows,
-                                  const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev, const float *x_dev,
-                                  int64_t ldx, const float *rel_dev, const float *loop_rel_dev, const float *ee_dev,
-                                  int32_t ee_in_slot_order, const float *loop_edge_dev, float *a_dev, int64_t lda,
-                                  int64_t node_begin, int64_t node_end, const int32_t *hubinfo_dev,
-                                  const int32_t *chunks_dev, int64_t chunk_begin, int64_t chunk_end, float *partial_dev,
-                                  int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub, void *stream) {
+namespace {
+// Both entry points; ee16: ee_dev is a bf16 table (include/mgcn_hip.h (2e))
+int aggregate_fwd(int64_t num_nodes, int64_t num_edges_half, int32_t dim, int32_t num_rel_rows, const int32_t *rowptr_dev,
+                  const mgcn_edge_rec *rec_dev, const float *x_dev, int64_t ldx, const float *rel_dev, const float *loop_rel_dev,
+                  const void *ee_dev, bool ee16, int32_t ee_in_slot_order, const float *loop_edge_dev, float *a_dev, int64_t lda,
+                  int64_t node_begin, int64_t node_end, const int32_t *hubinfo_dev, const int32_t *chunks_dev, int64_t chunk_begin,
+                  int64_t chunk_end, float *partial_dev, int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub, void *stream) {
   MGCN_REQUIRE(num_nodes >= 0 && num_edges_half >= 0 && dim > 0 && num_rel_rows > 0, "aggregate_fwd: bad sizes");
   MGCN_REQUIRE((ee_sub_in == 0 && ee_sub_out == 0 && ee_sub_hub == 0) || (ee_dev && ee_in_slot_order),
                "aggregate_fwd: table shard offsets need a per-edge table in slot order");
@@ -1026,7 +1043,7 @@ extern "C" int mgcn_aggregate_fwd(int64_t num_nodes, int64_t num_edges_half, int
                "aggregate_fwd: hub chunks need hubinfo / chunks / a 16-byte aligned partial buffer");
   if (node_end == node_begin) return MGCN_OK;
   const bool aligned = mgcn::aligned16(x_dev) && mgcn::aligned16(rel_dev) && mgcn::aligned16(loop_rel_dev) &&
-                       mgcn::aligned16(a_dev) && (!ee_dev || mgcn::aligned16(ee_dev)) &&
+                       mgcn::aligned16(a_dev) && (!ee_dev || (ee16 ? mgcn::aligned8(ee_dev) : mgcn::aligned16(ee_dev))) &&
                        (!loop_edge_dev || mgcn::aligned16(loop_edge_dev)) && ldx % 4 == 0 && lda % 4 == 0;
   Geometry g;
   if (!pick_geometry(dim, aligned, &g)) return mgcn::fail(MGCN_EUNSUPPORTED, "aggregate_fwd: dim %d too wide", dim);
@@ -1036,7 +1053,7 @@ extern "C" int mgcn_aggregate_fwd(int64_t num_nodes, int64_t num_edges_half, int
   p.x = x_dev;
   p.rel = rel_dev;
   p.loop_rel = loop_rel_dev;
-  p.ee = ee_dev;
+  p.ee = static_cast<const float *>(ee_dev);
   p.loop_edge = loop_edge_dev;
   p.a = a_dev;
   p.ldx = ldx;
@@ -1058,14 +1075,19 @@ extern "C" int mgcn_aggregate_fwd(int64_t num_nodes, int64_t num_edges_half, int
   p.ee_sub[0] = ee_sub_in; p.ee_sub[1] = ee_sub_out;
   if (num_chunks > 0) {
     if (int rc = mgcn::launch_hub_partials(num_nodes, dim, num_rel_rows, rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev,
-                                           ee_in_slot_order, ee_sub_hub, chunks_dev, chunk_begin, chunk_end, partial_dev, stream))
+                                           ee_in_slot_order, ee_sub_hub, chunks_dev, chunk_begin, chunk_end, partial_dev, stream,
+                                           ee16))
       return rc;
   }
   {
     const int64_t threads = (int64_t(modes) * p.nodes) << g.gs_log2;
     const unsigned grid = unsigned((threads + 255) / 256);
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define MGCN_FWD_CASE(V_, C_, U_) hipLaunchKernelGGL((agg_fwd_kernel<V_, C_, U_>), dim3(grid), dim3(256), 0, st, p, g.gs_log2)
+#define MGCN_FWD_CASE(V_, C_, U_)                                                                                       \
+  do {                                                                                                                  \
+    if (ee16) hipLaunchKernelGGL((agg_fwd_kernel<V_, C_, U_, false, true>), dim3(grid), dim3(256), 0, st, p, g.gs_log2); \
+    else hipLaunchKernelGGL((agg_fwd_kernel<V_, C_, U_>), dim3(grid), dim3(256), 0, st, p, g.gs_log2);                  \
+  } while (0)
     if (g.vec == 4) {
       switch (g.cpl) {
         case 1:
@@ -1091,6 +1113,33 @@ extern "C" int mgcn_aggregate_fwd(int64_t num_nodes, int64_t num_edges_half, int
   }
   MGCN_CHECK_LAUNCH("agg_fwd_kernel");
   return MGCN_OK;
+}
+}  // namespace
+
+extern "C" int mgcn_aggregate_fwd(int64_t num_nodes, int64_t num_edges_half, int32_t dim, int32_t num_rel_rows,
+                                  const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev, const float *x_dev,
+                                  int64_t ldx, const float *rel_dev, const float *loop_rel_dev, const float *ee_dev,
+                                  int32_t ee_in_slot_order, const float *loop_edge_dev, float *a_dev, int64_t lda,
+                                  int64_t node_begin, int64_t node_end, const int32_t *hubinfo_dev,
+                                  const int32_t *chunks_dev, int64_t chunk_begin, int64_t chunk_end, float *partial_dev,
+                                  int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub, void *stream) {
+  return aggregate_fwd(num_nodes, num_edges_half, dim, num_rel_rows, rowptr_dev, rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev,
+                       false, ee_in_slot_order, loop_edge_dev, a_dev, lda, node_begin, node_end, hubinfo_dev, chunks_dev, chunk_begin,
+                       chunk_end, partial_dev, ee_sub_in, ee_sub_out, ee_sub_hub, stream);
+}
+
+// (2e) The same launch on a bf16 per-edge table
+extern "C" int mgcn_aggregate_fwd_ee16(int64_t num_nodes, int64_t num_edges_half, int32_t dim, int32_t num_rel_rows,
+                                       const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev, const float *x_dev,
+                                       int64_t ldx, const float *rel_dev, const float *loop_rel_dev, const uint16_t *ee_dev,
+                                       int32_t ee_in_slot_order, const float *loop_edge_dev, float *a_dev, int64_t lda,
+                                       int64_t node_begin, int64_t node_end, const int32_t *hubinfo_dev,
+                                       const int32_t *chunks_dev, int64_t chunk_begin, int64_t chunk_end, float *partial_dev,
+                                       int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub, void *stream) {
+  MGCN_REQUIRE(ee_dev, "aggregate_fwd_ee16: null per-edge table");
+  return aggregate_fwd(num_nodes, num_edges_half, dim, num_rel_rows, rowptr_dev, rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev,
+                       true, ee_in_slot_order, loop_edge_dev, a_dev, lda, node_begin, node_end, hubinfo_dev, chunks_dev, chunk_begin,
+                       chunk_end, partial_dev, ee_sub_in, ee_sub_out, ee_sub_hub, stream);
 }
 
 static void launch_grel_final(const Geometry &g, const BwdArgs &p, int32_t num_rel_rows, int32_t dim, hipStream_t st) {

@@ -32,7 +32,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct LayerArgs {
   const int32_t *rowptr;
   const int4 *rec;
-  const float *x, *rel, *loop_rel, *ee, *loop_edge;
+  const float *x, *rel, *loop_rel, *ee, *loop_edge;   // ee: a bf16 table rides in the same field (the EE16 kernels)
   const u32x4 *wp;        // packed weights [k-block][column tile][3][64] (8 bf16 per lane), the generation's packing kernel
   const float *bias, *bn_mean, *bn_var, *bn_gamma, *bn_beta;
   float *out;
@@ -49,7 +49,7 @@ struct LayerArgs {
 
 inline void fill_layer_args(LayerArgs &p, const mgcn::FusedLaunch &a) {
   p.rowptr = a.rowptr; p.rec = reinterpret_cast<const int4 *>(a.rec);
-  p.x = a.x; p.rel = a.rel; p.loop_rel = a.loop_rel; p.ee = a.ee; p.loop_edge = a.loop_edge;
+  p.x = a.x; p.rel = a.rel; p.loop_rel = a.loop_rel; p.ee = static_cast<const float *>(a.ee); p.loop_edge = a.loop_edge;
   p.wp = reinterpret_cast<const u32x4 *>(a.wp);
   p.bias = a.bias; p.bn_mean = a.bn_mean; p.bn_var = a.bn_var; p.bn_gamma = a.bn_gamma; p.bn_beta = a.bn_beta;
   p.out = a.out; p.ldx = a.ldx; p.ldo = a.ldo;
@@ -78,6 +78,16 @@ __device__ __forceinline__ void split3p(float v0, float v1, uint32_t &h, uint32_
   m = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
   const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
   l = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{s0, s1}, bf16x2));
+}
+// A lane's four values of a per-edge row. The f32 table: one 16-byte load. The bf16 table (include/mgcn_hip.h (2e)): one 8-byte
+// load, each value widened exactly — the f32 whose bits are uint32(h) << 16.
+template <bool EE16> struct EeElem { using type = float; };
+template <> struct EeElem<true> { using type = uint16_t; };
+__device__ __forceinline__ float4 load_ee4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ float4 load_ee4(const uint16_t *p) {
+  const uint2 h = *reinterpret_cast<const uint2 *>(p);
+  return make_float4(__uint_as_float(h.x << 16), __uint_as_float(h.x & 0xffff0000u), __uint_as_float(h.y << 16),
+                     __uint_as_float(h.y & 0xffff0000u));
 }
 __device__ __forceinline__ float4 f4mul(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 __device__ __forceinline__ float4 f4axpy(float4 s, float4 m, float w) {

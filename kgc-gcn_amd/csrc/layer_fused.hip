@@ -68,12 +68,12 @@ extern "C" int mgcn_fused_kernel_generation(int32_t dim_in, int32_t dim_out, int
 }
 
 namespace {
-// Both entry points. live_rowptr_dev / live_rec_dev: the live view the main walk takes (null: the canonical layout); the hub
-// pre-pass reads the canonical records either way.
+// All four entry points. live_rowptr_dev / live_rec_dev: the live view the main walk takes (null: the canonical layout); the hub
+// pre-pass reads the canonical records either way. ee16: ee_dev is a bf16 table (include/mgcn_hip.h (2e)).
 int layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out, int32_t num_rel_rows,
                     const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev, const int32_t *live_rowptr_dev,
                     const mgcn_edge_rec *live_rec_dev, const float *x_dev, int64_t ldx, const float *rel_dev,
-                    const float *loop_rel_dev, const float *ee_dev, int32_t ee_in_slot_order, const float *loop_edge_dev,
+                    const float *loop_rel_dev, const void *ee_dev, bool ee16, int32_t ee_in_slot_order, const float *loop_edge_dev,
                     const float *wp_dev, const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev,
                     const float *bn_gamma_dev, const float *bn_beta_dev, float bn_eps, float *out_dev, int64_t ldo,
                     int64_t node_begin, int64_t node_end, int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub,
@@ -90,11 +90,11 @@ int layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, i
                    (num_edges_half == 0 || rec_dev), "layer_fwd_fused: null pointer");
   MGCN_REQUIRE(ldx >= dim_in && ldo >= dim_out, "layer_fwd_fused: ldx/ldo too small");
   const bool aligned = mgcn::aligned16(x_dev) && mgcn::aligned16(rel_dev) && mgcn::aligned16(loop_rel_dev) &&
-                       mgcn::aligned16(loop_edge_dev) && (!ee_dev || mgcn::aligned16(ee_dev)) &&
+                       mgcn::aligned16(loop_edge_dev) && (!ee_dev || (ee16 ? mgcn::aligned8(ee_dev) : mgcn::aligned16(ee_dev))) &&
                        mgcn::aligned16(out_dev) && mgcn::aligned16(wp_dev) && ldx % 4 == 0 && ldo % 4 == 0;
   if (!aligned || !mgcn::fused3_takes(dim_in, dim_out) || !ee_dev || !ee_in_slot_order || ldx >= (int64_t(1) << 31))
-    return mgcn::fail(MGCN_EUNSUPPORTED, "layer_fwd_fused: needs 16-byte aligned operands, a per-edge table in slot order, "
-                      "D %% 4 == 0, D <= 1024, O %% 4 == 0, O <= 512 (got D=%d O=%d)", dim_in, dim_out);
+    return mgcn::fail(MGCN_EUNSUPPORTED, "layer_fwd_fused: needs 16-byte aligned operands (a bf16 per-edge table: 8-byte), a "
+                      "per-edge table in slot order, D %% 4 == 0, D <= 1024, O %% 4 == 0, O <= 512 (got D=%d O=%d)", dim_in, dim_out);
   const int64_t num_chunks = chunk_end - chunk_begin;
   MGCN_REQUIRE(chunk_begin >= 0 && num_chunks >= 0 && chunk_end < (int64_t(1) << 31) &&
                    (num_chunks == 0 || (hubinfo_dev && chunks_dev && partial_dev && mgcn::aligned16(partial_dev))),
@@ -105,7 +105,7 @@ int layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, i
   if (num_chunks > 0 && node_end > node_begin) {
     if (int rc = mgcn::launch_hub_partials(num_nodes, dim_in, num_rel_rows, rec_dev, x_dev, ldx, rel_dev, loop_rel_dev,
                                            ee_dev, ee_in_slot_order, ee_sub_hub, chunks_dev, chunk_begin, chunk_end,
-                                           partial_dev, stream))
+                                           partial_dev, stream, ee16))
       return rc;
   }
   // tune bits 10-11: 0 = the launch's own kernel; 1 / 2 / 3 force generation 4 / 2 / 3 (A/B runs; wp_dev must be packed for it:
@@ -118,6 +118,8 @@ int layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, i
                dim_in, dim_out);
   MGCN_REQUIRE(num_row_bounds >= 0 && num_row_bounds <= 4096 && (num_row_bounds == 0 || row_bounds_dev),
                "layer_fwd_fused: bad row bounds");
+  if (ee16 && gen == 4)
+    return mgcn::fail(MGCN_EUNSUPPORTED, "layer_fwd_fused: tune %d: generation 4 does not read a bf16 per-edge table", tune);
   const bool live = live_rowptr_dev != nullptr;
   MGCN_REQUIRE(!live || gen != 4, "layer_fwd_fused: tune %d: generation 4 does not walk a live view", tune);
   const mgcn::FusedLaunch a = {num_nodes, dim_in, dim_out, num_rel_rows, live ? live_rowptr_dev : rowptr_dev,
@@ -125,7 +127,7 @@ int layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, i
                                loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev, bn_gamma_dev, bn_beta_dev, bn_eps, out_dev, ldo,
                                node_begin, node_end, ee_sub_in, ee_sub_out, num_chunks > 0 ? hubinfo_dev : nullptr, chunk_begin,
                                partial_dev, want_rel ? rels_weight_dev : nullptr, want_rel ? rel_out_dev : nullptr, row_bounds_dev,
-                               num_row_bounds, tune, status_dev, stream, live};
+                               num_row_bounds, tune, status_dev, stream, live, ee16};
   if (gen == 4) return mgcn::fused4_launch(a);
   if (gen == 2) return mgcn::fused2_launch(a);
   return mgcn::fused3_launch(a);
@@ -145,7 +147,7 @@ extern "C" int mgcn_layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, i
                                     float *rel_out_dev, const int32_t *row_bounds_dev, int32_t num_row_bounds,
                                     int32_t tune, uint32_t *status_dev, void *stream) {
   return layer_fwd_fused(num_nodes, num_edges_half, dim_in, dim_out, num_rel_rows, rowptr_dev, rec_dev, nullptr, nullptr, x_dev, ldx,
-                         rel_dev, loop_rel_dev, ee_dev, ee_in_slot_order, loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev,
+                         rel_dev, loop_rel_dev, ee_dev, false, ee_in_slot_order, loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev,
                          bn_gamma_dev, bn_beta_dev, bn_eps, out_dev, ldo, node_begin, node_end, ee_sub_in, ee_sub_out, ee_sub_hub,
                          hubinfo_dev, chunks_dev, chunk_begin, chunk_end, partial_dev, rels_weight_dev, rel_out_dev, row_bounds_dev,
                          num_row_bounds, tune, status_dev, stream);
@@ -166,7 +168,48 @@ extern "C" int mgcn_layer_fwd_fused_live(int64_t num_nodes, int64_t num_edges_ha
                                          int32_t num_row_bounds, int32_t tune, uint32_t *status_dev, void *stream) {
   MGCN_REQUIRE(live_rowptr_dev && live_rec_dev, "layer_fwd_fused_live: null live view");
   return layer_fwd_fused(num_nodes, num_edges_half, dim_in, dim_out, num_rel_rows, live_rowptr_dev, rec_dev, live_rowptr_dev,
-                         live_rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev, ee_in_slot_order, loop_edge_dev, wp_dev, bias_dev,
+                         live_rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev, false, ee_in_slot_order, loop_edge_dev, wp_dev, bias_dev,
+                         bn_mean_dev, bn_var_dev, bn_gamma_dev, bn_beta_dev, bn_eps, out_dev, ldo, node_begin, node_end, ee_sub_in,
+                         ee_sub_out, ee_sub_hub, hubinfo_dev, chunks_dev, chunk_begin, chunk_end, partial_dev, rels_weight_dev,
+                         rel_out_dev, row_bounds_dev, num_row_bounds, tune, status_dev, stream);
+}
+
+// (2e) The same two launches on a bf16 per-edge table
+extern "C" int mgcn_layer_fwd_fused_ee16(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out,
+                                         int32_t num_rel_rows, const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev,
+                                         const float *x_dev, int64_t ldx, const float *rel_dev, const float *loop_rel_dev,
+                                         const uint16_t *ee_dev, int32_t ee_in_slot_order, const float *loop_edge_dev,
+                                         const float *wp_dev, const float *bias_dev, const float *bn_mean_dev,
+                                         const float *bn_var_dev, const float *bn_gamma_dev, const float *bn_beta_dev,
+                                         float bn_eps, float *out_dev, int64_t ldo, int64_t node_begin, int64_t node_end,
+                                         int64_t ee_sub_in, int64_t ee_sub_out, int64_t ee_sub_hub,
+                                         const int32_t *hubinfo_dev, const int32_t *chunks_dev, int64_t chunk_begin,
+                                         int64_t chunk_end, float *partial_dev, const float *rels_weight_dev,
+                                         float *rel_out_dev, const int32_t *row_bounds_dev, int32_t num_row_bounds,
+                                         int32_t tune, uint32_t *status_dev, void *stream) {
+  MGCN_REQUIRE(ee_dev, "layer_fwd_fused_ee16: null per-edge table");
+  return layer_fwd_fused(num_nodes, num_edges_half, dim_in, dim_out, num_rel_rows, rowptr_dev, rec_dev, nullptr, nullptr, x_dev, ldx,
+                         rel_dev, loop_rel_dev, ee_dev, true, ee_in_slot_order, loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev,
+                         bn_gamma_dev, bn_beta_dev, bn_eps, out_dev, ldo, node_begin, node_end, ee_sub_in, ee_sub_out, ee_sub_hub,
+                         hubinfo_dev, chunks_dev, chunk_begin, chunk_end, partial_dev, rels_weight_dev, rel_out_dev, row_bounds_dev,
+                         num_row_bounds, tune, status_dev, stream);
+}
+
+extern "C" int mgcn_layer_fwd_fused_live_ee16(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out,
+                                              int32_t num_rel_rows, const int32_t *live_rowptr_dev,
+                                              const mgcn_edge_rec *live_rec_dev, const mgcn_edge_rec *rec_dev, const float *x_dev,
+                                              int64_t ldx, const float *rel_dev, const float *loop_rel_dev, const uint16_t *ee_dev,
+                                              int32_t ee_in_slot_order, const float *loop_edge_dev, const float *wp_dev,
+                                              const float *bias_dev, const float *bn_mean_dev, const float *bn_var_dev,
+                                              const float *bn_gamma_dev, const float *bn_beta_dev, float bn_eps, float *out_dev,
+                                              int64_t ldo, int64_t node_begin, int64_t node_end, int64_t ee_sub_in,
+                                              int64_t ee_sub_out, int64_t ee_sub_hub, const int32_t *hubinfo_dev,
+                                              const int32_t *chunks_dev, int64_t chunk_begin, int64_t chunk_end, float *partial_dev,
+                                              const float *rels_weight_dev, float *rel_out_dev, const int32_t *row_bounds_dev,
+                                              int32_t num_row_bounds, int32_t tune, uint32_t *status_dev, void *stream) {
+  MGCN_REQUIRE(live_rowptr_dev && live_rec_dev && ee_dev, "layer_fwd_fused_live_ee16: null live view or per-edge table");
+  return layer_fwd_fused(num_nodes, num_edges_half, dim_in, dim_out, num_rel_rows, live_rowptr_dev, rec_dev, live_rowptr_dev,
+                         live_rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev, true, ee_in_slot_order, loop_edge_dev, wp_dev, bias_dev,
                          bn_mean_dev, bn_var_dev, bn_gamma_dev, bn_beta_dev, bn_eps, out_dev, ldo, node_begin, node_end, ee_sub_in,
                          ee_sub_out, ee_sub_hub, hubinfo_dev, chunks_dev, chunk_begin, chunk_end, partial_dev, rels_weight_dev,
                          rel_out_dev, row_bounds_dev, num_row_bounds, tune, status_dev, stream);

@@ -55,7 +55,9 @@ constexpr int REL_LDS_MAX_BYTES = 32 * 1024;
 
 // LIVE: rowptr / rec are the graph's live view (include/mgcn_hip.h (1v)): zero-norm slots are left out, and a record's fourth
 // word is its canonical slot index — the per-edge row, where the canonical walk takes the slot position itself.
-template <int NT, int NRT, bool RELLDS, bool HUBS, bool LIVE>
+// EE16: the per-edge table holds bf16 (include/mgcn_hip.h (2e)): the lane's four values of a per-edge row are one 8-byte load,
+// widened exactly (load_ee4); the partition, the record chunks, the batches and the order of the loads are the f32 walk's.
+template <int NT, int NRT, bool RELLDS, bool HUBS, bool LIVE, bool EE16 = false>
 __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
   constexpr int BM = NRT * 16;
   constexpr int PIECE = 16 * BM * 16;   // bytes of one bf16 piece of a stage image: 16 chunk columns x BM rows x 16 B
@@ -196,7 +198,8 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
             const int coff_ = chunk * 128 + lig * 4;
             const bool col_ok = coff_ < p.d;
             const int coff = col_ok ? coff_ : 0;   // lanes past the row width repeat columns 0-3 and store zeros
-            const float *xb = p.x + coff, *relb = (RELLDS ? rel_lds : p.rel) + coff, *eeb = p.ee + coff;
+            const float *xb = p.x + coff, *relb = (RELLDS ? rel_lds : p.rel) + coff;
+            const typename EeElem<EE16>::type *eeb = reinterpret_cast<const typename EeElem<EE16>::type *>(p.ee) + coff;
             int4 myrec = firstrec;
             int row = e_lo, nb = __shfl(myrp, glane0 + 1);
             float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
                 if (!RELLDS) rv[u] = *reinterpret_cast<const float4 *>(relb + uint64_t(uint32_t(rtyp[u])) * d32);
                 const int pos = (s + u < end) ? s + u : end - 1;   // the per-edge row: the slot itself, or (LIVE) the record's fourth word
                 const uint32_t erow = MGCN_ABLATE(16) ? 0u : uint32_t((LIVE ? __shfl(myrec.w, glane0 + (pos - cbase)) : pos) - ee_sub_mode);
-                ev[u] = *reinterpret_cast<const float4 *>(eeb + uint64_t(erow) * d32);
+                ev[u] = load_ee4(eeb + uint64_t(erow) * d32);
               }
 #ifdef MGCN_DIAG
               if (wave == 8 && stage == 1 && bstamp < 126) { MGCN_STAMP(1, bstamp); ++bstamp; }   // batch loads issued
@@ -514,14 +517,14 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
   }
 }
 
-template <int NT, int NRT, bool RELLDS, bool HUBS, bool LIVE>
+template <int NT, int NRT, bool RELLDS, bool HUBS, bool LIVE, bool EE16>
 int launch2(const Args2 &p, int grid, hipStream_t st) {
   constexpr size_t lds_bytes = size_t(2) * 3 * 16 * (NRT * 16) * 16 + EPI_FLOATS * 4 + (RELLDS ? REL_LDS_MAX_BYTES : 0);
   // (the attribute is sticky per device and setting it costs microseconds: done on every launch, no state kept)
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused2_kernel<NT, NRT, RELLDS, HUBS, LIVE>),
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused2_kernel<NT, NRT, RELLDS, HUBS, LIVE, EE16>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)) != hipSuccess)
     return mgcn::fail(MGCN_ELAUNCH, "layer_fused2: cannot reserve %zu bytes of LDS", lds_bytes);
-  hipLaunchKernelGGL((layer_fused2_kernel<NT, NRT, RELLDS, HUBS, LIVE>), dim3(unsigned(grid)), dim3(T2), lds_bytes, st, p);
+  hipLaunchKernelGGL((layer_fused2_kernel<NT, NRT, RELLDS, HUBS, LIVE, EE16>), dim3(unsigned(grid)), dim3(T2), lds_bytes, st, p);
   MGCN_CHECK_LAUNCH("layer_fused2_kernel");
   return MGCN_OK;
 }
@@ -529,19 +532,19 @@ int launch2(const Args2 &p, int grid, hipStream_t st) {
 int pick_nt2(int o) { return o <= 32 ? 2 : o <= 64 ? 4 : o <= 128 ? 8 : 13; }
 
 // NT = 13 (the 200-wide layers) has all variants; narrower outputs take the general one
-template <bool LIVE>
+template <bool LIVE, bool EE16>
 int pick2(const Args2 &p, int dim_out, int nrt, int grid, int grid5, bool rel_lds, bool hubs, hipStream_t st) {
   switch (pick_nt2(dim_out)) {
-    case 2: return launch2<2, 5, false, true, LIVE>(p, grid5, st);
-    case 4: return launch2<4, 5, false, true, LIVE>(p, grid5, st);
-    case 8: return launch2<8, 5, false, true, LIVE>(p, grid5, st);
+    case 2: return launch2<2, 5, false, true, LIVE, EE16>(p, grid5, st);
+    case 4: return launch2<4, 5, false, true, LIVE, EE16>(p, grid5, st);
+    case 8: return launch2<8, 5, false, true, LIVE, EE16>(p, grid5, st);
     default:
       if (nrt == 4) {
-        if (rel_lds) return hubs ? launch2<13, 4, true, true, LIVE>(p, grid, st) : launch2<13, 4, true, false, LIVE>(p, grid, st);
-        return hubs ? launch2<13, 4, false, true, LIVE>(p, grid, st) : launch2<13, 4, false, false, LIVE>(p, grid, st);
+        if (rel_lds) return hubs ? launch2<13, 4, true, true, LIVE, EE16>(p, grid, st) : launch2<13, 4, true, false, LIVE, EE16>(p, grid, st);
+        return hubs ? launch2<13, 4, false, true, LIVE, EE16>(p, grid, st) : launch2<13, 4, false, false, LIVE, EE16>(p, grid, st);
       }
-      if (rel_lds) return hubs ? launch2<13, 5, true, true, LIVE>(p, grid, st) : launch2<13, 5, true, false, LIVE>(p, grid, st);
-      return hubs ? launch2<13, 5, false, true, LIVE>(p, grid, st) : launch2<13, 5, false, false, LIVE>(p, grid, st);
+      if (rel_lds) return hubs ? launch2<13, 5, true, true, LIVE, EE16>(p, grid, st) : launch2<13, 5, true, false, LIVE, EE16>(p, grid, st);
+      return hubs ? launch2<13, 5, false, true, LIVE, EE16>(p, grid, st) : launch2<13, 5, false, false, LIVE, EE16>(p, grid, st);
   }
 }
 
@@ -619,8 +622,11 @@ int fused2_launch(const FusedLaunch &a) {
   // the relation table rides in LDS when it fits beside the stage images (a third of the gather's row loads)
   const bool rel_lds = a.rel && size_t(a.num_rel_rows - 1) * dim_in * 4 <= size_t(REL_LDS_MAX_BYTES);
   const bool hubs = a.hubinfo != nullptr;
-  return a.live ? pick2<true>(p, dim_out, nrt, grid, grid_for(5), rel_lds, hubs, st)
-                : pick2<false>(p, dim_out, nrt, grid, grid_for(5), rel_lds, hubs, st);
+  if (a.ee16)
+    return a.live ? pick2<true, true>(p, dim_out, nrt, grid, grid_for(5), rel_lds, hubs, st)
+                  : pick2<false, true>(p, dim_out, nrt, grid, grid_for(5), rel_lds, hubs, st);
+  return a.live ? pick2<true, false>(p, dim_out, nrt, grid, grid_for(5), rel_lds, hubs, st)
+                : pick2<false, false>(p, dim_out, nrt, grid, grid_for(5), rel_lds, hubs, st);
 }
 
 }  // namespace mgcn

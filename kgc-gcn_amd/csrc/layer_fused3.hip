@@ -74,7 +74,9 @@ __device__ __forceinline__ void signal_add(uint32_t *c, int lane) {
 
 // LIVE: rowptr / rec are the graph's live view (include/mgcn_hip.h (1v)): zero-norm slots are left out, and a record's fourth
 // word is its canonical slot index — the per-edge row, where the canonical walk takes the slot position itself.
-template <int NT, int NRT, int NCH, bool RELLDS, bool LIVE>
+// EE16: the per-edge table holds bf16 (include/mgcn_hip.h (2e)): the lane's four values of a per-edge row are one 8-byte load,
+// widened exactly (load_ee4); the partition, the record chunks, the batches and the order of the loads are the f32 walk's.
+template <int NT, int NRT, int NCH, bool RELLDS, bool LIVE, bool EE16 = false>
 __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
   constexpr int BM = NRT * 16;
   constexpr int UB = 4 / NCH;           // slots per gather batch: 8 row loads of 16 B per lane in flight either way
@@ -310,7 +312,7 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
                 for (int j = 0; j < NCH; ++j) {
                   xv[u][j] = *reinterpret_cast<const float4 *>(p.x + coff[j] + uint64_t(uint32_t(rsrc[u])) * ldx32);
                   if (!RELLDS) rv[u][j] = *reinterpret_cast<const float4 *>(p.rel + coff[j] + uint64_t(uint32_t(rtyp[u])) * d32);
-                  ev[u][j] = *reinterpret_cast<const float4 *>(p.ee + coff[j] + uint64_t(erow) * d32);
+                  ev[u][j] = load_ee4(reinterpret_cast<const typename EeElem<EE16>::type *>(p.ee) + coff[j] + uint64_t(erow) * d32);
                 }
               }
               DIAG_LAP(t_a);
@@ -660,32 +662,38 @@ size_t lds_bytes3(const Shape3 &s, int nrt, int nimg, int nt, size_t rel_bytes) 
   return size_t(3) * s.ncc * (nrt * 16) * 16 + size_t(nimg) * (nrt * 16) * s.ncc * 32 + 64 + size_t(2) * nt * 16 * 4 + rel_bytes;
 }
 
-template <int NT, int NRT, int NCH, bool RELLDS, bool LIVE>
+template <int NT, int NRT, int NCH, bool RELLDS, bool LIVE, bool EE16>
 int launch3(const Args3 &p, int grid, size_t lds, hipStream_t st) {
   // (the attribute is sticky per device and raising it costs a few microseconds: set on every launch, no state kept)
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused3_kernel<NT, NRT, NCH, RELLDS, LIVE>),
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused3_kernel<NT, NRT, NCH, RELLDS, LIVE, EE16>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, int(LDS_MAX)) != hipSuccess)
     return mgcn::fail(MGCN_ELAUNCH, "layer_fused3: cannot reserve %zu bytes of LDS", LDS_MAX);
-  hipLaunchKernelGGL((layer_fused3_kernel<NT, NRT, NCH, RELLDS, LIVE>), dim3(unsigned(grid)), dim3(T3), lds, st, p);
+  hipLaunchKernelGGL((layer_fused3_kernel<NT, NRT, NCH, RELLDS, LIVE, EE16>), dim3(unsigned(grid)), dim3(T3), lds, st, p);
   MGCN_CHECK_LAUNCH("layer_fused3_kernel");
   return MGCN_OK;
 }
 
-template <int NT, int NRT, int NCH>
-int launch3_rel(const Args3 &p, int grid, size_t lds, bool rel_lds, bool live, hipStream_t st) {
+template <int NT, int NRT, int NCH, bool EE16>
+int launch3_live(const Args3 &p, int grid, size_t lds, bool rel_lds, bool live, hipStream_t st) {
   if (live) {
-    if (rel_lds) return launch3<NT, NRT, NCH, true, true>(p, grid, lds, st);
-    return launch3<NT, NRT, NCH, false, true>(p, grid, lds, st);
+    if (rel_lds) return launch3<NT, NRT, NCH, true, true, EE16>(p, grid, lds, st);
+    return launch3<NT, NRT, NCH, false, true, EE16>(p, grid, lds, st);
   }
-  if (rel_lds) return launch3<NT, NRT, NCH, true, false>(p, grid, lds, st);
-  return launch3<NT, NRT, NCH, false, false>(p, grid, lds, st);
+  if (rel_lds) return launch3<NT, NRT, NCH, true, false, EE16>(p, grid, lds, st);
+  return launch3<NT, NRT, NCH, false, false, EE16>(p, grid, lds, st);
+}
+
+template <int NT, int NRT, int NCH>
+int launch3_rel(const Args3 &p, int grid, size_t lds, bool rel_lds, bool live, bool ee16, hipStream_t st) {
+  return ee16 ? launch3_live<NT, NRT, NCH, true>(p, grid, lds, rel_lds, live, st)
+              : launch3_live<NT, NRT, NCH, false>(p, grid, lds, rel_lds, live, st);
 }
 
 template <int NT, int NCH>
-int launch3_nrt(const Args3 &p, int nrt, int grid, size_t lds, bool rel_lds, bool live, hipStream_t st) {
-  if (nrt == 3) return launch3_rel<NT, 3, NCH>(p, grid, lds, rel_lds, live, st);
-  if (nrt == 4) return launch3_rel<NT, 4, NCH>(p, grid, lds, rel_lds, live, st);
-  return launch3_rel<NT, 5, NCH>(p, grid, lds, rel_lds, live, st);
+int launch3_nrt(const Args3 &p, int nrt, int grid, size_t lds, bool rel_lds, bool live, bool ee16, hipStream_t st) {
+  if (nrt == 3) return launch3_rel<NT, 3, NCH>(p, grid, lds, rel_lds, live, ee16, st);
+  if (nrt == 4) return launch3_rel<NT, 4, NCH>(p, grid, lds, rel_lds, live, ee16, st);
+  return launch3_rel<NT, 5, NCH>(p, grid, lds, rel_lds, live, ee16, st);
 }
 
 }  // namespace
@@ -772,11 +780,11 @@ int fused3_launch(const FusedLaunch &a) {
   const size_t lds = lds_bytes3(s, nrt, nimg, nt, rel_lds ? rel_bytes : 0);
   hipStream_t st = static_cast<hipStream_t>(a.stream);
   if (nt == 32) {
-    if (s.nch == 1) return launch3_rel<32, 3, 1>(p, grid, lds, rel_lds, a.live, st);
-    return launch3_rel<32, 3, 2>(p, grid, lds, rel_lds, a.live, st);
+    if (s.nch == 1) return launch3_rel<32, 3, 1>(p, grid, lds, rel_lds, a.live, a.ee16, st);
+    return launch3_rel<32, 3, 2>(p, grid, lds, rel_lds, a.live, a.ee16, st);
   }
-  if (s.nch == 1) return launch3_nrt<13, 1>(p, nrt, grid, lds, rel_lds, a.live, st);
-  return launch3_nrt<13, 2>(p, nrt, grid, lds, rel_lds, a.live, st);
+  if (s.nch == 1) return launch3_nrt<13, 1>(p, nrt, grid, lds, rel_lds, a.live, a.ee16, st);
+  return launch3_nrt<13, 2>(p, nrt, grid, lds, rel_lds, a.live, a.ee16, st);
 }
 
 }  // namespace mgcn

@@ -28,11 +28,12 @@ inline int fail(int code, const char *fmt, ...) {
     if (e_ != hipSuccess) return mgcn::fail(MGCN_ELAUNCH, "%s: %s", name, hipGetErrorString(e_)); \
   } while (0)
 
-// hub pre-pass (aggregate.hip): chunk sums of the hub destinations' slots -> partial_dev [num_chunks, dim]
+// hub pre-pass (aggregate.hip): chunk sums of the hub destinations' slots -> partial_dev [num_chunks, dim]; ee16: ee_dev is a
+// bf16 table (include/mgcn_hip.h (2e))
 int launch_hub_partials(int64_t num_nodes, int32_t dim, int32_t num_rel_rows, const mgcn_edge_rec *rec_dev,
                         const float *x_dev, int64_t ldx, const float *rel_dev, const float *loop_rel_dev,
-                        const float *ee_dev, int32_t ee_in_slot_order, int64_t ee_sub_hub, const int32_t *chunks_dev,
-                        int64_t chunk_begin, int64_t chunk_end, float *partial_dev, void *stream);
+                        const void *ee_dev, int32_t ee_in_slot_order, int64_t ee_sub_hub, const int32_t *chunks_dev,
+                        int64_t chunk_begin, int64_t chunk_end, float *partial_dev, void *stream, bool ee16 = false);
 
 // The validated parameters of one mgcn_layer_fwd_fused call (include/mgcn_hip.h (4): the same names without _dev), filled once by
 // the dispatcher (layer_fused.hip) and read by the generation it picks.
@@ -43,7 +44,9 @@ struct FusedLaunch {
   const mgcn_edge_rec *rec;
   const float *x;
   int64_t ldx;
-  const float *rel, *loop_rel, *ee, *loop_edge;
+  const float *rel, *loop_rel;
+  const void *ee;              // f32, or bf16 when ee16
+  const float *loop_edge;
   const void *wp;
   const float *bias, *bn_mean, *bn_var, *bn_gamma, *bn_beta;
   float bn_eps;
@@ -61,6 +64,7 @@ struct FusedLaunch {
   uint32_t *status;            // generation 3
   void *stream;
   bool live;                   // rowptr / rec are the live view (include/mgcn_hip.h (1v)): generations 2 and 3
+  bool ee16;                   // ee is a bf16 table (include/mgcn_hip.h (2e)): generations 2 and 3
 };
 
 // fused layer, lockstep generation (layer_fused2.hip): D <= 256 and O <= 208 (the shapes whose alternating layers keep
@@ -85,5 +89,6 @@ int fused4_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_de
 int fused4_launch(const FusedLaunch &a);
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 }  // namespace mgcn

@@ -176,7 +176,8 @@ def shard_model_tables(model, csr, n0, n1, source):
     """Fill a model built with params.edge_table_rows = sum(csr.shard_slot_counts(n0, n1)) with the rows of destinations
     [n0, n1): in-half slots, out-half slots, hub slots (slot order). `source(layer, edge_ids) -> rows [len, D]` returns
     table rows by reference edge id — e.g. lambda l, ids: xavier_rows(ids, 2E, D_l, seed + l, device), or a slice of
-    a state dict that is streamed from disk. Nothing of size [2E, D] is allocated."""
+    a state dict that is streamed from disk. Nothing of size [2E, D] is allocated. A model with bf16 tables
+    (params.edge_table_dtype) rounds f32 rows to nearest even on the copy into the shard."""
     (i0, i1), (o0, o1), (h0, h1) = csr._shard_bounds(n0, n1)
     ids = torch.cat([csr.perm[i0:i1], csr.perm[o0:o1], csr.perm[h0:h1]])
     tables = [model.edge_embeddings] + list(model.edge_embeddings_extra)
@@ -790,6 +791,9 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
     forward_loss + backward + clip_grad_norm_ + step bit for bit AT ANY DROPOUT.
     Returns the global loss (0-dim tensor, detached)."""
     import torch.nn.functional as F
+    if _native.is_ee16(model.edge_embeddings):
+        raise _native.NativeError('train_step_sharded: this model holds its per-edge tables in bf16 (params.edge_table_dtype), '
+                                  'which is inference-only')
     csr, ex = _sharded_setup(model, graph, group, 'train_step_sharded')
     n0, n1, W = ex.n0, ex.n1, ex.world
     model.train()

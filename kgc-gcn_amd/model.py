@@ -234,6 +234,15 @@ def _counter_dropout_wanted(params):
     return (os.environ.get('MGCN_DROPOUT') or getattr(params, 'dropout', 'torch')) == 'counter'
 
 
+def edge_table_dtype(params):
+    """torch dtype of the per-edge tables: params.edge_table_dtype = 'bf16' (default 'f32'; MGCN_EE=bf16 | f32 overrides in both
+    directions) builds an INFERENCE-ONLY model that holds them in bf16."""
+    want = os.environ.get('MGCN_EE') or getattr(params, 'edge_table_dtype', 'f32')
+    if want not in ('bf16', 'f32'):
+        raise _native.NativeError('edge_table_dtype must be \'bf16\' or \'f32\' (got %r)' % (want,))
+    return torch.bfloat16 if want == 'bf16' else torch.float32
+
+
 class _CounterDropoutFn(torch.autograd.Function):
     """Dropout of a matrix [rows, cols] whose keep bits are the counter-based ones of csrc/dropout.hip: a pure
     function of (key, row0 + row, col). Forward and backward are the same launch; nothing is saved but the scalars."""
@@ -646,6 +655,11 @@ class MGCN(nn.Module):
         shard_rows = getattr(params, 'edge_table_rows', None)
         table = (lambda d: get_param((2 * num_edges, d))) if shard_rows is None else \
             (lambda d: nn.Parameter(torch.zeros((int(shard_rows), d))))
+        # params.edge_table_dtype = 'bf16' (DESIGN §4.9): the per-edge tables, sharded ones included, are bf16 parameters without
+        # gradients — an inference-only deployment form at half the bytes. Same draws as the f32 model (seeding is unchanged), rounded
+        # to nearest even; same state-dict keys; an f32 checkpoint is rounded as it loads (copy_'s own conversion).
+        if edge_table_dtype(params) == torch.bfloat16:
+            table = (lambda f32_table: lambda d: nn.Parameter(f32_table(d).data.to(torch.bfloat16), requires_grad=False))(table)
         self.edge_embeddings = table(params.gcn_in_dim)
         self.conv1 = MGCNConv(params.gcn_in_dim, params.gcn_out_dim, num_relations * 2)
         self.conv2 = ConvE(params, num_entities)
@@ -747,6 +761,12 @@ class MGCN(nn.Module):
         self._slot_csr = None
         self._enc_cache = None
 
+    def _refuse_training_ee16(self, what):
+        """bf16 per-edge tables are inference-only: raised before any launch of a training-mode call."""
+        if self.training and _native.is_ee16(self.edge_embeddings):
+            raise _native.NativeError('%s: this model holds its per-edge tables in bf16 (params.edge_table_dtype), which is '
+                                      'inference-only; train the f32 model and load its checkpoint into this one' % what)
+
     def _edge_table_ids(self):
         return {id(p) for _, p in self._edge_tables()}
 
@@ -847,6 +867,7 @@ class MGCN(nn.Module):
         the whole layer stack is replayed from a captured hipGraph (the step is ~6 short launches, so host launch
         cost would otherwise dominate), and — unless params.cache_encoder is False — the result is kept until a
         parameter, a BN statistic or the graph changes (main.py:117-121 recomputes it per batch, Q4)."""
+        self._refuse_training_ee16('MGCN.encode')
         csr, ent_identity, edge_identity = self._layout_for(data)
         frozen = not self.training and not torch.is_grad_enabled()
         if not frozen:
@@ -937,6 +958,7 @@ class MGCN(nn.Module):
         `index` is DataLoader.train_index() on the device; the targets are 1 at the known tails of (src, rel), 0
         elsewhere, smoothed as data_loader.py:41-43. Falls back to the two-step form for batch sizes the fused launch
         does not take (B % 4 != 0)."""
+        self._refuse_training_ee16('MGCN.forward_loss')
         all_ent, all_rel = self.encode(data)
         x = self.conv2.trunk(query_rows(self, all_ent, src), query_rows(self, all_rel, rel))
         n_ent = all_ent.size(0)
