@@ -811,6 +811,34 @@ int mgcn_dropout_mask_dev(int64_t rows, int32_t cols, uint8_t *mask_dev, int64_t
 int mgcn_dropout_mask_host(int64_t rows, int32_t cols, uint8_t *mask_host, int64_t ldm, uint64_t key, uint64_t row0,
                            uint32_t threshold);
 
+/* ---------------------------------------------------------------------------------------------
+ * (13) Scores of per-query candidate lists (csrc/dense.hip) — additive, MGCN_ABI_VERSION stays 4. What (5)
+ * answers for the whole table, answered for the entities a caller names: the score of a triple, a short list to re-rank,
+ * sampled negatives, the ids (7) returned. For query b and list position j, with id = cand[b * ldc + j] and o = id - ent_row0:
+ *   0 <= o < n_local   out[b * ldo + j] = sigmoid(ent[o,:] . x[b,:] + bias[o]); with mask_dev given (the bit-packed rows of
+ *                      mgcn_filter_mask for the same shard: bit (o & 31) of mask[b, o >> 5], ldm words per row, the layout
+ *                      and the ent_row0 of (7)) a candidate whose bit is set gets -inf instead;
+ *   any other id       the element of out is LEFT AS IT IS: -1 padding, an id of another shard, any int64 value, negative
+ *                      or huge. No value of cand makes the launch read ent, bias or mask outside the shard (the test is one
+ *                      unsigned comparison of id - ent_row0 against n_local before any of the three is addressed).
+ * Duplicate ids in a row are allowed, each occurrence gets the score. Callers that want (7)'s padding convention pre-fill
+ * out with -inf; shards then write disjoint elements of one block (launch per shard, or all-reduce MAX across ranks).
+ * CONTRACT: the score is the f32 value mgcn_score_fwd produces for the same (x, ent, bias), bit for bit, hence also the
+ * value of mgcn_score_target / mgcn_score_rank / mgcn_score_topk. The arithmetic family is chosen as in (5), by dim and by the
+ * alignment and leading dimensions of x and ent alone (never by cand, out, n_cand or batch): 16-byte aligned operands with
+ * dim % 4 == 0 and dim <= 352 take the six-product bf16 split in (5)'s product order per 32-wide k-block, everything else
+ * the exact-f32 MFMA's k-ordered chain (operands that are not 16-byte aligned or dim % 4 != 0: element-wise guarded loads,
+ * the same summation order).
+ * Launch: one workgroup of four waves per (query, 64 list positions), grid-stride; a wave's MFMA tile is 16 gathered
+ * candidate rows of its query, each row fetched once, the next k-block's loads in flight; no atomics, no workspace.
+ * MGCN_EINVAL, nothing launched: a null x / ent / bias / cand / out, ldc < n_cand, ldo < n_cand, ldx < dim, lde < dim,
+ * ent_row0 < 0, a negative size, dim < 1, batch / n_cand / n_local at or above 2^31 - 64, mask_dev given with
+ * ldm < ceil(n_local / 32). batch == 0, n_cand == 0 or n_local == 0 return MGCN_OK without a launch.
+ */
+int mgcn_score_candidates(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *x_dev,
+                          int64_t ldx, const float *ent_dev, int64_t lde, const float *bias_dev, const int64_t *cand_dev,
+                          int64_t ldc, const uint32_t *mask_dev, int64_t ldm, float *out_dev, int64_t ldo, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,8 @@ _SIGNATURES = {
     'mgcn_score_topk': (ctypes.c_int, [_i32, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _i64,
                                        _ptr, _i64, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_topk_merge': (ctypes.c_int, [_i32, _i32, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _ptr]),
+    'mgcn_score_candidates': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64,
+                                             _ptr, _i64, _ptr]),
     'mgcn_conve_packed_bytes': (ctypes.c_size_t, [_i32] * 5),
     'mgcn_conve_pack': (ctypes.c_int, [_i32] * 5 + [_ptr, _ptr, _ptr, _i64, _ptr] + ([_ptr] * 4 + [_f32]) * 3 +
                         [_ptr, ctypes.c_size_t, _ptr]),
@@ -916,6 +918,36 @@ def topk_merge(scores, ids, k, out=None):
                                  scores.size(1), k, _dev(out_s, torch.float32, 'out scores'),
                                  _dev(out_i, torch.int64, 'out ids'), _stream(scores)), 'mgcn_topk_merge')
     return out_s, out_i
+
+
+def score_candidates(x, ent, bias, cand, mask=None, ent_row0=0, out=None):
+    """(13) Scores [B, K] f32 of the per-query candidate lists cand [B, K] int64 (global entity ids; its row stride is the
+    ABI's ldc): element (b, j) is the f32 value score_fwd gives (b, cand[b, j]) when the id is a row of this shard
+    [ent_row0, ent_row0 + n), -inf when its bit is set in the bit-packed `mask` [B, >= ceil(n/32)] int32 of filter_mask(), and
+    is left as it is for every other id (-1 padding, another shard's id, any int64). out: a 2-d [B, K] f32 view to write into
+    (its row stride is ldo; columns outside the view are left alone); None allocates a block filled with -inf, so that padding
+    and foreign ids read -inf, the padding convention of score_topk."""
+    B, n, O = _score_args(x, ent, bias)
+    if cand.dim() != 2 or cand.size(0) != B:
+        raise NativeError('score_candidates: cand %s must be (%d, K)' % (tuple(cand.shape), B))
+    K = cand.size(1)
+    if B > 1 and K > 0 and cand.stride(0) < K:
+        raise NativeError('score_candidates: cand rows overlap (stride %d < %d)' % (cand.stride(0), K))
+    if mask is not None and (mask.dim() != 2 or mask.size(0) != B or mask.size(1) < (n + 31) // 32 or not mask.is_contiguous()):
+        raise NativeError('score_candidates: mask must be contiguous (%d, >= %d)' % (B, (n + 31) // 32))
+    if out is None:
+        out = torch.full((B, K), float('-inf'), dtype=torch.float32, device=x.device)
+    elif out.dim() != 2 or tuple(out.shape) != (B, K) or (B > 1 and K > 0 and out.stride(0) < K):
+        raise NativeError('score_candidates: out %s must be (%d, %d) with rows that do not overlap' % (tuple(out.shape), B, K))
+    _same_device(x, ent, bias, cand, mask, out)
+    if K == 0 or B == 0 or n == 0:         # nothing to write (an empty shard owns no id)
+        return out
+    _check(lib().mgcn_score_candidates(B, K, n, int(ent_row0), O, _dev(x, torch.float32, 'x'), _ld(x),
+                                       _dev(ent, torch.float32, 'ent'), _ld(ent), _dev(bias, torch.float32, 'bias'),
+                                       _dev(cand, torch.int64, 'cand'), _ld(cand), _dev(mask, torch.int32, 'mask', True),
+                                       mask.size(1) if mask is not None else 0, _dev(out, torch.float32, 'out'), _ld(out),
+                                       _stream(x)), 'mgcn_score_candidates')
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

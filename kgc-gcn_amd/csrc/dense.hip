@@ -7,7 +7,8 @@
 //   EPI_RANK      filtered counts gt / ties_lower / ties per query, scores never stored (main.py:122-126)
 //   EPI_BCE       training: BCE(sigmoid(score), target) partial sums + d loss / d logit [M, ncols] (main.py:61-66, N3)
 // and, for aligned scoring shapes with K <= 352, score_split_kernel<SIGMOID / TARGET / RANK>: the same three results on
-// the bf16 MFMA from exactly split operands (below).
+// the bf16 MFMA from exactly split operands (below); and cand_split_kernel / cand_tile_kernel: score[b, cand[b, j]] for per-query
+// candidate lists, the same two arithmetics over gathered rows (include/mgcn_hip.h (13)).
 //
 // Geometry. The streamed operand (aggregates [N,3D], or the entity table [N,O]) is always the MFMA A
 // operand and goes global -> registers directly: lane (r = l&15, q = l>>4) loads the 16 bytes
@@ -735,6 +736,152 @@ __global__ __launch_bounds__(SS_THREADS, 2) void score_split_kernel(TileArgs p) 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Candidate lists: out[b, j] = score[b, cand[b, j]] for a per-query list of entity ids, with the arithmetic of the
+// kernels above over GATHERED rows, so that an element has the bits mgcn_score_fwd gives it. A row tile is 16
+// candidates of ONE query: lane (r = l&15, q = l>>4) loads candidate r's row exactly as the kernels above load entity
+// row r of a tile, and the B fragment is that query's operand in all 16 columns (an output element of an MFMA depends
+// on its own A row and B column only, so column 0's chain is the chain of the full kernels; the other 15 columns repeat
+// it: 1/16 of the MFMA's work is used, against a launch that is bound by the gathered rows' bytes).
+// Block = 4 waves = 64 consecutive list positions of one query; units (query, chunk of 64) are walked grid-stride.
+// An id outside [row0, row0 + n_local) loads nothing and stores nothing (the unsigned difference id - row0 is compared
+// against n_local: negative and huge ids wrap far above it).
+struct CandArgs {
+  const float *x, *ent, *bias;
+  const int64_t *cand;
+  const uint32_t *mask;
+  float *out;
+  int64_t ldx, lde, ldc, ldm, ldo, n_cand, n_local, row0, units;
+  int32_t k, chunks;     // chunks of CD_ROWS list positions per query
+};
+constexpr int CD_WAVES = 4, CD_THREADS = 64 * CD_WAVES, CD_ROWS = 16 * CD_WAVES;
+
+// The candidate of this lane's tile row (l & 15): its shard row, or `ok` false
+__device__ __forceinline__ int64_t cand_row(const CandArgs &p, int b, int64_t j, bool &ok) {
+  ok = j < p.n_cand;
+  uint64_t d = 0;
+  if (ok) {
+    d = uint64_t(p.cand[int64_t(b) * p.ldc + j]) - uint64_t(p.row0);
+    ok = d < uint64_t(p.n_local);
+  }
+  return ok ? int64_t(d) : 0;
+}
+
+// acc[i] = logit of tile row 4 (l >> 4) + i, the same in every column: lanes l & 15 < 4 store row 4 (l >> 4) + (l & 15)
+__device__ __forceinline__ void cand_store(const CandArgs &p, int b, int64_t j0, const f32x4 &acc, int64_t o, bool ok, int lane) {
+  const int fr = lane & 15, row = 4 * (lane >> 4) + (fr & 3);
+  const int64_t orow = __shfl(o, row);           // lane `row` (q = 0) holds tile row `row`'s candidate
+  const bool okrow = __shfl(int(ok), row) != 0;
+  if (fr >= 4 || !okrow) return;
+  const float v = fr == 0 ? acc[0] : fr == 1 ? acc[1] : fr == 2 ? acc[2] : acc[3];
+  float s = sigmoidf_(v + p.bias[orow]);
+  if (p.mask && ((p.mask[int64_t(b) * p.ldm + (orow >> 5)] >> (orow & 31)) & 1u)) s = -__builtin_inff();
+  p.out[int64_t(b) * p.ldo + j0 + row] = s;
+}
+
+// The six-product family (score_split_kernel's k-block, RT = 1, one column tile): the query is split once per block into
+// LDS as [piece][8-k group][16 B]; every lane reads the group of its q (a broadcast over the 16 lanes of a group).
+__global__ __launch_bounds__(CD_THREADS) void cand_split_kernel(CandArgs p) {
+  __shared__ __attribute__((aligned(16))) unsigned char qs[3 * SS_MAX_KB * 4 * 16];
+  const int nkb = (p.k + 31) >> 5;
+  const int piece = nkb * 4 * 16;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int fr = lane & 15, fq = lane >> 4;
+  for (int64_t u = blockIdx.x; u < p.units; u += gridDim.x) {
+    const int b = int(u / p.chunks);
+    const int64_t j0 = (u - int64_t(b) * p.chunks) * CD_ROWS + wave * 16;
+    __syncthreads();   // the previous unit's readers are done with qs
+    if (tid < nkb * 4) {
+      const int k0 = 8 * tid;
+      const float *src = p.x + int64_t(b) * p.ldx;
+      const int ka = k0 < p.k ? k0 : 0, kb2 = k0 + 4 < p.k ? k0 + 4 : 0;   // (K % 4 == 0; past K: column 0, zeroed below)
+      float4 lo = *reinterpret_cast<const float4 *>(src + ka);
+      float4 hi = *reinterpret_cast<const float4 *>(src + kb2);
+      if (k0 >= p.k) lo = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (k0 + 4 >= p.k) hi = make_float4(0.f, 0.f, 0.f, 0.f);
+      u32x4s h, m, l;
+      split8_(lo, hi, h, m, l);
+      *reinterpret_cast<u32x4s *>(qs + tid * 16) = h;
+      *reinterpret_cast<u32x4s *>(qs + piece + tid * 16) = m;
+      *reinterpret_cast<u32x4s *>(qs + 2 * piece + tid * 16) = l;
+    }
+    __syncthreads();
+    if (j0 >= p.n_cand) continue;   // wave-uniform: a tile past the list
+    bool ok;
+    const int64_t o = cand_row(p, b, j0 + fr, ok);
+    const float *ap = p.ent + o * p.lde + 8 * fq;
+    auto aload = [&](float4 &lo, float4 &hi, int kb) {
+      const int k0 = 32 * kb + 8 * fq;
+      lo = make_float4(0.f, 0.f, 0.f, 0.f);
+      hi = lo;
+      if (ok && k0 < p.k) lo = *reinterpret_cast<const float4 *>(ap + 32 * kb);
+      if (ok && k0 + 4 < p.k) hi = *reinterpret_cast<const float4 *>(ap + 32 * kb + 4);
+    };
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    float4 clo, chi, nlo, nhi;
+    aload(clo, chi, 0);
+    for (int kb = 0; kb < nkb; ++kb) {
+      if (kb + 1 < nkb) aload(nlo, nhi, kb + 1);   // the next k-block's row loads in flight under this one's MFMAs
+      u32x4s ah, am, al;
+      split8_(clo, chi, ah, am, al);
+      const unsigned char *bp = qs + (kb * 4 + fq) * 16;
+      const bf16x8s bh = __builtin_bit_cast(bf16x8s, *reinterpret_cast<const u32x4s *>(bp));
+      const bf16x8s bm = __builtin_bit_cast(bf16x8s, *reinterpret_cast<const u32x4s *>(bp + piece));
+      const bf16x8s bl = __builtin_bit_cast(bf16x8s, *reinterpret_cast<const u32x4s *>(bp + 2 * piece));
+      f32x4 c = acc;   // the six products in score_split_kernel's order
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8s, ah), bl, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8s, al), bh, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8s, am), bm, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8s, ah), bm, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8s, am), bh, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8s, ah), bh, c, 0, 0, 0);
+      acc = c;
+      clo = nlo;
+      chi = nhi;
+    }
+    cand_store(p, b, j0, acc, o, ok, lane);
+  }
+}
+
+// The exact-f32 family (tile_kernel's k-ordered chain: k-blocks of 16 ascending, step i, the MFMA's four k = 4 q + i). The
+// query's 16 bytes per lane and k-block come straight from global (one address per 16-lane group, no staging: a query row
+// of any length, cached after the first tile). FAST / !FAST as in tile_kernel; values past K are zero on both operands
+// (tile_kernel's FAST query slab repeats a valid column there against a zero entity value: the same sum).
+template <bool FAST>
+__global__ __launch_bounds__(CD_THREADS) void cand_tile_kernel(CandArgs p) {
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int nkb = (p.k + KS - 1) / KS;
+  for (int64_t u = blockIdx.x; u < p.units; u += gridDim.x) {
+    const int b = int(u / p.chunks);
+    const int64_t j0 = (u - int64_t(b) * p.chunks) * CD_ROWS + wave * 16;
+    if (j0 >= p.n_cand) continue;   // wave-uniform
+    bool ok;
+    const int64_t o = cand_row(p, b, j0 + fr, ok);
+    const float *ap = p.ent + o * p.lde + 4 * fq;
+    const float *xp = p.x + int64_t(b) * p.ldx + 4 * fq;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    float4 a_cur = load4<FAST>(ap, ok, 4 * fq, p.k);
+    float4 x_cur = load4<FAST>(xp, true, 4 * fq, p.k);
+    for (int kb = 0; kb < nkb; ++kb) {
+      float4 a_next = make_float4(0.f, 0.f, 0.f, 0.f), x_next = a_next;
+      if (kb + 1 < nkb) {
+        a_next = load4<FAST>(ap + (kb + 1) * KS, ok, (kb + 1) * KS + 4 * fq, p.k);
+        x_next = load4<FAST>(xp + (kb + 1) * KS, true, (kb + 1) * KS + 4 * fq, p.k);
+      }
+      const float av[4] = {a_cur.x, a_cur.y, a_cur.z, a_cur.w};
+      const float xv[4] = {x_cur.x, x_cur.y, x_cur.z, x_cur.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], xv[i], acc, 0, 0, 0);
+      a_cur = a_next;
+      x_cur = x_next;
+    }
+    cand_store(p, b, j0, acc, o, ok, lane);
+  }
+}
+
 // all_rel = rels_embs @ rels_weight (model.py:107 without the dropped last row): [T, K] x [K, O], T tiny, so
 // the kernel is pure latency. Block = (one output row, 64 columns); its 4 waves split K and keep UNR
 // independent loads in flight per lane; partial sums meet in LDS and are added in wave order.
@@ -1042,3 +1189,41 @@ extern "C" int mgcn_score_rank(int32_t batch, int64_t n_local, int64_t ent_row0,
   return launch<EPI_RANK, true>(p, 1280, static_cast<hipStream_t>(stream), "tile_kernel<RANK>");
 }
 
+
+// (13) Per-query candidate lists. The arithmetic family is split_scoring's choice for (x, ent, dim) — what mgcn_score_fwd
+// takes for the same operands — and nothing else: not the list, its length, the batch or the output.
+extern "C" int mgcn_score_candidates(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim,
+                                     const float *x_dev, int64_t ldx, const float *ent_dev, int64_t lde,
+                                     const float *bias_dev, const int64_t *cand_dev, int64_t ldc, const uint32_t *mask_dev,
+                                     int64_t ldm, float *out_dev, int64_t ldo, void *stream) {
+  if (int rc = check_common("score_candidates", n_local, dim, batch)) return rc;
+  MGCN_REQUIRE(n_cand >= 0 && ent_row0 >= 0, "score_candidates: bad sizes");
+  MGCN_REQUIRE(n_cand < (int64_t(1) << 31) - 64, "score_candidates: sizes exceed int32");
+  MGCN_REQUIRE(x_dev && ent_dev && bias_dev && cand_dev && out_dev, "score_candidates: null pointer");
+  MGCN_REQUIRE(ldx >= dim && lde >= dim && ldc >= n_cand && ldo >= n_cand, "score_candidates: leading dimension too small");
+  MGCN_REQUIRE(!mask_dev || ldm >= (n_local + 31) / 32, "score_candidates: mask rows too short");
+  if (batch == 0 || n_cand == 0 || n_local == 0) return MGCN_OK;
+  TileArgs t = {};
+  t.a = ent_dev; t.lda = lde;
+  t.b = x_dev; t.ldb = ldx;
+  t.k = dim;
+  const bool split = split_scoring(&t);
+  const bool fast = t.a_vec && t.b_vec && dim % 4 == 0;
+  CandArgs p = {};
+  p.x = x_dev; p.ent = ent_dev; p.bias = bias_dev; p.cand = cand_dev; p.mask = mask_dev; p.out = out_dev;
+  p.ldx = ldx; p.lde = lde; p.ldc = ldc; p.ldm = ldm; p.ldo = ldo;
+  p.n_cand = n_cand; p.n_local = n_local; p.row0 = ent_row0; p.k = dim;
+  p.chunks = int32_t((n_cand + CD_ROWS - 1) / CD_ROWS);
+  p.units = int64_t(batch) * p.chunks;
+  const unsigned gx = unsigned(p.units < (int64_t(1) << 22) ? p.units : (int64_t(1) << 22));   // beyond: grid-stride
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (split) {
+    hipLaunchKernelGGL(cand_split_kernel, dim3(gx), dim3(CD_THREADS), 0, s, p);
+  } else if (fast) {
+    hipLaunchKernelGGL(cand_tile_kernel<true>, dim3(gx), dim3(CD_THREADS), 0, s, p);
+  } else {
+    hipLaunchKernelGGL(cand_tile_kernel<false>, dim3(gx), dim3(CD_THREADS), 0, s, p);
+  }
+  MGCN_CHECK_LAUNCH(split ? "cand_split_kernel" : "cand_tile_kernel");
+  return MGCN_OK;
+}

@@ -153,6 +153,30 @@ def sharded_topk(x, qkey, ent_shard, bias_shard, row0, k, filt=None, group=None,
     return scores[rank * B:(rank + 1) * B], ids[rank * B:(rank + 1) * B]
 
 
+def sharded_score_candidates(x, qkey, cand, ent_shard, bias_shard, row0, filt=None, group=None, kernels=_native):
+    """Scores of this rank's per-query candidate lists against the WHOLE entity table, which is sharded by rows (the
+    counterpart of sharded_topk for _native.score_candidates): x [B, O] query embeddings, qkey [B] filter keys (ignored
+    without `filt`), cand [B, K] int64 global ids, ent_shard / bias_shard the rows [row0, row0 + n_local). The exchange: one
+    all-gather of x, of the keys (only with `filt`) and of cand, the local launch into a -inf block (a rank writes only the
+    ids of its shard), one all_reduce(MAX): at most one rank writes an element and a score is above -inf, so the result is
+    exact in any order. Returns this rank's [B, K] rows, equal to the unsharded result (-inf at padding, at ids no shard
+    owns and at filtered candidates). All ranks pass the same B and K, and all or none pass `filt`."""
+    world = dist.get_world_size(group) if (group is not None or dist.is_initialized()) else 1
+    rank = dist.get_rank(group) if world > 1 else 0
+    B = x.size(0)
+    if world > 1:
+        x_all, cand_all = _gather(x, group, world), _gather(cand, group, world)
+        key_all = _gather(qkey, group, world) if filt is not None else None
+    else:
+        x_all, key_all, cand_all = x.contiguous(), qkey, cand
+    mask = kernels.filter_mask(key_all, filt.keys, filt.ptr, filt.tails, ent_shard.size(0), ent_row0=row0) \
+        if filt is not None else None
+    scores = kernels.score_candidates(x_all, ent_shard, bias_shard, cand_all, mask=mask, ent_row0=row0)
+    if world > 1 and scores.numel() > 0:
+        dist.all_reduce(scores, op=dist.ReduceOp.MAX, group=group)
+    return scores[rank * B:(rank + 1) * B]
+
+
 def xavier_rows(edge_ids, num_rows, dim, seed, device, chunk=1 << 16):
     """Rows `edge_ids` (reference edge ids, int64) of a [num_rows, dim] xavier-uniform table (utils.get_param's
     initialiser, utils.py:113-118) that is DEFINED chunk-wise: rows [c * chunk, (c + 1) * chunk) come from a generator

@@ -143,3 +143,21 @@ def evaluate(model, data_iters, graph, params, data_type, mark='Val', hits=(1, 3
         results['hits@{}'.format(k)] = np.round((tail['hits@{}'.format(k)] + head['hits@{}'.format(k)]) / (2 * count), 5)
     logging.info('- {} metrics: {}  '.format(mark, '; '.join('{}: {:05.3f}'.format(k, v) for k, v in results.items())))
     return results
+
+
+def evaluate_candidates(model, queries, cand, graph, batch_size, hits=(1, 3, 10)):
+    """Evaluation against per-query candidate lists (sampled negatives: the usual protocol once the table is too large to
+    rank against whole): queries [Q, 3] int64 rows (src, rel, obj) and cand [Q, K] int64, both on the device. The rank of
+    a query is 1 + gt + ties_lower of model.rank_candidates over its list (the target itself, padding and ids outside the
+    table are never counted). Returns evaluate's keys for this one side: mr, mrr and hits@k over the Q queries, rounded to
+    5 decimals."""
+    results = {}
+    for i in range(0, queries.size(0), int(batch_size)):
+        q, c = queries[i:i + batch_size], cand[i:i + batch_size]
+        counts, _ = model.rank_candidates(q[:, 0].contiguous(), q[:, 1].contiguous(), q[:, 2].contiguous(), c, graph)
+        _accumulate(results, 1 + counts[:, 0] + counts[:, 1])
+    count = float(results.get('count', 0.0))
+    out = {'mr': np.round(results.get('mr', 0.0) / max(count, 1.0), 5), 'mrr': np.round(results.get('mrr', 0.0) / max(count, 1.0), 5)}
+    for k in hits:
+        out['hits@{}'.format(k)] = np.round(results.get('hits@{}'.format(k), 0.0) / max(count, 1.0), 5)
+    return out

@@ -268,6 +268,18 @@ def counter_dropout(x, p, seed, step, site, row0=0, step_key_dev=None):
     return _CounterDropoutFn.apply(x, _site_key(ctx, site), row0, p)
 
 
+def candidate_counts(scores, cand, obj, target):
+    """The count rule of MGCN.rank_candidates on plain tensors (any device): scores [B, K] f32 with -inf at every entry that
+    is not to be counted (padding, ids outside the table, filtered entities), cand [B, K] int64, obj [B] int64, target [B]
+    f32 -> counts [B, 3] int64 = gt / ties_lower / ties over the LIST, with the meaning of rank_counts: entries equal to
+    obj[b] are never counted (main.py:125), ties_lower are the ties whose entity id is below obj[b], a duplicate counts once
+    per occurrence."""
+    o, t = obj.view(-1, 1), target.view(-1, 1)
+    live = (scores != float('-inf')) & (cand != o)
+    eq = live & (scores == t)
+    return torch.stack([(live & (scores > t)).sum(1), (eq & (cand < o)).sum(1), eq.sum(1)], dim=1).to(torch.int64)
+
+
 class _ScoreFn(torch.autograd.Function):
     """sigmoid(x @ ent^T + bias): forward and both backward products on the HIP f32 MFMA tile kernel."""
 
@@ -1013,3 +1025,53 @@ class MGCN(nn.Module):
         finally:
             self.train(was_training)
         return ids, scores
+
+    # -- per-query candidate lists (include/mgcn_hip.h (13)) -------------------------------------------
+    def _candidate_scores(self, src, rel, lists, data, filter_index):
+        """The score blocks of lists = [(cand [B, K], takes the filter)] from ONE encoder pass and one trunk launch, in eval
+        mode (restored afterwards)."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                all_ent, all_rel = self.encode(data)
+                x = self.conv2.trunk_indexed(all_ent, src, all_rel, rel)
+                ent = all_ent.contiguous()
+                mask = None
+                if filter_index is not None and any(filtered for _, filtered in lists):
+                    f = filter_index
+                    mask = _native.filter_mask(f.query_keys(src, rel), f.keys, f.ptr, f.tails, ent.size(0))
+                return [_native.score_candidates(x, ent, self.conv2.bias, c, mask=mask if filtered else None)
+                        for c, filtered in lists]
+        finally:
+            self.train(was_training)
+
+    @staticmethod
+    def _candidate_block(cand, B):
+        if cand.dim() != 2 or cand.size(0) != B or cand.dtype != torch.int64:
+            raise _native.NativeError('candidates must be int64 [%d, K], got %s %s' % (B, cand.dtype, tuple(cand.shape)))
+        return cand if cand.stride(1) == 1 or cand.size(1) <= 1 else cand.contiguous()
+
+    def score_candidates(self, src, rel, cand, data, filter_index=None):
+        """What the model says about THESE entities for each query: scores [B, K] f32 of the per-query candidate lists
+        cand [B, K] int64, element (b, j) equal to forward(src, rel, data)[b, cand[b, j]] bit for bit, without the [B, N]
+        block (triple classification, re-ranking a proposed short list, sampled-negative evaluation, re-scoring
+        predict_topk's ids). -1 and every id outside [0, N) give -inf; with `filter_index` (a dist.FilterIndex on the
+        device) so do the known tails of (src, rel). Eval mode (restored afterwards), through encode() as predict_topk."""
+        return self._candidate_scores(src, rel, [(self._candidate_block(cand, src.numel()), True)], data, filter_index)[0]
+
+    def score_triples(self, src, rel, obj, data):
+        """score [B] f32 of the triples (src, rel, obj): the K = 1 case of score_candidates, equal to the target of
+        rank_counts bit for bit (-inf for an obj outside [0, N))."""
+        return self._candidate_scores(src, rel, [(obj.reshape(-1, 1), False)], data, None)[0].view(-1)
+
+    def rank_candidates(self, src, rel, obj, cand, data, filter_index=None):
+        """rank_counts over a candidate list instead of the table: (counts [B, 3] int64, target [B] f32) with gt /
+        ties_lower (equal score and entity id < obj[b]) / ties counted over cand [B, K]; entries equal to obj[b], padding,
+        ids outside the table and (with `filter_index`) known tails are never counted, a duplicate counts once per
+        occurrence. The target is the unfiltered score of obj. rank = 1 + gt + ties_lower; with cand = every entity this
+        is rank_counts. The counts are a few comparisons over the [B, K] block on the device (candidate_counts)."""
+        cand = self._candidate_block(cand, src.numel())
+        scores, target = self._candidate_scores(src, rel, [(cand, True), (obj.reshape(-1, 1), False)], data, filter_index)
+        target = target.view(-1)
+        return candidate_counts(scores, cand, obj, target), target

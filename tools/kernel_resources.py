@@ -5,7 +5,12 @@
 compiles aggregate.hip, layer_fused2.hip and layer_fused3.hip for gfx950 (device code only) and prints one line per instantiation
 of agg_fwd_kernel, agg_hub_kernel, layer_fused2_kernel and layer_fused3_kernel. A trailing `false` of the EE16 template parameter
  is dropped from the name, so that the table of a tree without that parameter can be compared line by line with
-`diff`: profiles/ee16_kernel_resources.txt is that comparison for the commit that added the bf16 per-edge table."""
+`diff`: profiles/ee16_kernel_resources.txt is that comparison for the commit that added the bf16 per-edge table.
+
+    python tools/kernel_resources.py [csrc directory] dense.hip [more.hip ...] > table.txt
+
+prints every kernel of the named translation units instead (profiles/candidates_kernel_resources.txt: dense.hip before and after
+the candidate-list kernels were added to it)."""
 import os
 import re
 import shutil
@@ -49,12 +54,12 @@ def normalised(mangled):
     return (m.group(1) + m.group(3), m.group(2) == '1') if m else (mangled, False)
 
 
-def table(csrc, has_ee16):
+def table(csrc, has_ee16, files=None):
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for name in FILES:
+        for name in files or FILES:
             for k, v in sorted(parse(remarks(csrc, name, tmp)).items()):
-                if not any(kk in k for kk in KERNELS):
+                if not files and not any(kk in k for kk in KERNELS):
                     continue
                 shown, ee16 = normalised(k) if has_ee16 else (k, False)
                 rows.append('%s%s  %s' % (shown, '  [EE16]' if ee16 else '', '  '.join('%s=%s' % (SHORT[f], v.get(f, '?')) for f in FIELDS)))
@@ -62,6 +67,8 @@ def table(csrc, has_ee16):
 
 
 if __name__ == '__main__':
-    csrc = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'kgc-gcn_amd', 'csrc')
-    has = 'EE16' in open(os.path.join(csrc, 'aggregate.hip')).read()
-    print('\n'.join(table(csrc, has)))
+    files = [a for a in sys.argv[1:] if a.endswith(('.hip', '.cpp'))]
+    dirs = [a for a in sys.argv[1:] if a not in files]
+    csrc = dirs[0] if dirs else os.path.join(ROOT, 'kgc-gcn_amd', 'csrc')
+    has = not files and 'EE16' in open(os.path.join(csrc, 'aggregate.hip')).read()
+    print('\n'.join(table(csrc, has, files)))
