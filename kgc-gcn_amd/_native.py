@@ -543,15 +543,56 @@ def pack_weights(w_cat, out=None, generation=None):
     return out
 
 
+MAX_ROW_BOUNDS = 4096     # runs per launch (mgcn_layer_fwd_fused num_row_bounds)
+
+
+def row_bounds_cap(rows, runs):
+    """Longest run a launch over `rows` destinations in `runs` runs sizes its tiles for: per = ceil(rows / runs) rounded up to
+    whole 16-row tiles while per <= 80, to whole 80-row tiles past that (fused3_launch, GraphCSR.workgroup_bounds)."""
+    per = -(-int(rows) // int(runs))
+    return (per + 15) // 16 * 16 if per <= 80 else (per + 79) // 80 * 80
+
+
+def check_row_bounds(offsets, rows):
+    """What the elastic launch assumes of a caller's runs, on the host values `offsets` (a sequence of ints): raises NativeError."""
+    b = [int(v) for v in offsets]
+    runs = len(b) - 1
+    if not 1 <= runs <= MAX_ROW_BOUNDS:
+        raise NativeError('layer_fwd_fused: row_bounds must give 1 .. %d runs (got %d offsets)' % (MAX_ROW_BOUNDS, len(b)))
+    if b[0] != 0 or b[-1] != int(rows) or any(hi <= lo for lo, hi in zip(b[:-1], b[1:])):
+        raise NativeError('layer_fwd_fused: row_bounds must increase strictly from 0 to the %d rows of the launch' % int(rows))
+    cap = row_bounds_cap(rows, runs)
+    longest = max(hi - lo for lo, hi in zip(b[:-1], b[1:]))
+    if longest > cap:
+        raise NativeError('layer_fwd_fused: row_bounds has a run of %d rows; %d rows in %d runs allow at most %d'
+                          % (longest, int(rows), runs, cap))
+
+
+def _checked_row_bounds(b, rows, x):
+    if not torch.is_tensor(b) or b.dtype != torch.int32 or b.dim() != 1 or not b.is_contiguous() or not b.is_cuda or \
+            b.device != x.device:
+        raise NativeError('layer_fwd_fused: row_bounds must be a contiguous 1-D int32 tensor on %s' % x.device)
+    if b.numel() > MAX_ROW_BOUNDS + 1:
+        raise NativeError('layer_fwd_fused: row_bounds must give 1 .. %d runs (got %d offsets)' % (MAX_ROW_BOUNDS, b.numel()))
+    check_row_bounds(b.tolist(), rows)
+    return b
+
+
 def layer_fwd_fused(csr, x, rel, loop_rel, ee, ee_in_slot_order, loop_edge, w_packed, d_out, bias, bn_mean, bn_var,
                     bn_gamma, bn_beta, eps, out, node_range=None, ee_sub=(0, 0, 0), rels_weight=None, rel_out=None,
-                    tune=None, balance=True, live=None):
+                    tune=None, balance=True, live=None, row_bounds=None):
     """(2)+(4) in one launch: out = tanh(BN_eval((aggregates @ W) / 3 + bias)), aggregates kept in LDS.
     `w_packed` = pack_weights(stacked [3D, O] weights). With `node_range` = (n0, n1) only those destinations are
     computed and `out` is [n1 - n0, O]; `ee` may then be this range's shard of the slot-ordered table (see
     graph.GraphCSR.edge_table_shard) with `ee_sub` its three slot offsets (in-half, out-half, hub region).
     `balance`: hand the launch the graph's work-balanced per-workgroup row runs (GraphCSR.workgroup_bounds, one run per
     CU, None when equal runs are balanced already); results do not depend on it.
+    `row_bounds`: the caller's own runs instead (it overrides `balance`): an int32 tensor on the launch's device, row offsets
+    from n0, strictly increasing from 0 to n1 - n0, at most 4096 runs, one workgroup each. No run may be longer than the cap the
+    launch sizes its tiles by, from per = ceil(rows / runs): per rounded up to whole 16-row tiles while per <= 80, to whole 80-row
+    tiles past that (the rule of GraphCSR.workgroup_bounds); anything else raises NativeError before a launch (the check reads
+    the tensor back: it synchronises). Read by generations 3 and 4 (bounds make a lockstep shape with O > 128 and fewer than two
+    tiles per CU take generation 3); generation 2 tiles the range itself. Results do not depend on the runs.
     `live`: walk the graph's live view (GraphCSR.live_rowptr / live_rec: zero-norm slots left out; bit-identical rows for
     finite inputs). None = whenever the graph has one and MGCN_LIVE_SLOTS is not 0; False = the canonical launch; True raises
     where there is no view to walk.
@@ -589,12 +630,16 @@ def layer_fwd_fused(csr, x, rel, loop_rel, ee, ee_in_slot_order, loop_edge, w_pa
                 tuple(rel_out.shape) != (csr.num_rel_rows - 1, O) or not rel_out.is_contiguous():
             raise NativeError('layer_fwd_fused: rels_weight must be contiguous (%d, %d) and rel_out (%d, %d)'
                               % (D, O, csr.num_rel_rows - 1, O))
+    if row_bounds is not None:
+        row_bounds = _checked_row_bounds(row_bounds, n1 - n0, x)
     if n1 == n0 and rel_out is None:
         return out                                   # an empty destination range: nothing to launch
     if ee is not None and ee.numel() == 0:           # a range whose destinations have no slots: the kernel still wants
         ee = torch.zeros((1, D), dtype=ee.dtype, device=x.device)   # a valid (never read) table pointer
     hub_info, hub_chunks, hub_c0, hub_c1, hub_partial = _hub_args(csr, D, x.device, n0, n1)
     bounds = csr.workgroup_bounds(n0, n1, _cu_count(x.device)) if balance and n1 > n0 else None
+    if row_bounds is not None:
+        bounds = row_bounds
     # the graph's live view (zero-norm slots left out) whenever it has one: same rows for finite inputs, fewer row loads
     has_view = getattr(csr, 'live_rowptr', None) is not None and tune_generation(tune) != 4
     if live and not has_view:
