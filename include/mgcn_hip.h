@@ -839,6 +839,69 @@ int mgcn_score_candidates(int32_t batch, int64_t n_cand, int64_t n_local, int64_
                           int64_t ldx, const float *ent_dev, int64_t lde, const float *bias_dev, const int64_t *cand_dev,
                           int64_t ldc, const uint32_t *mask_dev, int64_t ldm, float *out_dev, int64_t ldo, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (14) Training on per-query candidate lists (csrc/dense.hip: labels and forward; csrc/query_train.hip: backward; DESIGN
+ * §4.11) — additive, MGCN_ABI_VERSION stays 4. The mean BCE of (6) over the lists of (13) instead of the table: the true tails
+ * plus sampled negatives. Nothing here has a [B, N] or [B, N/32] operand; the work is B n_cand dim. No float atomics, every sum
+ * has a fixed order: the same inputs give the same bits.
+ * Liveness is that of (13): with id = cand[b * ldc + j] and d = uint64(id) - uint64(ent_row0), position (b, j) is LIVE iff
+ * d < n_local, its shard row is o = d. One unsigned comparison, made before any address of ent, bias, d_ent or d_bias is formed:
+ * -1, another shard's id, +-2^62 are DEAD and load nothing.
+ *
+ * mgcn_cand_labels: label[b * ldl + j] (uint8) = 1 iff position (b, j) is live and cand[b, j] is among the known tails of
+ *   qkey[b] in the keys / ptr / tails arrays of mgcn_filter_mask (tails ascending within a key), else 0. The key lookup of
+ *   mgcn_filter_mask, then a binary search in the key's run. One launch, integers only.
+ * mgcn_cand_bce_partials(batch, n_cand) = batch * ceil(n_cand / 64), the length of loss_partial.
+ * mgcn_cand_bce_fwd: one launch with the geometry of (13) (a workgroup of four waves per (query, 64 list positions),
+ *   grid-stride, a wave's tile 16 gathered rows). For a live (b, j): z = the exact-f32 MFMA's k-ordered chain of (13) -- ALWAYS
+ *   that family, never the six-product split, because mgcn_score_bce_fwd always takes it --, p = sigmoid(z + bias[o]),
+ *   y = label[b, j] ? hot : cold, and
+ *     g[b * ldg + j] = (p - y) / max(p (1 - p), 1e-12) * p (1 - p) * inv_count
+ *   with the term (y - 1) max(log1p(-p), -100) - y max(log(p), -100) added to the unit's partial. A dead position writes
+ *   g = 0 and adds no term, so g [batch, n_cand] is written completely. loss_partial[b * chunks + ch] is the sum of the unit's
+ *   terms in a fixed order (lanes: xor tree; then the four waves in wave order), a function of its own (query, chunk) and of
+ *   nothing else in the launch; the loss is the sum of the partials times inv_count.
+ *   CONTRACT: for a live position, g[b, j] has the bits of grad_logit[o, b] of mgcn_score_bce_fwd for the same x, ent, bias, hot,
+ *   cold, inv_count and a mask whose bit o of row b equals label[b, j] (operands that entry point takes: 16-byte aligned,
+ *   dim % 4 == 0, batch % 4 == 0). Other operands take element-wise guarded loads and the same summation order.
+ * mgcn_cand_bce_bwd_x: dx [batch, dim] (rows ldx apart), written completely:
+ *     dx[b, c] = 0;  for ch = 0 .. chunks - 1:  s = 0;  for the LIVE j of [64 ch, min(64 ch + 64, n_cand)) ascending:
+ *     s = s + (g[b, j] * ent[o_j, c]);  then dx[b, c] = dx[b, c] + s
+ *   every product and every sum rounded to f32 (no contraction). The order depends on n_cand alone.
+ * mgcn_cand_bce_bwd_ent: the caller supplies a plan perm [batch * n_cand] int64: the flat positions b * n_cand + j of the live
+ *   entries ordered by (shard row, flat position), then the dead ones; n_live is the length of the live prefix (only the prefix
+ *   is read). The kernel recomputes the row of every perm[i] it meets from cand with the liveness test and follows nothing it
+ *   has not checked: a perm[i] outside [0, batch * n_cand) or a dead one inside the prefix is skipped and ends the run before
+ *   it. A run is a maximal stretch of plan entries with equal rows; the wave of a run's first entry owns it, every other wave
+ *   exits. The owner walks the run in plan order and writes
+ *     d_ent[o * lde + c] = sum of (g[pos] * x[b(pos), c]),   d_bias[o] = sum of g[pos]
+ *   each the sequential f32 loop from 0, products and sums rounded separately. Rows that no live position names are LEFT AS THEY
+ *   ARE (the caller zero-fills: the convention of (13)). Either of d_ent_dev / d_bias_dev may be NULL, which only removes work
+ *   (with d_ent_dev NULL, x_dev / ldx / lde are not looked at).
+ *   A RUN IS WALKED BY ONE WAVE, HOWEVER LONG IT IS: a list in which every query names the same entity is a chain of batch
+ *   addends per column on one wave (measured: tools/bench_cand_train.py). With a plan that is not sorted as described, a row
+ *   whose entries are not adjacent has several owners and receives the sum of one of its stretches; nothing outside the rows
+ *   that live positions name is ever written.
+ * All checks precede the first launch; a refusal writes nothing. MGCN_EINVAL: a null required pointer, a negative size, dim < 1,
+ * ent_row0 < 0, batch / n_cand / n_local at or above 2^31 - 64, ldc / ldl / ldg < n_cand, ldx / lde < dim, n_live outside
+ * [0, batch * n_cand]. batch == 0, n_cand == 0 or n_local == 0 (bwd_ent: also n_live == 0, or both outputs NULL) return MGCN_OK
+ * without a launch and write nothing.
+ */
+int mgcn_cand_labels(int32_t batch, int64_t n_cand, const int64_t *qkey_dev, int64_t num_keys, const int64_t *keys_dev,
+                     const int64_t *ptr_dev, const int32_t *tails_dev, int64_t ent_row0, int64_t n_local, const int64_t *cand_dev,
+                     int64_t ldc, uint8_t *label_dev, int64_t ldl, void *stream);
+int64_t mgcn_cand_bce_partials(int32_t batch, int64_t n_cand);
+int mgcn_cand_bce_fwd(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *x_dev,
+                      int64_t ldx, const float *ent_dev, int64_t lde, const float *bias_dev, const int64_t *cand_dev, int64_t ldc,
+                      const uint8_t *label_dev, int64_t ldl, float hot, float cold, float inv_count, float *g_dev, int64_t ldg,
+                      float *loss_partial_dev, void *stream);
+int mgcn_cand_bce_bwd_x(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *g_dev,
+                        int64_t ldg, const int64_t *cand_dev, int64_t ldc, const float *ent_dev, int64_t lde, float *dx_dev,
+                        int64_t ldx, void *stream);
+int mgcn_cand_bce_bwd_ent(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *g_dev,
+                          int64_t ldg, const int64_t *cand_dev, int64_t ldc, const int64_t *perm_dev, int64_t n_live,
+                          const float *x_dev, int64_t ldx, float *d_ent_dev, int64_t lde, float *d_bias_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

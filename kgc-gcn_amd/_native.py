@@ -85,6 +85,13 @@ _SIGNATURES = {
     'mgcn_topk_merge': (ctypes.c_int, [_i32, _i32, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _ptr]),
     'mgcn_score_candidates': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64,
                                              _ptr, _i64, _ptr]),
+    'mgcn_cand_labels': (ctypes.c_int, [_i32, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr]),
+    'mgcn_cand_bce_partials': (_i64, [_i32, _i64]),
+    'mgcn_cand_bce_fwd': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _f32, _f32,
+                                         _f32, _ptr, _i64, _ptr, _ptr]),
+    'mgcn_cand_bce_bwd_x': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr]),
+    'mgcn_cand_bce_bwd_ent': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64,
+                                             _ptr, _ptr]),
     'mgcn_conve_packed_bytes': (ctypes.c_size_t, [_i32] * 5),
     'mgcn_conve_pack': (ctypes.c_int, [_i32] * 5 + [_ptr, _ptr, _ptr, _i64, _ptr] + ([_ptr] * 4 + [_f32]) * 3 +
                         [_ptr, ctypes.c_size_t, _ptr]),
@@ -993,6 +1000,136 @@ def score_candidates(x, ent, bias, cand, mask=None, ent_row0=0, out=None):
                                        mask.size(1) if mask is not None else 0, _dev(out, torch.float32, 'out'), _ld(out),
                                        _stream(x)), 'mgcn_score_candidates')
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# (14) Training on per-query candidate lists
+def _cand_block(cand, B, what):
+    if cand.dim() != 2 or cand.size(0) != B or cand.dtype != torch.int64:
+        raise NativeError('%s: cand must be int64 (%d, K), got %s %s' % (what, B, cand.dtype, tuple(cand.shape)))
+    K = cand.size(1)
+    if B > 1 and K > 0 and cand.stride(0) < K:
+        raise NativeError('%s: cand rows overlap (stride %d < %d)' % (what, cand.stride(0), K))
+    return K
+
+
+def _cand_rows(t, B, K, dtype, what, name):
+    """(pointer, row stride) of the [B, K] block `t` of `dtype` (uint8 also takes bool) whose rows do not overlap."""
+    if t.dim() != 2 or tuple(t.shape) != (B, K) or (B > 1 and K > 0 and t.stride(0) < K):
+        raise NativeError('%s: %s %s must be (%d, %d) with rows that do not overlap' % (what, name, tuple(t.shape), B, K))
+    if dtype == torch.uint8 and t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    return _dev(t, dtype, name), _ld(t)
+
+
+def cand_labels(qkey, keys, ptr, tails, cand, n_local, ent_row0=0, out=None):
+    """(14) label [B, K] uint8: 1 where cand[b, j] is a row of the shard [ent_row0, ent_row0 + n_local) and a known tail of
+    qkey[b] in the index arrays of filter_mask(), else 0 (see mgcn_cand_labels). No [B, N/32] mask is built."""
+    B = qkey.numel()
+    K = _cand_block(cand, B, 'cand_labels')
+    if ptr.numel() != keys.numel() + 1:
+        raise NativeError('cand_labels: ptr must have len(keys) + 1 entries')
+    if out is None:
+        out = torch.zeros((B, K), dtype=torch.uint8, device=cand.device)
+    _same_device(qkey, keys, ptr, tails, cand, out)
+    op, ldl = _cand_rows(out, B, K, torch.uint8, 'cand_labels', 'out')
+    if B == 0 or K == 0 or int(n_local) == 0:
+        return out
+    _check(lib().mgcn_cand_labels(B, K, _dev(qkey, torch.int64, 'qkey'), keys.numel(), _dev(keys, torch.int64, 'keys'),
+                                  _dev(ptr, torch.int64, 'ptr'), _dev(tails, torch.int32, 'tails'), int(ent_row0), int(n_local),
+                                  _dev(cand, torch.int64, 'cand'), _ld(cand), op, ldl, _stream(cand)), 'mgcn_cand_labels')
+    return out
+
+
+def cand_bce_fwd(x, ent, bias, cand, label, hot, cold, inv_count=None, ent_row0=0):
+    """(14) One launch: (loss [] f32, g [B, K] f32 = d loss / d logit per list position) of the mean BCE of
+    sigmoid(x[b] . ent[o] + bias[o]) over the lists cand [B, K] int64 against `hot` where label [B, K] (uint8 / bool) is set,
+    `cold` elsewhere. inv_count: the mean's weight, default 1 / (B K): EVERY list position counts, dead ones (ids outside the
+    shard) contribute zero and get g = 0. For a live position g has the bits of score_bce_fwd's G[o, b] under the same
+    inv_count."""
+    B, n, O = _score_args(x, ent, bias)
+    K = _cand_block(cand, B, 'cand_bce_fwd')
+    _same_device(x, ent, bias, cand, label)
+    lp, ldl = _cand_rows(label, B, K, torch.uint8, 'cand_bce_fwd', 'label')
+    inv = 1.0 / (float(B) * float(K)) if inv_count is None else float(inv_count)
+    g = torch.zeros((B, K), dtype=torch.float32, device=x.device)
+    parts = torch.zeros(int(lib().mgcn_cand_bce_partials(B, K)), dtype=torch.float32, device=x.device)
+    if B and K and n:
+        _check(lib().mgcn_cand_bce_fwd(B, K, n, int(ent_row0), O, _dev(x, torch.float32, 'x'), _ld(x), _dev(ent, torch.float32, 'ent'),
+                                       _ld(ent), _dev(bias, torch.float32, 'bias'), _dev(cand, torch.int64, 'cand'), _ld(cand), lp, ldl,
+                                       float(hot), float(cold), inv, _dev(g, torch.float32, 'g'), K,
+                                       _dev(parts, torch.float32, 'loss_partial'), _stream(x)), 'mgcn_cand_bce_fwd')
+    return parts.sum() * inv, g
+
+
+def cand_bce_bwd_x(g, cand, ent, ent_row0=0):
+    """(14) dx [B, dim] = sum over the live list positions of g[b, j] ent[o_j], in the fixed chunked order of
+    mgcn_cand_bce_bwd_x."""
+    B = g.size(0)
+    K = _cand_block(cand, B, 'cand_bce_bwd_x')
+    _same_device(g, cand, ent)
+    if ent.dim() != 2:
+        raise NativeError('cand_bce_bwd_x: ent %s must be (n, dim)' % (tuple(ent.shape),))
+    gp, ldg = _cand_rows(g, B, K, torch.float32, 'cand_bce_bwd_x', 'g')
+    n, O = ent.size(0), ent.size(1)
+    ep = _dev(ent, torch.float32, 'ent')
+    dx = torch.zeros((B, O), dtype=torch.float32, device=g.device)
+    if B and K and n:
+        _check(lib().mgcn_cand_bce_bwd_x(B, K, n, int(ent_row0), O, gp, ldg, _dev(cand, torch.int64, 'cand'), _ld(cand),
+                                         ep, _ld(ent), _dev(dx, torch.float32, 'dx'), O, _stream(g)),
+               'mgcn_cand_bce_bwd_x')
+    return dx
+
+
+def cand_plan(cand, n_local, ent_row0=0, count=True):
+    """(perm [B K] int64, n_live): the flat positions b K + j of the live entries of cand [B, K] (ids in
+    [ent_row0, ent_row0 + n_local)) ordered by (shard row, flat position), then the dead ones by flat position: the plan
+    mgcn_cand_bce_bwd_ent takes. One torch.sort of the UNIQUE keys row * (B K) + pos (dead entries: row = n_local), so the plan is a
+    function of cand alone whatever the sort does with ties. Integer work in torch, on any device. Counting the live entries
+    reads one integer back from the device; count=False skips that and returns n_live = B K, which mgcn_cand_bce_bwd_ent takes
+    as well: the dead entries sort last, and the kernel re-checks every entry and skips a dead one."""
+    if cand.dim() != 2 or cand.dtype != torch.int64:
+        raise NativeError('cand_plan: cand must be int64 [B, K], got %s %s' % (cand.dtype, tuple(cand.shape)))
+    n_local, row0, total = int(n_local), int(ent_row0), cand.numel()
+    if n_local < 0 or row0 < 0:
+        raise NativeError('cand_plan: n_local and ent_row0 must be >= 0')
+    if (n_local + 1) * total >= 2 ** 63:
+        raise NativeError('cand_plan: the sort key row * (B K) + position overflows int64 (n_local = %d, B K = %d)' % (n_local, total))
+    flat = cand.reshape(-1)
+    live = flat >= row0                            # with ent_row0 >= 0 and n_local < 2^63 this pair of signed comparisons is the
+    if row0 + n_local <= 2 ** 63 - 1:              # kernels' one unsigned comparison of id - ent_row0 against n_local
+        live = live & (flat < row0 + n_local)
+    row = torch.where(live, flat - row0, torch.full_like(flat, n_local))     # (a wrapped difference of a dead id is never used)
+    key = row * total + torch.arange(total, dtype=torch.int64, device=cand.device)
+    perm = torch.sort(key).indices
+    return perm, int(live.sum()) if count else total
+
+
+def cand_bce_bwd_ent(g, cand, x, perm, n_live, n_local, ent_row0=0, d_ent=None, d_bias=None, want=('ent', 'bias')):
+    """(14) (d_ent [n_local, dim], d_bias [n_local]): the rows that live list positions name receive their fixed-order sums of
+    g[pos] x[b(pos)] and of g[pos] (plan order, see mgcn_cand_bce_bwd_ent); every other row is LEFT AS IT IS. d_ent / d_bias:
+    blocks to write into (d_ent may be a column window); None allocates zeros for what `want` names."""
+    B = g.size(0)
+    K = _cand_block(cand, B, 'cand_bce_bwd_ent')
+    _same_device(g, cand, x, perm, d_ent, d_bias)
+    if x.dim() != 2 or x.size(0) != B or perm.dim() != 1 or perm.numel() != B * K or not 0 <= int(n_live) <= B * K:
+        raise NativeError('cand_bce_bwd_ent: x must be (%d, dim), perm [%d] and 0 <= n_live <= %d' % (B, B * K, B * K))
+    gp, ldg = _cand_rows(g, B, K, torch.float32, 'cand_bce_bwd_ent', 'g')
+    n, O = int(n_local), x.size(1)
+    if d_ent is None and 'ent' in want:
+        d_ent = torch.zeros((n, O), dtype=torch.float32, device=g.device)
+    if d_bias is None and 'bias' in want:
+        d_bias = torch.zeros(n, dtype=torch.float32, device=g.device)
+    if d_ent is not None and (d_ent.dim() != 2 or tuple(d_ent.shape) != (n, O)):
+        raise NativeError('cand_bce_bwd_ent: d_ent must be (%d, %d)' % (n, O))
+    if d_bias is not None and (d_bias.numel() != n or not d_bias.is_contiguous()):
+        raise NativeError('cand_bce_bwd_ent: d_bias must be contiguous [%d]' % n)
+    if B and K and n and int(n_live):
+        _check(lib().mgcn_cand_bce_bwd_ent(B, K, n, int(ent_row0), O, gp, ldg, _dev(cand, torch.int64, 'cand'), _ld(cand),
+                                           _dev(perm, torch.int64, 'perm'), int(n_live), _dev(x, torch.float32, 'x'), _ld(x),
+                                           _dev(d_ent, torch.float32, 'd_ent', True), _ld(d_ent) if d_ent is not None else 0,
+                                           _dev(d_bias, torch.float32, 'd_bias', True), _stream(g)), 'mgcn_cand_bce_bwd_ent')
+    return d_ent, d_bias
 
 
 # ------------------------------------------------------------------------------------------------

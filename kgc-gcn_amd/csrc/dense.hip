@@ -882,6 +882,80 @@ __global__ __launch_bounds__(CD_THREADS) void cand_tile_kernel(CandArgs p) {
   }
 }
 
+// Training on candidate lists (include/mgcn_hip.h (14)): cand_tile_kernel's chain -- ALWAYS the exact-f32 family, because
+// mgcn_score_bce_fwd always runs tile_kernel<EPI_BCE> -- followed by the EPI_BCE epilogue of tile_kernel, expression for
+// expression, so that g[b, j] has the bits of that launch's grad_logit[o, b]. A dead position writes g = 0 and adds no term.
+// The unit's partial is the lanes' xor tree, then the four waves in wave order: a function of its (query, chunk) alone.
+struct CandBceArgs {
+  CandArgs c;
+  const uint8_t *label;
+  float *g, *loss_partial;
+  int64_t ldl, ldg;
+  float hot, cold, inv_count;
+};
+
+template <bool FAST>
+__global__ __launch_bounds__(CD_THREADS) void cand_bce_kernel(CandBceArgs a) {
+  __shared__ float wsum[CD_WAVES];
+  const CandArgs &p = a.c;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int nkb = (p.k + KS - 1) / KS;
+  for (int64_t u = blockIdx.x; u < p.units; u += gridDim.x) {
+    const int b = int(u / p.chunks);
+    const int64_t j0 = (u - int64_t(b) * p.chunks) * CD_ROWS + wave * 16;
+    float term = 0.f;
+    if (j0 < p.n_cand) {   // wave-uniform: a tile past the list adds nothing
+      bool ok;
+      const int64_t o = cand_row(p, b, j0 + fr, ok);
+      const float *ap = p.ent + o * p.lde + 4 * fq;
+      const float *xp = p.x + int64_t(b) * p.ldx + 4 * fq;
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      float4 a_cur = load4<FAST>(ap, ok, 4 * fq, p.k);
+      float4 x_cur = load4<FAST>(xp, true, 4 * fq, p.k);
+      for (int kb = 0; kb < nkb; ++kb) {
+        float4 a_next = make_float4(0.f, 0.f, 0.f, 0.f), x_next = a_next;
+        if (kb + 1 < nkb) {
+          a_next = load4<FAST>(ap + (kb + 1) * KS, ok, (kb + 1) * KS + 4 * fq, p.k);
+          x_next = load4<FAST>(xp + (kb + 1) * KS, true, (kb + 1) * KS + 4 * fq, p.k);
+        }
+        const float av[4] = {a_cur.x, a_cur.y, a_cur.z, a_cur.w};
+        const float xv[4] = {x_cur.x, x_cur.y, x_cur.z, x_cur.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], xv[i], acc, 0, 0, 0);
+        a_cur = a_next;
+        x_cur = x_next;
+      }
+      // acc[i] = logit of tile row 4 (l >> 4) + i in every column: lanes l & 15 < 4 finish row 4 (l >> 4) + (l & 15)
+      const int row = 4 * fq + (fr & 3);
+      const int64_t orow = __shfl(o, row);
+      const bool okrow = __shfl(int(ok), row) != 0;
+      const int64_t j = j0 + row;
+      if (fr < 4 && j < p.n_cand) {
+        float gz = 0.f;
+        if (okrow) {
+          const float v = fr == 0 ? acc[0] : fr == 1 ? acc[1] : fr == 2 ? acc[2] : acc[3];
+          const float pz = sigmoidf_(v + p.bias[orow]);
+          const bool pos = a.label[int64_t(b) * a.ldl + j] != 0;
+          const float y = pos ? a.hot : a.cold;
+          term = (y - 1.0f) * fmaxf(log1pf(-pz), -100.0f) - y * fmaxf(logf(pz), -100.0f);
+          const float pq = (1.0f - pz) * pz;
+          gz = (pz - y) / fmaxf(pq, 1e-12f) * pq * a.inv_count;
+        }
+        a.g[int64_t(b) * a.ldg + j] = gz;
+      }
+    }
+    float v = term;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+    __syncthreads();   // the previous unit's reader is done with wsum
+    if (lane == 0) wsum[wave] = v;
+    __syncthreads();
+    if (tid == 0) a.loss_partial[u] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+  }
+}
+
 // all_rel = rels_embs @ rels_weight (model.py:107 without the dropped last row): [T, K] x [K, O], T tiny, so
 // the kernel is pure latency. Block = (one output row, 64 columns); its 4 waves split K and keep UNR
 // independent loads in flight per lane; partial sums meet in LDS and are added in wave order.
@@ -961,6 +1035,40 @@ __global__ __launch_bounds__(256) void label_rows_kernel(const int64_t *__restri
   for (int64_t i = ptr[lo] + threadIdx.x; i < ptr[lo + 1]; i += 256) {
     const int64_t n = int64_t(tails[i]) - row0;
     if (n >= 0 && n < n_local) row[n] = hot;
+  }
+}
+
+// Labels of candidate lists (include/mgcn_hip.h (14)): label[b, j] = 1 iff cand[b, j] is a known tail of qkey[b] AND a row of the
+// shard. filter_mask_kernel's key lookup, then a binary search in the key's ascending tail run; integers only. A unit is
+// (query, 256 list positions).
+__global__ __launch_bounds__(256) void cand_labels_kernel(const int64_t *__restrict__ qkey, const int64_t *__restrict__ keys,
+                                                          int64_t nkeys, const int64_t *__restrict__ ptr,
+                                                          const int32_t *__restrict__ tails, const int64_t *__restrict__ cand,
+                                                          int64_t ldc, int64_t n_cand, int64_t row0, int64_t n_local,
+                                                          uint8_t *__restrict__ label, int64_t ldl, int64_t chunks, int64_t units) {
+  for (int64_t u = blockIdx.x; u < units; u += gridDim.x) {
+    const int64_t b = u / chunks;
+    const int64_t j = (u - b * chunks) * 256 + threadIdx.x;
+    const int64_t key = qkey[b];
+    int64_t lo = 0, hi = nkeys;
+    while (lo < hi) {  // block-uniform
+      const int64_t mid = (lo + hi) >> 1;
+      if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    const bool found = lo < nkeys && keys[lo] == key;
+    if (j >= n_cand) continue;
+    const int64_t id = cand[b * ldc + j];
+    uint8_t hit = 0;
+    if (found && uint64_t(id) - uint64_t(row0) < uint64_t(n_local)) {
+      int64_t t0 = ptr[lo], t1 = ptr[lo + 1];
+      const int64_t end = t1;
+      while (t0 < t1) {
+        const int64_t mid = (t0 + t1) >> 1;
+        if (int64_t(tails[mid]) < id) t0 = mid + 1; else t1 = mid;
+      }
+      hit = t0 < end && int64_t(tails[t0]) == id;
+    }
+    label[b * ldl + j] = hit;
   }
 }
 
@@ -1225,5 +1333,64 @@ extern "C" int mgcn_score_candidates(int32_t batch, int64_t n_cand, int64_t n_lo
     hipLaunchKernelGGL(cand_tile_kernel<false>, dim3(gx), dim3(CD_THREADS), 0, s, p);
   }
   MGCN_CHECK_LAUNCH(split ? "cand_split_kernel" : "cand_tile_kernel");
+  return MGCN_OK;
+}
+
+// (14) Training on per-query candidate lists: labels, and the forward of the BCE loss with d loss / d logit.
+extern "C" int mgcn_cand_labels(int32_t batch, int64_t n_cand, const int64_t *qkey_dev, int64_t num_keys, const int64_t *keys_dev,
+                                const int64_t *ptr_dev, const int32_t *tails_dev, int64_t ent_row0, int64_t n_local,
+                                const int64_t *cand_dev, int64_t ldc, uint8_t *label_dev, int64_t ldl, void *stream) {
+  MGCN_REQUIRE(batch >= 0 && n_cand >= 0 && num_keys >= 0 && n_local >= 0 && ent_row0 >= 0, "cand_labels: bad sizes");
+  MGCN_REQUIRE(batch < (int64_t(1) << 31) - 64 && n_cand < (int64_t(1) << 31) - 64 && n_local < (int64_t(1) << 31) - 64,
+               "cand_labels: sizes exceed int32");
+  MGCN_REQUIRE(qkey_dev && ptr_dev && cand_dev && label_dev && (num_keys == 0 || (keys_dev && tails_dev)), "cand_labels: null pointer");
+  MGCN_REQUIRE(ldc >= n_cand && ldl >= n_cand, "cand_labels: leading dimension too small");
+  if (batch == 0 || n_cand == 0 || n_local == 0) return MGCN_OK;
+  const int64_t chunks = (n_cand + 255) / 256, units = int64_t(batch) * chunks;
+  const unsigned gx = unsigned(units < (int64_t(1) << 22) ? units : (int64_t(1) << 22));
+  hipLaunchKernelGGL(cand_labels_kernel, dim3(gx), dim3(256), 0, static_cast<hipStream_t>(stream), qkey_dev, keys_dev, num_keys,
+                     ptr_dev, tails_dev, cand_dev, ldc, n_cand, ent_row0, n_local, label_dev, ldl, chunks, units);
+  MGCN_CHECK_LAUNCH("cand_labels_kernel");
+  return MGCN_OK;
+}
+
+extern "C" int64_t mgcn_cand_bce_partials(int32_t batch, int64_t n_cand) {
+  if (batch <= 0 || n_cand <= 0) return 0;
+  return int64_t(batch) * ((n_cand + CD_ROWS - 1) / CD_ROWS);
+}
+
+extern "C" int mgcn_cand_bce_fwd(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *x_dev,
+                                 int64_t ldx, const float *ent_dev, int64_t lde, const float *bias_dev, const int64_t *cand_dev,
+                                 int64_t ldc, const uint8_t *label_dev, int64_t ldl, float hot, float cold, float inv_count,
+                                 float *g_dev, int64_t ldg, float *loss_partial_dev, void *stream) {
+  if (int rc = check_common("cand_bce_fwd", n_local, dim, batch)) return rc;
+  MGCN_REQUIRE(n_cand >= 0 && ent_row0 >= 0, "cand_bce_fwd: bad sizes");
+  MGCN_REQUIRE(n_cand < (int64_t(1) << 31) - 64, "cand_bce_fwd: sizes exceed int32");
+  MGCN_REQUIRE(x_dev && ent_dev && bias_dev && cand_dev && label_dev && g_dev && loss_partial_dev, "cand_bce_fwd: null pointer");
+  MGCN_REQUIRE(ldx >= dim && lde >= dim && ldc >= n_cand && ldl >= n_cand && ldg >= n_cand,
+               "cand_bce_fwd: leading dimension too small");
+  if (batch == 0 || n_cand == 0 || n_local == 0) return MGCN_OK;
+  TileArgs t = {};
+  t.a = ent_dev; t.lda = lde;
+  t.b = x_dev; t.ldb = ldx;
+  set_vec_flags(&t);
+  const bool fast = t.a_vec && t.b_vec && dim % 4 == 0;
+  CandBceArgs a = {};
+  CandArgs &p = a.c;
+  p.x = x_dev; p.ent = ent_dev; p.bias = bias_dev; p.cand = cand_dev;
+  p.ldx = ldx; p.lde = lde; p.ldc = ldc;
+  p.n_cand = n_cand; p.n_local = n_local; p.row0 = ent_row0; p.k = dim;
+  p.chunks = int32_t((n_cand + CD_ROWS - 1) / CD_ROWS);
+  p.units = int64_t(batch) * p.chunks;
+  a.label = label_dev; a.ldl = ldl; a.g = g_dev; a.ldg = ldg; a.loss_partial = loss_partial_dev;
+  a.hot = hot; a.cold = cold; a.inv_count = inv_count;
+  const unsigned gx = unsigned(p.units < (int64_t(1) << 22) ? p.units : (int64_t(1) << 22));   // beyond: grid-stride
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (fast) {
+    hipLaunchKernelGGL(cand_bce_kernel<true>, dim3(gx), dim3(CD_THREADS), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(cand_bce_kernel<false>, dim3(gx), dim3(CD_THREADS), 0, s, a);
+  }
+  MGCN_CHECK_LAUNCH("cand_bce_kernel");
   return MGCN_OK;
 }

@@ -101,6 +101,127 @@ __global__ __launch_bounds__(TPB) void rows_sum_kernel(int batch, int dim, const
 
 inline size_t rows_workspace(int64_t batch) { return (size_t(batch) * (sizeof(int64_t) + sizeof(int32_t)) + 15u) & ~size_t(15); }
 
+// ------------------------------------------------------------------------------------------------ (c) candidate lists
+// The backward of the candidate-list loss, paragraph (14) of include/mgcn_hip.h. A list position (b, j) is live iff
+// uint64(cand[b, j]) - uint64(row0) < n_local: one unsigned comparison before any address of ent / d_ent / d_bias is formed.
+constexpr int CB_CHUNK = 64;                          // list positions of a chunk (the forward's unit)
+constexpr int CB_UNR = 16;                            // row loads in flight per lane
+
+__device__ __forceinline__ int64_t cand_live_row(int64_t id, int64_t row0, int64_t n_local) {
+  const uint64_t d = uint64_t(id) - uint64_t(row0);
+  return d < uint64_t(n_local) ? int64_t(d) : int64_t(-1);
+}
+
+// dx[b, c] = sum over chunks ch ascending of s_ch, s_ch = sum over the chunk's live positions j ascending of g[b, j] ent[o_j, c],
+// every product and every sum rounded to f32. Workgroup = (query, 64 columns); wave w takes chunks w, w + 4, ... in rounds of four,
+// a lane holds one position's (row, g) of the chunk and one column; wave 0 folds a round's four sums into dx in chunk order.
+__global__ __launch_bounds__(TPB) void cand_bwd_x_kernel(int64_t n_cand, int64_t n_local, int64_t row0, int dim,
+                                                         const float *__restrict__ g, int64_t ldg, const int64_t *__restrict__ cand,
+                                                         int64_t ldc, const float *__restrict__ ent, int64_t lde,
+                                                         float *__restrict__ dx, int64_t ldx) {
+  __shared__ float part[TPB / 64][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t b = blockIdx.x;
+  const int c = blockIdx.y * 64 + lane;
+  const bool col = c < dim;
+  const int64_t chunks = (n_cand + CB_CHUNK - 1) / CB_CHUNK;
+  float acc = 0.f;
+  for (int64_t r0 = 0; r0 < chunks; r0 += TPB / 64) {
+    const int64_t ch = r0 + wave;
+    float s = 0.f;
+    if (ch < chunks) {                                // wave-uniform
+      const int64_t j = ch * CB_CHUNK + lane;
+      int64_t o_l = -1;
+      float g_l = 0.f;
+      if (j < n_cand) {
+        o_l = cand_live_row(cand[b * ldc + j], row0, n_local);
+        g_l = g[b * ldg + j];
+      }
+      const int64_t left = n_cand - ch * CB_CHUNK;
+      const int n = int(left < CB_CHUNK ? left : CB_CHUNK);
+      for (int i0 = 0; i0 < n; i0 += CB_UNR) {
+        float e[CB_UNR], gv[CB_UNR];
+        bool ok[CB_UNR];
+#pragma unroll
+        for (int i = 0; i < CB_UNR; ++i) {            // (positions past n hold row -1)
+          const int64_t o = __shfl(o_l, (i0 + i) & 63);
+          gv[i] = __shfl(g_l, (i0 + i) & 63);
+          ok[i] = o >= 0;
+          e[i] = (ok[i] && col) ? ent[o * lde + c] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < CB_UNR; ++i)
+          if (ok[i]) s = __fadd_rn(s, __fmul_rn(gv[i], e[i]));
+      }
+    }
+    part[wave][lane] = s;
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int w = 0; w < TPB / 64; ++w)
+        if (r0 + w < chunks) acc = __fadd_rn(acc, part[w][lane]);
+    }
+    __syncthreads();
+  }
+  if (wave == 0 && col) dx[b * ldx + c] = acc;
+}
+
+// The row of plan entry i (its flat position pos = b K + j looked up in cand and tested), or -1: nothing is followed unchecked
+__device__ __forceinline__ int64_t plan_row(const int64_t *__restrict__ perm, int64_t i, int64_t total, int64_t n_cand,
+                                            const int64_t *__restrict__ cand, int64_t ldc, int64_t row0, int64_t n_local,
+                                            int64_t &b, int64_t &j) {
+  const int64_t pos = perm[i];
+  if (pos < 0 || pos >= total) return -1;
+  b = pos / n_cand;
+  j = pos - b * n_cand;
+  return cand_live_row(cand[b * ldc + j], row0, n_local);
+}
+
+// d_ent[o, :] = sum of g[pos] x[b(pos), :], d_bias[o] = sum of g[pos] over the run of plan entries with row o, in plan order, each
+// the sequential f32 loop from 0. One WAVE per plan entry: the wave of a run's first entry walks the run, every other one exits;
+// lanes over columns, four column slabs (256 columns) per walk.
+__global__ __launch_bounds__(TPB) void cand_bwd_ent_kernel(int64_t total, int64_t n_cand, int64_t n_local, int64_t row0, int dim,
+                                                           const float *__restrict__ g, int64_t ldg, const int64_t *__restrict__ cand,
+                                                           int64_t ldc, const int64_t *__restrict__ perm, int64_t n_live,
+                                                           const float *__restrict__ x, int64_t ldx, float *__restrict__ d_ent,
+                                                           int64_t lde, float *__restrict__ d_bias) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t i = int64_t(blockIdx.x) * (TPB / 64) + wave; i < n_live; i += int64_t(gridDim.x) * (TPB / 64)) {
+    int64_t b = 0, j = 0, pb = 0, pj = 0;
+    const int64_t row = plan_row(perm, i, total, n_cand, cand, ldc, row0, n_local, b, j);
+    if (row < 0) continue;                            // wave-uniform
+    if (i > 0 && plan_row(perm, i - 1, total, n_cand, cand, ldc, row0, n_local, pb, pj) == row) continue;
+    const int slabs = d_ent ? (dim + 255) / 256 : 1;
+    for (int sl = 0; sl < slabs; ++sl) {
+      const int c0 = sl * 256 + lane;
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, sb = 0.f;
+      int64_t kb = b, kj = j;
+      for (int64_t k = i;;) {
+        const float gv = g[kb * ldg + kj];
+        if (d_ent) {
+          const float *xr = x + kb * ldx;
+          const float x0 = c0 < dim ? xr[c0] : 0.f, x1 = c0 + 64 < dim ? xr[c0 + 64] : 0.f;
+          const float x2 = c0 + 128 < dim ? xr[c0 + 128] : 0.f, x3 = c0 + 192 < dim ? xr[c0 + 192] : 0.f;
+          a0 = __fadd_rn(a0, __fmul_rn(gv, x0));
+          a1 = __fadd_rn(a1, __fmul_rn(gv, x1));
+          a2 = __fadd_rn(a2, __fmul_rn(gv, x2));
+          a3 = __fadd_rn(a3, __fmul_rn(gv, x3));
+        }
+        sb = __fadd_rn(sb, gv);
+        if (++k >= n_live || plan_row(perm, k, total, n_cand, cand, ldc, row0, n_local, kb, kj) != row) break;
+      }
+      if (d_ent) {
+        float *dr = d_ent + row * lde;
+        if (c0 < dim) dr[c0] = a0;
+        if (c0 + 64 < dim) dr[c0 + 64] = a1;
+        if (c0 + 128 < dim) dr[c0 + 128] = a2;
+        if (c0 + 192 < dim) dr[c0 + 192] = a3;
+      }
+      if (sl == 0 && d_bias && lane == 0) d_bias[row] = sb;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ (b) trunk tail
 constexpr int CW = 16;                                // columns of a workgroup
 constexpr int RL = TPB / CW;                          // row lanes: thread (ty, tx) walks rows ty, ty + RL, ... of column tx
@@ -295,5 +416,48 @@ extern "C" int mgcn_conve_tail_bwd(int32_t batch, int32_t dim, const float *z_de
   tail_bwd_kernel<<<dim3((dim + CW - 1) / CW), dim3(TPB), 0, static_cast<hipStream_t>(stream)>>>(
       a, x_dev, ldx, saved_dev, ldsv, gamma_dev, gx_dev, ldg, gz_dev, ldgz, d_gamma_dev, d_beta_dev);
   MGCN_CHECK_LAUNCH("mgcn_conve_tail_bwd");
+  return MGCN_OK;
+}
+
+namespace {
+// what both candidate-list backward entry points check of the arguments they share
+int check_cand_bwd(const char *what, int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *g,
+                   int64_t ldg, const int64_t *cand, int64_t ldc) {
+  MGCN_REQUIRE(batch >= 0 && n_cand >= 0 && n_local >= 0 && ent_row0 >= 0 && dim >= 1, "%s: bad sizes", what);
+  MGCN_REQUIRE(batch < (int64_t(1) << 31) - 64 && n_cand < (int64_t(1) << 31) - 64 && n_local < (int64_t(1) << 31) - 64,
+               "%s: sizes exceed int32", what);
+  MGCN_REQUIRE(g && cand, "%s: null pointer", what);
+  MGCN_REQUIRE(ldg >= n_cand && ldc >= n_cand, "%s: leading dimension too small", what);
+  return MGCN_OK;
+}
+}  // namespace
+
+extern "C" int mgcn_cand_bce_bwd_x(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *g_dev,
+                                   int64_t ldg, const int64_t *cand_dev, int64_t ldc, const float *ent_dev, int64_t lde,
+                                   float *dx_dev, int64_t ldx, void *stream) {
+  if (int rc = check_cand_bwd("cand_bce_bwd_x", batch, n_cand, n_local, ent_row0, dim, g_dev, ldg, cand_dev, ldc)) return rc;
+  MGCN_REQUIRE(ent_dev && dx_dev, "cand_bce_bwd_x: null pointer");
+  MGCN_REQUIRE(lde >= dim && ldx >= dim, "cand_bce_bwd_x: leading dimension too small");
+  if (batch == 0 || n_cand == 0 || n_local == 0) return MGCN_OK;
+  cand_bwd_x_kernel<<<dim3(unsigned(batch), unsigned((dim + 63) / 64)), dim3(TPB), 0, static_cast<hipStream_t>(stream)>>>(
+      n_cand, n_local, ent_row0, dim, g_dev, ldg, cand_dev, ldc, ent_dev, lde, dx_dev, ldx);
+  MGCN_CHECK_LAUNCH("cand_bwd_x_kernel");
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_cand_bce_bwd_ent(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *g_dev,
+                                     int64_t ldg, const int64_t *cand_dev, int64_t ldc, const int64_t *perm_dev, int64_t n_live,
+                                     const float *x_dev, int64_t ldx, float *d_ent_dev, int64_t lde, float *d_bias_dev, void *stream) {
+  if (int rc = check_cand_bwd("cand_bce_bwd_ent", batch, n_cand, n_local, ent_row0, dim, g_dev, ldg, cand_dev, ldc)) return rc;
+  MGCN_REQUIRE(perm_dev && (!d_ent_dev || x_dev), "cand_bce_bwd_ent: null pointer");   // (x is read for d_ent only)
+  MGCN_REQUIRE(!d_ent_dev || (ldx >= dim && lde >= dim), "cand_bce_bwd_ent: leading dimension too small");
+  const int64_t total = int64_t(batch) * n_cand;
+  MGCN_REQUIRE(n_live >= 0 && n_live <= total, "cand_bce_bwd_ent: n_live outside [0, batch * n_cand]");
+  if (batch == 0 || n_cand == 0 || n_local == 0 || n_live == 0 || (!d_ent_dev && !d_bias_dev)) return MGCN_OK;
+  const int64_t groups = (n_live + TPB / 64 - 1) / (TPB / 64);
+  cand_bwd_ent_kernel<<<dim3(unsigned(groups < (int64_t(1) << 22) ? groups : (int64_t(1) << 22))), dim3(TPB), 0,
+                        static_cast<hipStream_t>(stream)>>>(total, n_cand, n_local, ent_row0, dim, g_dev, ldg, cand_dev, ldc, perm_dev,
+                                                            n_live, x_dev, ldx, d_ent_dev, lde, d_bias_dev);
+  MGCN_CHECK_LAUNCH("cand_bwd_ent_kernel");
   return MGCN_OK;
 }

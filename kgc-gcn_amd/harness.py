@@ -83,6 +83,62 @@ def train_device_labels(model, queries, index, graph, optimizer, params, batch_s
     return loss_avg()
 
 
+def sample_candidates(q, index, num_entities, num_neg, generator=None, check=True):
+    """Candidate lists [B, 1 + num_neg] int64 for the queries q [B, >= 2] (src, rel): column 0 is ONE known tail of the query drawn
+    uniformly from its run in `index` (a dist.FilterIndex on q's device; every query must have a key in it, as every training
+    query has in DataLoader.train_index()), the other columns are uniform ids in [0, num_entities). A negative that happens to be
+    a known tail is simply labelled hot by cand_labels. Integer torch ops on q's device (CPU tensors work); `generator` must live
+    on that device. check=False skips the test that every query has a key (two reads back from the device): for callers that
+    have made it for all their queries already, as train_sampled_negatives does once per epoch."""
+    B, dev = q.size(0), q.device
+    keys = index.query_keys(q[:, 0], q[:, 1])
+    at = torch.searchsorted(index.keys, keys)
+    if check and B:
+        nk = index.keys.numel()
+        if nk == 0 or bool((at >= nk).any()) or not torch.equal(index.keys[at.clamp(max=nk - 1)], keys):
+            raise ValueError('sample_candidates: a query has no known tail in the index')
+    lo, hi = index.ptr[at], index.ptr[at + 1]
+    pick = lo + (torch.rand(B, generator=generator, device=dev, dtype=torch.float64) * (hi - lo).double()).long().clamp(max=hi - lo - 1)
+    cand = torch.empty((B, 1 + int(num_neg)), dtype=torch.int64, device=dev)
+    cand[:, 0] = index.tails[pick].long()
+    if num_neg:
+        cand[:, 1:] = torch.randint(0, int(num_entities), (B, int(num_neg)), generator=generator, device=dev, dtype=torch.int64)
+    return cand
+
+
+def train_sampled_negatives(model, queries, index, graph, optimizer, params, batch_size, num_neg, generator=None):
+    """One epoch like train_device_labels' eager loop, on sampled negatives: per step the candidate lists of
+    sample_candidates (one known tail + num_neg uniform ids per query) and MGCN.forward_loss_candidates over them, so that no
+    step touches a [B, N] block. `generator`: a CPU generator (or None: the default one) shuffles as train_device_labels does and
+    seeds a generator on params.device that draws the epoch's lists; a generator that lives on params.device draws the lists
+    itself and the shuffle takes the default CPU generator. Same clipping / optimizer calls as main.py:56-70."""
+    model.train()
+    loss_avg = RunningAverage()
+    dev = torch.device(params.device)
+    queries = queries.to(dev)
+    on_cpu = generator is None or generator.device.type == 'cpu'
+    order = torch.randperm(queries.size(0), generator=generator if on_cpu else None).to(dev)
+    if on_cpu and dev.type != 'cpu':
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator))
+        generator = torch.Generator(device=dev)
+        generator.manual_seed(seed)
+    n_ent = model.entity_embedding.size(0)
+    sample_candidates(queries, index, n_ent, 0, generator=generator)      # every query has a key: checked once, not per step
+    for i in range(0, queries.size(0), batch_size):
+        q = queries.index_select(0, order[i:i + batch_size])
+        cand = sample_candidates(q, index, n_ent, num_neg, generator=generator, check=False)
+        optimizer.zero_grad()
+        loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, index=index, lbl_smooth=params.lbl_smooth)
+        loss.backward()
+        if hasattr(optimizer, 'clip_and_step'):          # optim.ClipAdam: norm, clipping and update on the HIP kernels
+            optimizer.clip_and_step(params.clip_grad)
+        else:
+            nn.utils.clip_grad_norm_(parameters=model.parameters(), max_norm=params.clip_grad)
+            optimizer.step()
+        loss_avg.update(loss.item())
+    return loss_avg()
+
+
 def _captured_step(model, graph, index, optimizer, params):
     """The CapturedTrainStep of train_device_labels(captured=True): built once per (graph, index, optimizer) and kept on the model."""
     from .captured import CapturedTrainStep

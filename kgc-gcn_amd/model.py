@@ -328,6 +328,33 @@ class _ScoreBCEFn(torch.autograd.Function):
                 g.sum(1) * gl if ctx.needs_input_grad[2] else None, None, None, None)
 
 
+class _CandBCEFn(torch.autograd.Function):
+    """mean BCE over per-query candidate lists (include/mgcn_hip.h (14)): one launch leaves the loss partials and d loss / d logit
+    [B, K]; the backward is two fixed-order sums on the kernels of csrc/query_train.hip, d x over the gathered entity rows and
+    d ent / d bias over the runs of a sorted plan into a zeroed block. Nothing of size [B, N] exists; no float atomics."""
+
+    @staticmethod
+    def forward(ctx, x, ent, bias, cand, label, hot, cold):
+        loss, g = _native.cand_bce_fwd(x, ent, bias, cand, label, hot, cold)
+        # (no host read of the live count: the whole plan is handed over, its dead tail is skipped entry by entry)
+        perm, ctx.n_live = _native.cand_plan(cand, ent.size(0), count=False)
+        ctx.save_for_backward(x, ent, cand, g, perm)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        x, ent, cand, g, perm = ctx.saved_tensors
+        # d x gl, d ent gl, d bias gl with gl folded into g [B, K] first: the sums are linear in g, and the [N, dim] block is
+        # written once instead of being scaled in a second pass (gl = 1, the usual case, changes no bit of g)
+        g = g * gl
+        gx = _native.cand_bce_bwd_x(g, cand, ent) if ctx.needs_input_grad[0] else None
+        want = tuple(n for i, n in ((1, 'ent'), (2, 'bias')) if ctx.needs_input_grad[i])
+        d_ent, d_bias = (None, None)
+        if want:
+            d_ent, d_bias = _native.cand_bce_bwd_ent(g, cand, x, perm, ctx.n_live, ent.size(0), want=want)
+        return (gx, d_ent, d_bias, None, None, None, None)
+
+
 class MGCNConv(nn.Module):
     """One relational layer (model.py:47-127). Parameter names are the reference's."""
 
@@ -982,6 +1009,31 @@ class MGCN(nn.Module):
             return _ScoreBCEFn.apply(x, ent, self.conv2.bias, mask, hot, cold)
         labels = _native.label_rows(keys, index.keys, index.ptr, index.tails, n_ent, lbl_smooth=lbl_smooth)
         return self.loss_fn(_ScoreFn.apply(x, ent, self.conv2.bias), labels)
+
+    def forward_loss_candidates(self, src, rel, cand, data, index=None, labels=None, lbl_smooth=0.0):
+        """forward_loss with a per-query candidate list in place of the entity table (training on sampled negatives): the mean
+        BCE of the scores of cand [B, K] int64 (the true tails plus sampled negatives, e.g. harness.sample_candidates) against
+        targets that are hot at the known tails and cold elsewhere, smoothed with 1/N as forward_loss smooths. Exactly one of
+        `index` (DataLoader.train_index() on the device: the labels are looked up on the device, _native.cand_labels) and
+        `labels` ([B, K] uint8 / bool). The mean runs over ALL B K list positions (inv_count = 1 / (B K)): an id outside [0, N)
+        (-1 padding) contributes zero to the loss and to every gradient but still counts in the divisor. The scoring stage costs
+        B K dim, not N: no [B, N] block, mask or GEMM over the table; its backward has a fixed summation order. Everything
+        upstream (encoder, query rows, trunk and their switches) is forward_loss's."""
+        self._refuse_training_ee16('MGCN.forward_loss_candidates')
+        if (index is None) == (labels is None):
+            raise _native.NativeError('forward_loss_candidates: give exactly one of index / labels')
+        cand = self._candidate_block(cand, src.numel())
+        all_ent, all_rel = self.encode(data)
+        x = self.conv2.trunk(query_rows(self, all_ent, src), query_rows(self, all_rel, rel))
+        n_ent = all_ent.size(0)
+        ent = all_ent.contiguous()
+        x = x if x.stride(-1) == 1 else x.contiguous()
+        if labels is None:
+            labels = _native.cand_labels(index.query_keys(src, rel), index.keys, index.ptr, index.tails, cand, n_ent)
+        elif labels.dtype not in (torch.uint8, torch.bool) or tuple(labels.shape) != tuple(cand.shape):
+            raise _native.NativeError('forward_loss_candidates: labels must be uint8 / bool %s' % (tuple(cand.shape),))
+        hot, cold = _native.smoothed_targets(lbl_smooth, n_ent)
+        return _CandBCEFn.apply(x, ent, self.conv2.bias, cand, labels, hot, cold)
 
     # -- fused evaluation path (main.py:121-126 without materialising [B, N] scores) -------------
     @torch.no_grad()
