@@ -617,7 +617,8 @@ int mgcn_conve_trunk_fwd(int32_t batch, int32_t k_w, int32_t k_h, int32_t kernel
  * Reductions: no atomics, no spinning, no workgroup waits on another. Every sum over the batch is a multi-launch reduction: one
  * partial per block of rows (bn0: 8 rows; bn1, its backward sums, taps and conv bias: 16 rows; d fc_b: 32 rows; the bn0 backward
  * sums: 1 row, folded in blocks of 16 rows and then across the blocks), each a strided per-thread chain and a halving tree over the workgroup, then the partials added in ascending
- * block order from 0. h fc_w^T is cut along K into up to 128 splits of whole 16-element units; a split is one MFMA chain in
+ * block order from 0 (up to 128 partials an f32 chain; more -- bn0 past 1024 rows, the 16-row blocks past 2048 -- in a double
+ * accumulator, rounded once). h fc_w^T is cut along K into up to 128 splits of whole 16-element units; a split is one MFMA chain in
  * ascending k, the splits are added in ascending order from 0, then the bias. gz^T h is one chain over ascending rows, gz fc_w one
  * over ascending outputs. The launch plan is a function of (batch, geometry) alone: same inputs and mask, same bits.
  * workspace_dev: mgcn_conve_train_workspace(batch, ...) bytes (0 = refused), 16-byte aligned, in floats from its start (each

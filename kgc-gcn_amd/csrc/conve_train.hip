@@ -15,7 +15,7 @@
 //
 // Every reduction over the batch: one partial per block of rows (a strided per-thread chain, then a halving tree in LDS: a
 // function of the block's size alone), and the partials added in ascending block order from 0 by every consumer that needs
-// the total. No atomics, no waiting between workgroups: same inputs, same bits.
+// the total (more than TT_FOLD_F32 of them in a double accumulator, rounded once). No atomics, no waiting between workgroups: same inputs, same bits.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -38,6 +38,7 @@ constexpr int TT_SPLIT_BLOCKS = 512;
 constexpr int TT_STAGE = 4096;     // floats of gc / taps staged in LDS by tt_corr
 constexpr int TT_SLOTS_T = 5;      // ceil((1024 + 1) / 256): taps + bias per thread in tt_tap
 constexpr int TT_SLOTS_I = 4;      // 1024 / 256: image elements per thread in tt_corr
+constexpr int TT_FOLD_F32 = 128;   // partials added as an f32 chain; more of them in a double accumulator
 
 struct TGeo {
   int kw, kh, ks, F, O, H, W, P, T, I, NT, NCG;
@@ -116,7 +117,15 @@ __device__ __forceinline__ float block_sum(float v, float *red) {
   return r;
 }
 
+// partials in ascending order from 0: up to TT_FOLD_F32 of them an f32 chain. A longer chain (bn0 past 1024 rows, the 16-row
+// blocks past 2048) runs in a double accumulator and is rounded once: 512 f32 adds are ~sqrt(512) u / 4 off, which at
+// B = 4095 put rstd0 5.7 u and, through x0, rstd1 9.7 u from float64, past the 8 u such a statistic is held to
 __device__ __forceinline__ float fold(const float *__restrict__ part, int n, int64_t stride) {
+  if (n > TT_FOLD_F32) {
+    double d = 0.0;
+    for (int i = 0; i < n; ++i) d += double(part[int64_t(i) * stride]);
+    return float(d);
+  }
   float s = 0.f;
   for (int i = 0; i < n; ++i) s += part[int64_t(i) * stride];
   return s;

@@ -45,9 +45,13 @@ def module_sd(conv):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1
-@pytest.mark.parametrize('B', T.BATCHES)
-@pytest.mark.parametrize('case', T.GRID, ids=IDS)
+PARITY = [(c, b) for c in T.GRID for b in T.BATCHES] + [(c, b) for c in T.LIMIT_GRID for b in T.LIMIT_BATCHES]
+
+
+@pytest.mark.parametrize('case,B', PARITY, ids=['%s-%d' % (T.case_id(c), b) for c, b in PARITY])
 def test_grid_parity_through_the_c_abi(pkg, case, B):
+    """The grid, and the limits of the domain (trunk_ref.LIMIT_GRID: up to 1024 taps, one output position, F = 1 and
+    F > 256), to the same bar."""
     nat = pkg._native
     geom, O = T.geometry(case), case[0] * case[1]
     assert nat.conve_supported(*geom)
@@ -73,6 +77,17 @@ def test_grid_parity_through_the_c_abi(pkg, case, B):
     out_i.check('conve_trunk (indexed) ' + T.case_id(case))
     assert R.max_ratio(out_i.view, want_i, bar_i) <= 1.0
     assert torch.equal(out_i.view, nat.conve_trunk(geom, pack, ent[si].contiguous(), None, rel[ri].contiguous(), None))
+    # (c) one segment (P <= 4): no batch has a workspace, and the call succeeds with a NULL one -- the same bits
+    if T.launch_figures(case)['PQ'] == 1:
+        lib = nat.lib()
+        assert lib.mgcn_conve_trunk_workspace(B, *geom) == 0
+        out_n = R.Guarded(B, O, O + 1, DEV)
+        rc = lib.mgcn_conve_trunk_fwd(B, *geom, s.data_ptr(), O, B, None, r.data_ptr(), O, B, None, pack.data_ptr(), out_n.ptr(), O + 1,
+                                      None, 0, torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, lib.mgcn_last_error()
+        torch.cuda.synchronize()
+        out_n.check('conve_trunk (NULL workspace) ' + T.case_id(case))
+        assert torch.equal(out_n.view, out.view)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2
@@ -150,9 +165,18 @@ def test_goldens_with_the_hip_trunk(pkg, case):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3
+KS9 = (10, 20, 9, 32, False)
+
+
 def test_rows_are_bit_identical_across_batches_chunks_and_launch_forms(pkg):
+    """At the production geometry, and at the same image with ks = 9 (the generic convolution, 81 taps)."""
+    assert KS9 in T.LIMIT_GRID and KS9[:2] == T.PRODUCTION[:2]
+    for case in (T.PRODUCTION, KS9):
+        _rows_are_bit_identical(pkg, case)
+
+
+def _rows_are_bit_identical(pkg, case):
     nat = pkg._native
-    case = T.PRODUCTION
     geom, O = T.geometry(case), 200
     pack = pack_of(nat, case, T.weights(case))
     g = R.gen(12)
@@ -198,7 +222,10 @@ def test_sharded_evaluation_does_not_depend_on_the_trunk_chunk(pkg):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4
-@pytest.mark.parametrize('case', [T.PRODUCTION, SMALL], ids=[T.case_id(T.PRODUCTION), T.case_id(SMALL)])
+MANY_TAPS = (16, 32, 17, 4, True)
+
+
+@pytest.mark.parametrize('case', [T.PRODUCTION, SMALL, MANY_TAPS], ids=[T.case_id(T.PRODUCTION), T.case_id(SMALL), T.case_id(MANY_TAPS)])
 def test_non_finite_rows_stay_alone(pkg, case):
     nat = pkg._native
     geom = T.geometry(case)

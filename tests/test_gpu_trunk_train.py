@@ -42,12 +42,12 @@ def _wide(t, extra):
 class Call(object):
     """One forward + backward through the C ABI: inputs as windows (ld > O), every output a window of a guarded buffer."""
 
-    def __init__(self, nat, case, B, p, skip=()):
+    def __init__(self, nat, case, B, p, skip=(), seed=0):
         self.lib, self.case, self.B = nat.lib(), case, B
         self.geom = T.geometry(case)
         k_w, k_h, ks, F, O = self.geom
         K = T.sizes(case)[2]
-        sd, s, r, keep, inv_keep, gz = TT.inputs(case, B, p)
+        sd, s, r, keep, inv_keep, gz = TT.inputs(case, B, p, seed)
         d = lambda k: sd['conv2.' + k].to(DEV).contiguous() if 'conv2.' + k in sd else None
         self.s, self.r, self.gz = _wide(s, 3), _wide(r, 1), _wide(gz, 2)
         self.keep, self.inv_keep = (None if keep is None else keep.to(DEV).contiguous()), inv_keep
@@ -113,11 +113,14 @@ class Call(object):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1
-@pytest.mark.parametrize('case,B,p', TT.grid_cases(), ids=lambda v: T.case_id(v) if isinstance(v, tuple) else str(v))
-def test_grid_parity_through_the_c_abi(pkg, case, B, p):
-    cid = '%s-B%d-p%g' % (T.case_id(case), B, p)
-    ref = TT.reference(case, B, p)
-    c = Call(pkg._native, case, B, p)
+@pytest.mark.parametrize('case,B,p,seed', [c + (0,) for c in TT.grid_cases()] + TT.limit_cases(),
+                         ids=TT.case_ids(TT.grid_cases() + TT.limit_cases()))
+def test_grid_parity_through_the_c_abi(pkg, case, B, p, seed):
+    """The grid, and the limits of the domain (trunk_train_ref.limit_cases: up to 1024 taps, P = 1, F = 1 and F > 256,
+    B = 4096), to the same bars."""
+    cid = '%s-B%d-p%g%s' % (T.case_id(case), B, p, '-s%d' % seed if seed else '')
+    ref = TT.reference(case, B, p, seed)
+    c = Call(pkg._native, case, B, p, seed=seed)
     assert c.fwd() == 0, c.lib.mgcn_last_error()
     assert c.bwd() == 0, c.lib.mgcn_last_error()
     torch.cuda.synchronize()
@@ -131,11 +134,12 @@ def test_grid_parity_through_the_c_abi(pkg, case, B, p):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2
-@pytest.mark.parametrize('case,B,p', [(SMALL, 17, 0.2), (T.PRODUCTION, 130, 0.2)], ids=['small', 'production'])
-def test_same_inputs_same_bits_and_null_gradients(pkg, case, B, p):
+@pytest.mark.parametrize('case,B,p,seed', [(SMALL, 17, 0.2, 0), (T.PRODUCTION, 130, 0.2, 0), TT.MOST_TAPS, TT.FULL_BATCH],
+                         ids=['small', 'production', 'taps-1024', 'batch-4096'])
+def test_same_inputs_same_bits_and_null_gradients(pkg, case, B, p, seed):
     runs = []
     for skip in ((), (), ('d_fc_w', 'ds', 'd_conv_b'), ('d_conv_w', 'd_conv_b', 'd_fc_b', 'dr', 'd_g0', 'd_b0')):
-        c = Call(pkg._native, case, B, p, skip=skip)
+        c = Call(pkg._native, case, B, p, skip=skip, seed=seed)
         assert c.fwd() == 0 and c.bwd() == 0, c.lib.mgcn_last_error()
         torch.cuda.synchronize()
         c.check_guards('repeat')
@@ -172,6 +176,11 @@ def test_refusals_write_nothing(pkg):
     for what, kw in bad_b:
         assert c.bwd(**kw) == EINVAL, what
     assert c.bwd(geom=(32, 32, 3, 2, 1024)) == EUNSUPPORTED
+    # the batch limit: 4096 is taken, 4097 refused by all three entry points and by the wrapper's question
+    assert lib.mgcn_conve_train_workspace(4096, *c.geom) > 0 and lib.mgcn_conve_train_workspace(4097, *c.geom) == 0
+    assert c.fwd(batch=4097) == EUNSUPPORTED and lib.mgcn_last_error()
+    assert c.bwd(batch=4097) == EUNSUPPORTED
+    assert pkg._native.conve_train_supported(4096, c.geom) and not pkg._native.conve_train_supported(4097, c.geom)
     torch.cuda.synchronize()
     assert all(gd.untouched() for gd in c.out.values())
     assert all(torch.equal(v, c.run_stats[k]) for k, v in stats_before.items())
@@ -197,7 +206,7 @@ PARAM_OF = {'d_conv_w': 'conv_e.weight', 'd_conv_b': 'conv_e.bias', 'd_g0': 'bn0
             'd_b1': 'bn1.bias', 'd_fc_w': 'fc.weight', 'd_fc_b': 'fc.bias'}
 
 
-@pytest.mark.parametrize('case,B', [((3, 8, 3, 6, True), 17), (T.PRODUCTION, 128)], ids=['small', 'production'])
+@pytest.mark.parametrize('case,B', [((3, 8, 3, 6, True), 17), (T.PRODUCTION, 128), TT.MODULE_KS9], ids=['small', 'production', 'ks9'])
 def test_module_against_float64(pkg, monkeypatch, case, B):
     """ConvE.trunk(s, r, generator=g) + backward with the switch on against the float64 reference fed the masks drawn from a
     clone of g's state; the reference carries the torch tail (hidden_drop -> bn2 -> relu) in its own dtype, and the bars
@@ -293,6 +302,18 @@ def test_dispatch(pkg, monkeypatch):
         torch.manual_seed(8)
         outs.append(m.trunk(sw, rw))
     assert torch.equal(outs[0], outs[1]) and taken(a) == 0
+    # one row past the batch limit: the torch path's bits, and no HIP launch counted
+    a, b = conve_module(pkg, case, conve_trunk_train='hip'), conve_module(pkg, case)
+    s_full, r_full = (t.to(DEV) for t in T.queries(case, 4097))
+    assert pkg._native.conve_train_supported(4096, T.geometry(case)) and not pkg._native.conve_train_supported(4097, T.geometry(case))
+    outs = []
+    for m in (a, b):
+        torch.manual_seed(9)
+        outs.append(m.trunk(s_full, r_full))
+    assert torch.equal(outs[0], outs[1]) and taken(a) == 0
+    assert torch.equal(a.bn1.running_var, b.bn1.running_var) and torch.equal(a.bn0.running_mean, b.bn0.running_mean)
+    a.trunk(s_full[:4096], r_full[:4096])
+    assert taken(a) == 1                                                    # ... and 4096 rows take the kernels
     # dist._trunk with a generator: its torch path and the HIP path see the same masks, so they agree to rounding
     gen = lambda: torch.Generator(device=DEV).manual_seed(21)
     a, b = conve_module(pkg, case, conve_trunk_train='hip'), conve_module(pkg, case)

@@ -1,6 +1,7 @@
 """tests/trunk_train_ref.py checked on the CPU (`-m "not gpu"`): the float64 reference against the torch modules of ConvE
-in float64 with the same masks, the masks' draw order against dist._dropout, the bars against their vacuity caps, and
-what the training-mode trunk's entry points (paragraph (9) of include/mgcn_hip.h) do without a GPU."""
+in float64 with the same masks, the masks' draw order against dist._dropout, the bars against their vacuity caps, what
+the training-mode trunk's entry points (paragraph (9) of include/mgcn_hip.h) do without a GPU, and the limit cases: their
+launch arithmetic, the two conditions on their inputs (caps, relu margin) and four faults that must break a bar there."""
 import copy
 import os
 import types
@@ -26,7 +27,8 @@ def conve_module(pkg, case, **over):
     return conv.train()
 
 
-@pytest.mark.parametrize('case,B', [(T.GRID[2], 17), (T.GRID[6], 5), (T.GRID[1], 2), (T.PRODUCTION, 16)],
+@pytest.mark.parametrize('case,B', [(T.GRID[2], 17), (T.GRID[6], 5), (T.GRID[1], 2), (T.PRODUCTION, 16)]
+                         + [(c, 17 if T.launch_figures(c)['P'] == 1 else 5) for c in T.LIMIT_GRID],
                          ids=lambda v: T.case_id(v) if isinstance(v, tuple) else str(v))
 def test_reference_equals_the_torch_modules_in_float64(pkg, case, B):
     """ConvE's own torch branch (through dist._trunk, which draws the masks from a generator) cast to double, against the
@@ -156,15 +158,151 @@ def test_switch_with_cpu_tensors_takes_the_torch_path(pkg, monkeypatch):
         m.trunk(*T.queries(one, 1))
 
 
-@pytest.mark.parametrize('case,B,p', [c for c in TT.grid_cases() if c[2] < 1.0],
-                         ids=lambda v: T.case_id(v) if isinstance(v, tuple) else str(v))
-def test_bars_stay_under_their_vacuity_caps(case, B, p):
+CAPPED_CASES = [c for c in TT.grid_cases() if c[2] < 1.0]
+
+
+@pytest.mark.parametrize('case,B,p,seed', [c + (0,) for c in CAPPED_CASES] + TT.limit_cases(),
+                         ids=TT.case_ids(CAPPED_CASES + TT.limit_cases()))
+def test_bars_stay_under_their_vacuity_caps(case, B, p, seed):
     """No bar of the GPU parity grid may exceed 1e-4 of the tensor (of its terms, for the three that cancel): a kernel wrong
     in the fourth digit must fail. Printed as bar / cap."""
-    ref = TT.reference(case, B, p)
+    ref = TT.reference(case, B, p, seed)
     caps = TT.vacuity(ref)
     print('%s B=%d p=%g: %s' % (T.case_id(case), B, p, ' '.join('%s=%.3g' % kv for kv in sorted(caps.items()))))
     for name, ratio in caps.items():
         assert ratio <= 1.0, (name, ratio)
     for name in TT.STATS:
         assert ref.bar[name] <= 1e-5 * max(1.0, float(ref.ref[name].abs().max())), name
+
+
+# ------------------------------------------------------------------------------------------------ the limits of the domain
+LIMIT_IDS = TT.case_ids(TT.limit_cases())
+
+
+@pytest.mark.parametrize('case,B,p,seed', TT.limit_cases(), ids=LIMIT_IDS)
+def test_limit_cases_keep_their_relu_masks(case, B, p, seed):
+    """The smallest float64 |a| before the relu is at least 4 x the largest |a32 - a64| of the same inputs in torch-CPU f32
+    (4: what derived_bar gives a kernel over the CPU's f32 error), and f32 flips no mask: otherwise one activation at 1e-8
+    decides the case. The recorded seed is the first from 0 that meets this and the caps."""
+    ref = TT.reference(case, B, p, seed)
+    print('%s B=%d p=%g seed=%d: min |a64| = %.3g, max |a32 - a64| = %.3g, margin %.3g, %d masks flipped'
+          % (T.case_id(case), B, p, seed, ref.a_min, ref.a_err, TT.margin(ref), ref.a_flips))
+    assert ref.a_flips == 0
+    assert TT.margin(ref) >= 4.0
+    for earlier in range(seed):
+        other = TT.Reference(case, *TT.inputs(case, B, p, earlier))
+        assert TT.margin(other) < 4.0 or max(TT.vacuity(other).values()) > 1.0, earlier
+
+
+def test_module_case_at_kernel_size_9_keeps_its_relu_masks():
+    """test_module_against_float64's ks = 9 case draws its masks on the device, but the activations before the relu depend on
+    trunk_ref's weights and queries alone: the same margin, at the batch it uses."""
+    case, B = TT.MODULE_KS9
+    assert case == (10, 20, 9, 32, False) and case in T.LIMIT_GRID
+    ref = TT.reference(case, B, 0.2)
+    assert ref.a_flips == 0 and TT.margin(ref) >= 4.0
+
+
+def test_limit_cases_reach_what_they_are_there_for(pkg):
+    """The launch arithmetic of csrc/conve_train.hip restated per case: a later change of a constant or of the list cannot
+    silently empty one."""
+    cases = TT.limit_cases()
+    assert len(set(cases)) == len(cases)
+    geoms = [c[0] for c in cases]
+    assert all(g in geoms for g in T.LIMIT_GRID)
+    fig = {g: T.launch_figures(g) for g in geoms}
+    ps = [c[2] for c in cases]
+    assert all(a != b for a, b in zip(ps, ps[1:])) and set(ps) == {0.0, 0.2}            # the masks alternate
+    # tt_tap_kernel: 64 threads while T + 1 <= 64, else 256 with t = threadIdx.x + s * 256 in slot s < TT_SLOTS_T = 5
+    assert fig[(4, 8, 8, 8, True)]['T'] + 1 == 65
+    assert fig[(10, 20, 9, 32, False)]['T'] + 1 == 82 and fig[(10, 20, 9, 32, False)]['P'] == 144
+    assert 256 < fig[(16, 32, 17, 4, True)]['T'] + 1 <= 512 and fig[(16, 32, 17, 4, True)]['P'] == 256      # slots 0 and 1
+    assert fig[(16, 32, 32, 3, False)]['T'] == 1024 == 4 * 256                                             # t == T: slot 4, thread 0
+    assert TT.MOST_TAPS[0] == (16, 32, 32, 3, False) and TT.MANY_TAPS[0] == (16, 32, 17, 4, True)
+    assert sum(fig[g]['T'] + 1 > 64 for g in set(geoms)) == 4
+    assert fig[(16, 32, 32, 3, False)]['NCG'] == 3 and fig[(16, 32, 32, 3, False)]['K'] == 3
+    # the generic convolution (ks not 3, 5, 7) with a real kernel
+    assert {g[2] for g in geoms} >= {4, 6, 8, 9, 17, 32}
+    # one output position: bn1 over the batch alone, which needs rows
+    for case, B, _, _ in cases:
+        if fig[case]['P'] == 1:
+            assert case[2] == case[1] == 2 * case[0] and fig[case]['K'] == case[3] and B >= 16
+    assert [g for g in T.LIMIT_GRID if fig[g]['P'] == 1] == [(4, 8, 8, 8, True), (16, 32, 32, 3, False)]
+    assert fig[(2, 4, 3, 5, False)]['P'] == 4 and fig[(3, 5, 4, 3, True)]['P'] == 6
+    # F > 256: a second block of tt_bn1_finish_kernel / tt_prep_kernel; F = 1
+    assert (4, 8, 4, 300, True) in geoms and 300 > 256 and fig[(4, 8, 4, 300, True)]['K'] == 7500
+    assert (4, 8, 3, 1, False) in geoms
+    assert fig[(5, 8, 6, 7, True)]['K'] == 105
+    # tt_gh_kernel's 64-row blocks at a small geometry; the batch limit
+    assert [(B) for case, B, _, _ in cases if case == TT.SMALL] == [64, 65, 257]
+    full = [B for case, B, _, _ in cases if case == TT.LIMIT_B4096]
+    assert full == [4096, 4095] and TT.FULL_BATCH[:2] == (TT.LIMIT_B4096, 4096) and fig[TT.LIMIT_B4096]['P'] > 1
+    assert -(-4096 // 16) == 256 and -(-4095 // 16) == 256                   # gb[256], gg[256]: one entry per thread
+    lib = pkg._native.lib()
+    for case, B, _, _ in cases:
+        assert lib.mgcn_conve_train_workspace(B, *T.geometry(case)) > 0, (case, B)
+    for case in set(geoms):
+        geom = T.geometry(case)
+        assert lib.mgcn_conve_train_workspace(4096, *geom) > 0 and lib.mgcn_conve_train_workspace(4097, *geom) == 0
+        assert pkg._native.conve_train_supported(4096, geom) and not pkg._native.conve_train_supported(4097, geom)
+        assert (lib.mgcn_conve_train_workspace(1, *geom) > 0) == (fig[case]['P'] > 1)      # B P >= 2
+
+
+def _breaks(ref, name, value):
+    return float((value.double().reshape(ref.ref[name].shape) - ref.ref[name]).abs().max()) > ref.bar[name]
+
+
+def _broken(ref, outs):
+    return sorted(k for k, v in outs.items() if k in ref.bar and _breaks(ref, k, v))
+
+
+@pytest.mark.parametrize('spec', [TT.MANY_TAPS, TT.FULL_BATCH], ids=TT.case_ids([TT.MANY_TAPS, TT.FULL_BATCH]))
+def test_the_bars_bite_at_the_limits(spec):
+    """Value-only faults a kernel could have at these shapes, applied to the float64 computation on the CPU: each must break
+    the bar of at least one output (and, where the fault sits in one output, of that output)."""
+    case, B, p, seed = spec
+    k_w, k_h, ks, f, bias = case
+    ref = TT.reference(case, B, p, seed)
+    sd, s, r, keep, inv_keep, gz = TT.inputs(case, B, p, seed)
+    full = TT.run(case, sd, s, r, keep, inv_keep, gz, extra=('gc',))
+    # 1. the last tap of one filter dropped: from the convolution, and from d conv weight alone
+    cut = dict(sd)
+    cut['conv2.conv_e.weight'] = sd['conv2.conv_e.weight'].clone()
+    cut['conv2.conv_e.weight'][f - 1, 0, ks - 1, ks - 1] = 0.0
+    broken = _broken(ref, TT.run(case, cut, s, r, keep, inv_keep, gz))
+    print('%s: last tap of the last filter dropped from the convolution breaks %s' % (T.case_id(case), broken))
+    assert 'z' in broken
+    dw = full['d_conv_w'].clone()
+    dw[f - 1, 0, ks - 1, ks - 1] = 0.0
+    assert _breaks(ref, 'd_conv_w', dw)
+    # 2. the image shifted by one column
+    img = torch.stack([s, r], dim=2).reshape(B, 2 * k_w, k_h).roll(1, dims=2).reshape(B, k_w * k_h, 2)
+    broken = _broken(ref, TT.run(case, sd, img[:, :, 0].contiguous(), img[:, :, 1].contiguous(), keep, inv_keep, gz))
+    print('%s: image shifted by one column breaks %s' % (T.case_id(case), broken))
+    assert 'z' in broken and 'd_conv_w' in broken
+    # 3. the conv bias left out. Under a training-mode bn1 the whole of d conv bias is 0 in exact arithmetic (a kernel that
+    # left ALL of it out would be right), so what must show is a part left out: the conv-bias sums of the last block of 16
+    # rows missing from d conv bias; and, with a conv bias, the bias missing from the convolution (bn1 removes it from
+    # everything but its own mean)
+    gc = full['gc']
+    assert _breaks(ref, 'd_conv_b', gc[:B - 16].sum((0, 2, 3)))
+    if bias:
+        nob = {k: v for k, v in sd.items() if k != 'conv2.conv_e.bias'}
+        broken = _broken(ref, TT.run((k_w, k_h, ks, f, False), nob, s, r, keep, inv_keep, gz))
+        print('%s: conv bias left out of the convolution breaks %s' % (T.case_id(case), broken))
+        assert 'mu1' in broken and 'rm1' in broken
+    # 4. the last block of 16 rows dropped from a batch sum: d fc.bias, d fc.weight, d conv weight, the bn0 mean
+    h = B - 16
+    assert _breaks(ref, 'd_fc_b', gz[:h].double().sum(0))
+    part = TT.run(case, sd, s, r, keep, inv_keep, torch.cat([gz[:h], torch.zeros_like(gz[h:])]))
+    assert float((part['z'] - full['z']).abs().max()) == 0.0            # (the forward is the same: only the sums lose rows)
+    assert _breaks(ref, 'd_fc_w', part['d_fc_w'])
+    x = torch.stack([s, r], dim=2).double()
+    assert _breaks(ref, 'mu0', x[:h].sum().reshape(1) / x.numel())
+    pat = TT._patches(_x0(ref, x, sd).reshape(B, 2 * k_w, k_h), ks)
+    assert _breaks(ref, 'd_conv_w', torch.einsum('bfhw,bhwt->ft', gc[:h], pat[:h]))
+
+
+def _x0(ref, x, sd):
+    """bn0's output in float64 from the reference's own statistics."""
+    return (x - ref.ref['mu0']) * ref.ref['rstd0'] * sd['conv2.bn0.weight'].double() + sd['conv2.bn0.bias'].double()

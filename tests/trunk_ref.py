@@ -1,7 +1,8 @@
 """Float64 reference, inputs, shape grid and error bar of the eval-mode ConvE query trunk (csrc/conve_trunk.hip, paragraph
 (8) of include/mgcn_hip.h). A plain module like tests/dense_ref.py, whose constants and helpers it reuses:
 tests/test_trunk_ref_host.py checks the reference against the oracle and re-measures the constants at the trunk's lengths
-on the CPU; tests/test_gpu_trunk.py holds the kernel to the bar.
+on the CPU; tests/test_gpu_trunk.py holds the kernel to the bar. GRID is the shapes in use; LIMIT_GRID the limits of the domain
+both trunks take (kernels up to 1024 taps, one output position, F = 1 and F > 256), with what each geometry reaches beside it.
 
 The trunk, for a query with rows s, r [O], O = k_w k_h (reference model.py:161-175 in eval mode):
   1. image [2 k_w, k_h], flat element 2 j = s[j], 2 j + 1 = r[j] (interleaved, not two stacked halves);
@@ -41,6 +42,42 @@ GRID = [
 ]
 PRODUCTION = GRID[0]
 BATCHES = (1, 63, 128, 333)
+
+# The limits of the trunks' domain (O <= 512, 1 <= ks <= min(2 k_w, k_h), F >= 1), which GRID (ks in {1, 2, 3, 5, 7}, F <= 200,
+# T + 1 = ks^2 + 1 <= 50, P = H W >= 30) never reaches. What each geometry is there for, training trunk (9) and eval trunk (8):
+#   (4, 8, 8, 8, True)       P = 1 (H = W = 1, ks = k_h = 2 k_w): idx / P, idx % P and k / g.P degenerate, bn1 is a statistic
+#                            over the batch alone, K = F = 8 so the fc product has KU = 1 and S = 1; T + 1 = 65, the first
+#                            256-thread launch of tt_tap_kernel; eval: PQ = 1, plan_make returns nsplit = 0 -- the one-launch
+#                            form with no workspace at every batch
+#   (16, 32, 32, 3, False)   T = 1024: accumulator slots s >= 1 of acc[TT_SLOTS_T] hold taps and the conv-bias sum t == T lands
+#                            in slot 4 of thread 0; O = 512, NCG = 3; K = 3, the non-vector fc path; P = 1
+#   (16, 32, 17, 4, True)    T + 1 = 290: tap slots 0 and 1; P = 256; the generic convolution (KS = 0) with a large kernel
+#   (10, 20, 9, 32, False)   the production image with ks = 9: T + 1 = 82, P = 144
+#   (4, 8, 4, 300, True)     F > 256: a second block of tt_bn1_finish_kernel and tt_prep_kernel; an even generic ks; K = 7500
+#   (4, 8, 3, 1, False)      F = 1: the eval trunk's two-filter software pipeline never iterates, only the tail step runs
+#   (5, 8, 6, 7, True)       ks = 6; K = 105, odd
+#   (2, 4, 3, 5, False)      eval trunk: P = 4, PQ = 1
+#   (3, 5, 4, 3, True)       eval trunk: P = 6, PQ = 2, a second segment that is half zero-weight padding (two positions)
+LIMIT_GRID = [
+    (4, 8, 8, 8, True),
+    (16, 32, 32, 3, False),
+    (16, 32, 17, 4, True),
+    (10, 20, 9, 32, False),
+    (4, 8, 4, 300, True),
+    (4, 8, 3, 1, False),
+    (5, 8, 6, 7, True),
+    (2, 4, 3, 5, False),
+    (3, 5, 4, 3, True),
+]
+LIMIT_BATCHES = (1, 63, 333)
+
+
+def launch_figures(case):
+    """The launch arithmetic of csrc/conve_trunk.hip and csrc/conve_train.hip restated: T taps, P output positions, PQ position
+    quads (segments of the eval trunk), K = F P, NCG column groups of 13 tiles of 16 outputs."""
+    k_w, k_h, ks, f, _ = case
+    h, w, k = sizes(case)
+    return dict(T=ks * ks, P=h * w, PQ=(h * w + 3) // 4, K=k, NCG=((k_w * k_h + 15) // 16 + 12) // 13)
 
 
 def geometry(case):

@@ -41,6 +41,63 @@ def grid_cases():
     return cases + [(T.PRODUCTION, 128, 0.0), (SMALL, 17, 0.0), (SMALL, 16, 0.2), (SMALL, 17, 1.0)]
 
 
+LIMIT_B4096 = (3, 7, 2, 3, False)          # the small geometry with P > 1 (P = 30, K = 90) that takes the batch limit
+# (case, B, p, seed). p alternates between the NULL mask and 0.2; seed is the first from 0 upward at which the inputs meet both
+# conditions tests/test_trunk_train_ref_host.py asserts: the vacuity() caps, and margin() >= 4.
+_LIMIT_CASES = [
+    (T.LIMIT_GRID[0], 33, 0.0, 0),
+    (T.LIMIT_GRID[1], 65, 0.2, 0),
+    (T.LIMIT_GRID[2], 17, 0.0, 1),
+    (T.LIMIT_GRID[3], 65, 0.2, 1),
+    (T.LIMIT_GRID[4], 17, 0.0, 0),
+    (T.LIMIT_GRID[5], 17, 0.2, 0),
+    (T.LIMIT_GRID[6], 31, 0.0, 0),
+    (T.LIMIT_GRID[7], 18, 0.2, 0),
+    (T.LIMIT_GRID[8], 33, 0.0, 0),
+    (SMALL, 64, 0.2, 0),
+    (SMALL, 65, 0.0, 0),
+    (SMALL, 257, 0.2, 0),
+    (LIMIT_B4096, 4096, 0.0, 1),
+    (LIMIT_B4096, 4095, 0.2, 2),
+]
+MANY_TAPS = _LIMIT_CASES[2]
+MOST_TAPS = _LIMIT_CASES[1]
+FULL_BATCH = _LIMIT_CASES[12]
+# (case, B) of the module test at the production image with ks = 9: its inputs are trunk_ref's at seed 0, and B is one at which
+# they keep margin() >= 4 (the activations do not depend on the masks the test draws on the device)
+MODULE_KS9 = (T.LIMIT_GRID[3], 17)
+
+
+def limit_cases():
+    """(case, B, p, seed) at the limits of the training trunk's domain, which grid_cases() (T + 1 <= 50, F <= 200, P >= 30,
+    B <= 130) never reaches. Every geometry of trunk_ref.LIMIT_GRID (the training trunk takes them all):
+      4x8 ks 8 F 8 bias, B = 33     P = 1 (H = W = 1, ks = k_h = 2 k_w): idx / P, idx % P and k / g.P degenerate, bn1 is a
+                                    statistic over the batch alone (hence B >= 16: B P >= 2 is the ABI's minimum, and with very
+                                    few rows bn1 over the batch cancels everything), K = F = 8 so the fc product has KU = 1 and
+                                    S = 1; T + 1 = 65: the first 256-thread launch of tt_tap_kernel
+      16x32 ks 32 F 3, B = 65       T = 1024: accumulator slots s >= 1 of acc[TT_SLOTS_T] hold taps, and the conv-bias sum
+                                    t == T lands in slot 4 of thread 0 -- the one shape TT_SLOTS_T = 5 exists for; O = 512,
+                                    NCG = 3; K = 3, the non-vector fc path; P = 1; tt_gh_kernel's second 64-row block
+      16x32 ks 17 F 4 bias, B = 17  T + 1 = 290: tap slots 0 and 1; P = 256; tt_conv_kernel<0>, the generic convolution, with
+                                    a large kernel
+      10x20 ks 9 F 32, B = 65       the production image with ks = 9: T + 1 = 82, P = 144
+      4x8 ks 4 F 300 bias, B = 17   F > 256: the second block of tt_bn1_finish_kernel and tt_prep_kernel; an even generic ks;
+                                    K = 7500
+      4x8 ks 3 F 1, B = 17          F = 1
+      5x8 ks 6 F 7 bias, B = 31     ks = 6; K = 105, odd
+      2x4 ks 3 F 5, B = 18          P = 4
+      3x5 ks 4 F 3 bias, B = 33     P = 6
+    the small geometry 4x8 ks 3 F 8 at B = 64, 65, 257: tt_gh_kernel's 64-row blocks (r0 = blockIdx.y 64) full, crossed by one
+    row, and five of them; and the batch limit at 3x7 ks 2 F 3 (P = 30): B = 4096 = TT_MAX_B fills gb[256] and gg[256] of
+    tt_bn0_bwd_apply_kernel, one entry per thread, and B = 4095 leaves the last of the 256 blocks of 16 rows one short."""
+    return list(_LIMIT_CASES)
+
+
+def case_ids(cases):
+    """pytest ids of (case, B, p[, seed]) tuples: those pytest itself forms from the three values, '-sN' added for a seed."""
+    return ['%s-%d-%s%s' % (T.case_id(c[0]), c[1], c[2], '-s%d' % c[3] if len(c) > 3 else '') for c in cases]
+
+
 def cancelling_of(case):
     """The tensors whose exact value is 0 for this geometry. With a 1 x 1 kernel c[b, f, :] = w[f] x0[b, :] + cb[f], and bn1
     removes the per-filter scale w[f] as it removes the shift cb[f]: d conv weight cancels like the other three (its
@@ -48,14 +105,15 @@ def cancelling_of(case):
     return CANCELLING + (('d_conv_w',) if case[2] == 1 else ())
 
 
-def inputs(case, batch, p):
+def inputs(case, batch, p, seed=0):
     """(sd, s, r, keep, inv_keep, gz) on the CPU, f32: trunk_ref's weights and queries, a seeded keep-mask of rate 1 - p
-    (None at p = 0, zeros with inv_keep = 0 at p = 1) and a seeded +-U[0.25, 1] gradient of z."""
+    (None at p = 0, zeros with inv_keep = 0 at p = 1) and a seeded +-U[0.25, 1] gradient of z. `seed` picks another draw of
+    all of them (0: the one every case of grid_cases() has always had)."""
     _, _, k = T.sizes(case)
     o = case[0] * case[1]
-    sd = T.weights(case)
-    s, r = T.queries(case, batch)
-    g = R.gen(R.seed_of(12, batch, int(round(p * 1000)), *T.geometry(case)))
+    sd = T.weights(case, seed)
+    s, r = T.queries(case, batch, seed)
+    g = R.gen(R.seed_of(12, batch, int(round(p * 1000)), *(T.geometry(case) + ((seed,) if seed else ()))))
     gz = R.pm_uniform((batch, o), g)
     if p <= 0:
         keep, inv_keep = None, 1.0
@@ -73,10 +131,11 @@ def _patches(x, ks):
     return pat.reshape(b, pat.size(1), pat.size(2), ks * ks)
 
 
-def run(case, sd, s, r, keep, inv_keep, gz, dtype=torch.float64, with_mag=False, tail=None):
+def run(case, sd, s, r, keep, inv_keep, gz, dtype=torch.float64, with_mag=False, tail=None, extra=()):
     """Every output of the forward and the backward in `dtype` (a dict of detached tensors), and with `with_mag` the
     magnitudes of the reduced ones (same keys). `tail(z, dtype) -> (y, loss)`: backpropagate that loss instead of gz (the
-    module test's hidden_drop -> bn2 -> relu), and return y as well."""
+    module test's hidden_drop -> bn2 -> relu), and return y as well. `extra`: intermediates to return with the outputs, 'a'
+    (the activation before the relu, [B, F, H, W]) and 'gc' (the gradient of the convolution's output)."""
     k_w, k_h, ks, f, bias = case
     b = s.size(0)
     t = lambda k: sd['conv2.' + k].to(dtype)
@@ -132,6 +191,9 @@ def run(case, sd, s, r, keep, inv_keep, gz, dtype=torch.float64, with_mag=False,
         out['d_conv_b'] = c.grad.sum((0, 2, 3))
     if y is not None:
         out['y'] = y
+    for k, v in (('a', a), ('gc', c.grad)):
+        if k in extra:
+            out[k] = v
     out = {k: v.detach() for k, v in out.items()}
     if not with_mag:
         return out
@@ -169,8 +231,12 @@ class Reference(object):
 
     def __init__(self, case, sd, s, r, keep, inv_keep, gz, tail=None):
         self.case = case
-        self.ref, self.mag = run(case, sd, s, r, keep, inv_keep, gz, torch.float64, with_mag=True, tail=tail)
-        f32 = run(case, sd, s, r, keep, inv_keep, gz, torch.float32, tail=tail)
+        self.ref, self.mag = run(case, sd, s, r, keep, inv_keep, gz, torch.float64, with_mag=True, tail=tail, extra=('a',))
+        f32 = run(case, sd, s, r, keep, inv_keep, gz, torch.float32, tail=tail, extra=('a',))
+        a64, a32 = self.ref.pop('a'), f32.pop('a').double()
+        # the relu masks: smallest |a| in float64, largest |a32 - a64|, and how many masks torch-CPU f32 flips
+        self.a_min, self.a_err = float(a64.abs().min()), float((a32 - a64).abs().max())
+        self.a_flips = int(((a32 > 0) != (a64 > 0)).sum())
         self.cpu_err = {k: float((f32[k].double() - v).abs().max()) for k, v in self.ref.items()}
         self.floor = {k: 8 * U * float(self.mag[k].abs().max()) for k in self.ref}
         self.bar = {k: R.derived_bar(self.cpu_err[k], self.floor[k]) for k in self.ref}
@@ -183,9 +249,18 @@ class Reference(object):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(case, batch, p):
-    """The reference of inputs(case, batch, p), computed once per session and shared (treat it as read-only)."""
-    return Reference(case, *inputs(case, batch, p))
+def reference(case, batch, p, seed=0):
+    """The reference of inputs(case, batch, p, seed), computed once per session and shared (treat it as read-only)."""
+    return Reference(case, *inputs(case, batch, p, seed))
+
+
+def margin(ref):
+    """smallest float64 |a| / largest |a32 - a64| of the activations before the relu (inf where torch-CPU f32 is exact), or 0
+    when torch-CPU f32 flips a mask. Below 4 -- the factor derived_bar gives a kernel over the CPU's f32 error -- an f32
+    evaluation inside its bar may flip a relu mask, and the case is a coin toss."""
+    if ref.a_flips:
+        return 0.0
+    return math.inf if ref.a_err == 0.0 else ref.a_min / ref.a_err
 
 
 def vacuity(ref):
