@@ -903,6 +903,44 @@ int mgcn_cand_bce_bwd_ent(int32_t batch, int64_t n_cand, int64_t n_local, int64_
                           int64_t ldg, const int64_t *cand_dev, int64_t ldc, const int64_t *perm_dev, int64_t n_live,
                           const float *x_dev, int64_t ldx, float *d_ent_dev, int64_t lde, float *d_bias_dev, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (15) Counter-drawn candidate lists (csrc/dropout.hip, next to the Philox function it calls) — additive,
+ * MGCN_ABI_VERSION stays 4. The lists (14) trains on, one known tail plus sampled negatives per query, as a pure function of
+ * (seed, step, global batch row, list position) and of the index: every rank of a sharded step draws the same [B, K] block
+ * without an exchange, and a checkpoint restores the stream from (seed, step count). Integers only, so the bits are exact.
+ *
+ *   - key = sm(sm(sm(seed) ^ step) ^ site) of (12) with the site id 0x2000; the host forms it and passes it by value.
+ *   - For list position (b, j), with the 64-bit global batch row row = row0 + b: the words w0..w3 are Philox4x32-10 of (12) with
+ *     key words (key & 0xffffffff, key >> 32) and counter (row_lo, row_hi, j >> 1, 0); r = w0 | w1 << 32 for even j,
+ *     r = w2 | w3 << 32 for odd j. One Philox call serves two positions.
+ *   - j >= 1 (negatives): cand[b * ldc + j] = (r * num_entities) >> 64, the high half of the 128-bit product: an id in
+ *     [0, num_entities).
+ *   - j == 0 (one known tail): qkey[b] is looked up in keys (the lookup of mgcn_filter_mask); with its run [lo, hi) =
+ *     [ptr[i], ptr[i + 1]): cand[b * ldc] = tails[lo + ((r * (hi - lo)) >> 64)]. It is -1 when the key is absent or the run is
+ *     empty, reversed or not inside [0, n_tails]: the kernel follows nothing it has not checked. -1 is a dead position of (14):
+ *     it contributes zero and counts in the divisor.
+ *   - label_dev (optional) [batch, n_cand] uint8, rows ldl bytes apart: 1 iff 0 <= id < num_entities and the id is found in the
+ *     query's run by mgcn_cand_labels' binary search (the run the thread already holds; no run: 0), else 0. For an index whose
+ *     runs are ascending with tails in [0, num_entities), column 0 is therefore 1 wherever it is not -1, and the block equals
+ *     mgcn_cand_labels(..., ent_row0 = 0, n_local = num_entities) of the drawn list bit for bit: the GLOBAL label, valid on any
+ *     shard because mgcn_cand_bce_fwd never reads the label of a dead position. label_dev == NULL removes only that work.
+ *
+ * mgcn_cand_draw: one launch, at most 2048 workgroups of 256 threads grid-striding over (b, j >> 1); no LDS, no atomics, 64-bit
+ *   index arithmetic. Columns n_cand .. ldc of a padded row are not touched. ptr holds num_keys + 1 entries, tails n_tails.
+ * mgcn_cand_draw_host: the same block on the CPU over host pointers, from the SAME inline function the kernel calls: test
+ *   infrastructure, the role mgcn_dropout_mask_host plays in (12).
+ * MGCN_EINVAL, nothing launched and nothing written (all checks precede the first HIP call): a null qkey / ptr / cand, a null
+ * keys with num_keys > 0 or a null tails with n_tails > 0; batch < 0, n_cand < 1, num_keys < 0, n_tails < 0; num_entities outside
+ * [1, 2^40]; batch or n_cand at or above 2^31 - 64; ldc < n_cand, or ldl < n_cand when labels are asked for; batch x leading
+ * dimension above 2^60. batch == 0 launches nothing.
+ */
+int mgcn_cand_draw(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
+                   const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails, uint64_t key,
+                   uint64_t row0, int64_t *cand_dev, int64_t ldc, uint8_t *label_dev, int64_t ldl, void *stream);
+int mgcn_cand_draw_host(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_host, int64_t num_keys,
+                        const int64_t *keys_host, const int64_t *ptr_host, const int32_t *tails_host, int64_t n_tails, uint64_t key,
+                        uint64_t row0, int64_t *cand_host, int64_t ldc, uint8_t *label_host, int64_t ldl);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,8 @@ _SIGNATURES = {
                                                    _f32, _ptr]),
     'mgcn_dropout_mask_dev': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _u64, _u64, _u32, _ptr]),
     'mgcn_dropout_mask_host': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _u64, _u64, _u32]),
+    'mgcn_cand_draw': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _u64, _u64, _ptr, _i64, _ptr, _i64, _ptr]),
+    'mgcn_cand_draw_host': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _u64, _u64, _ptr, _i64, _ptr, _i64]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
     'mgcn_ingest_count': (_i64, [_ptr, _i32]),
@@ -1634,6 +1636,63 @@ def dropout_mask_host(rows, cols, key, row0, p):
     _check(lib().mgcn_dropout_mask_host(int(rows), int(cols), out.data_ptr(), int(cols),
                                         int(key) & _M64, int(row0) & _M64, dropout_scale(p)[0]), 'mgcn_dropout_mask_host')
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# (15) counter-drawn candidate lists (csrc/dropout.hip)
+CAND_DRAW_SITE = 0x2000
+
+
+def _cand_draw(fn, what, on_gpu, qkey, keys, ptr, tails, num_entities, n_cand, key, row0, labels, out):
+    B, K = qkey.numel(), int(n_cand)
+    dev = qkey.device
+    if dev.type != ('cuda' if on_gpu else 'cpu'):
+        raise NativeError('%s: the tensors must live on %s (got %s)' % (what, 'a GPU' if on_gpu else 'the CPU', dev))
+    if qkey.dim() != 1 or ptr.numel() != keys.numel() + 1:
+        raise NativeError('%s: qkey must be [B] and ptr must have len(keys) + 1 entries' % what)
+    cand, label = out if isinstance(out, (tuple, list)) else (out, None)
+    if cand is None:
+        cand = torch.empty((B, max(K, 0)), dtype=torch.int64, device=dev)
+    if label is None and labels:
+        label = torch.empty((B, max(K, 0)), dtype=torch.uint8, device=dev)
+    if not labels:
+        label = None
+    _same_device(qkey, keys, ptr, tails, cand, label)
+
+    def block(t, dtype, name):
+        if t.dim() != 2 or tuple(t.shape) != (B, K) or (t.dtype != dtype and not (dtype == torch.uint8 and t.dtype == torch.bool)) \
+                or (K > 1 and t.stride(1) != 1) or (B > 1 and t.stride(0) < K):
+            raise NativeError('%s: %s must be %s (%d, %d) with unit column stride and rows that do not overlap, got %s %s strides %s'
+                              % (what, name, dtype, B, K, t.dtype, tuple(t.shape), t.stride()))
+        return t.data_ptr(), _ld(t)
+
+    def arr(t, dtype, name):
+        if t.dtype != dtype or (t.numel() > 1 and not t.is_contiguous()):
+            raise NativeError('%s: %s must be a contiguous %s array' % (what, name, dtype))
+        return t.data_ptr() if t.numel() else None
+
+    cp, ldc = block(cand, torch.int64, 'cand') if K >= 1 else (cand.data_ptr(), 0)
+    lp, ldl = (block(label, torch.uint8, 'label') if K >= 1 else (label.data_ptr(), 0)) if label is not None else (None, 0)
+    args = [B, K, int(num_entities), arr(qkey, torch.int64, 'qkey') if B else qkey.new_zeros(1).data_ptr(), keys.numel(),
+            arr(keys, torch.int64, 'keys'), arr(ptr, torch.int64, 'ptr'), arr(tails, torch.int32, 'tails'), tails.numel(),
+            int(key) & _M64, int(row0) & _M64, cp, ldc, lp, ldl]
+    _check(fn(*(args + ([_stream(cand)] if on_gpu else []))), what)
+    return cand, label
+
+
+def cand_draw(qkey, keys, ptr, tails, num_entities, n_cand, key, row0=0, labels=True, out=None):
+    """(15) (cand [B, n_cand] int64, label [B, n_cand] uint8 or None): the candidate lists of the queries with keys qkey [B] under
+    `key` (dropout_key(seed, step, CAND_DRAW_SITE)), row b being global batch row row0 + b. Column 0 is one known tail of the query
+    drawn from its run in the keys / ptr / tails arrays of filter_mask() (-1 for a query without one), the other columns are ids
+    in [0, num_entities); label is cand_labels() of the drawn list against the whole table. One launch (see mgcn_cand_draw).
+    out: a cand tensor, or (cand, label), to write into (padded row views are fine)."""
+    return _cand_draw(lib().mgcn_cand_draw, 'mgcn_cand_draw', True, qkey, keys, ptr, tails, num_entities, n_cand, key, row0, labels, out)
+
+
+def cand_draw_host(qkey, keys, ptr, tails, num_entities, n_cand, key, row0=0, labels=True, out=None):
+    """(15) cand_draw on CPU tensors, from the same inline function the kernel calls: test infrastructure."""
+    return _cand_draw(lib().mgcn_cand_draw_host, 'mgcn_cand_draw_host', False, qkey, keys, ptr, tails, num_entities, n_cand, key, row0,
+                      labels, out)
 
 
 class IngestUnsupported(NativeError):

@@ -4,6 +4,8 @@
 // loading a saved one. Streaming kernels: one Philox call serves four columns, one lane moves one 16-byte group when base pointers
 // and leading dimensions allow it and takes the element-wise path otherwise (same bits). No atomics, no LDS, no inline assembly;
 // all index arithmetic is 64-bit.
+// The same Philox function also draws the candidate lists of sampled-negative training (include/mgcn_hip.h (15)):
+// mgcn_cand_draw and its host twin, at the end of the anonymous namespace.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -275,7 +277,126 @@ int mask_launch(const char *what, int64_t rows, int32_t cols, uint8_t *mask_dev,
   return MGCN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Counter-drawn candidate lists (include/mgcn_hip.h (15)): list position (b, j) of a [B, K] block is a pure function
+// of (key, global batch row row0 + b, j) and of the index, so every rank of a sharded step draws the same lists without an
+// exchange. One Philox call (counter word 2 = j >> 1) serves positions 2 jp and 2 jp + 1. Integers only.
+struct DrawArgs {
+  int64_t n_cand, num_entities;
+  const int64_t *qkey;
+  int64_t num_keys;
+  const int64_t *keys, *ptr;
+  const int32_t *tails;
+  int64_t n_tails;
+  uint64_t key, row0;
+  int64_t *cand;
+  int64_t ldc;
+  uint8_t *label;      // null: no labels, and no key lookup for the pairs that hold negatives only
+  int64_t ldl;
+};
+
+// the high half of the 128-bit product: floor(r m / 2^64), a value in [0, m)
+__host__ __device__ inline uint64_t mul_hi64(uint64_t r, uint64_t m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umul64hi(r, m);
+#else
+  return uint64_t((static_cast<unsigned __int128>(r) * m) >> 64);
+#endif
+}
+
+// Positions 2 jp and 2 jp + 1 of row b. The ONE definition: draw_kernel and mgcn_cand_draw_host both call it.
+__host__ __device__ inline void draw_pair(const DrawArgs &a, int64_t b, int64_t jp) {
+  uint32_t w[4];
+  dropout_words(a.key, a.row0 + uint64_t(b), uint32_t(jp), w);
+  const uint64_t r[2] = {uint64_t(w[0]) | uint64_t(w[1]) << 32, uint64_t(w[2]) | uint64_t(w[3]) << 32};
+  // the query's run of known tails [lo, hi): mgcn_filter_mask's lookup; a run that is empty, reversed or leaves [0, n_tails] is no
+  // run (lo = hi = 0), and nothing of tails is addressed through it
+  int64_t lo = 0, hi = 0;
+  if (a.label || jp == 0) {
+    const int64_t q = a.qkey[b];
+    int64_t k0 = 0, k1 = a.num_keys;
+    while (k0 < k1) {
+      const int64_t mid = (k0 + k1) >> 1;
+      if (a.keys[mid] < q) k0 = mid + 1; else k1 = mid;
+    }
+    if (k0 < a.num_keys && a.keys[k0] == q) {
+      const int64_t p0 = a.ptr[k0], p1 = a.ptr[k0 + 1];
+      if (p0 >= 0 && p0 < p1 && p1 <= a.n_tails) lo = p0, hi = p1;
+    }
+  }
+  for (int h = 0; h < 2; ++h) {
+    const int64_t j = 2 * jp + h;
+    if (j >= a.n_cand) break;
+    int64_t id;
+    if (j == 0)
+      id = hi > lo ? int64_t(a.tails[lo + int64_t(mul_hi64(r[0], uint64_t(hi - lo)))]) : int64_t(-1);
+    else
+      id = int64_t(mul_hi64(r[h], uint64_t(a.num_entities)));
+    a.cand[b * a.ldc + j] = id;
+    if (a.label) {
+      // the GLOBAL label, mgcn_cand_labels' for the shard [0, num_entities): the id is an entity and is found in the run
+      uint8_t hit = 0;
+      if (uint64_t(id) < uint64_t(a.num_entities)) {
+        int64_t t0 = lo, t1 = hi;
+        while (t0 < t1) {
+          const int64_t mid = (t0 + t1) >> 1;
+          if (int64_t(a.tails[mid]) < id) t0 = mid + 1; else t1 = mid;
+        }
+        hit = t0 < hi && int64_t(a.tails[t0]) == id;
+      }
+      a.label[b * a.ldl + j] = hit;
+    }
+  }
+}
+
+__global__ __launch_bounds__(TPB) void draw_kernel(int64_t batch, int32_t npairs, DrawArgs a) {
+  const int64_t units = batch * npairs, stride = int64_t(gridDim.x) * TPB;
+  for (int64_t u = int64_t(blockIdx.x) * TPB + threadIdx.x; u < units; u += stride) {
+    int64_t b;
+    int32_t jp;
+    unit_of(u, npairs, b, jp);
+    draw_pair(a, b, jp);
+  }
+}
+
+// every check of mgcn_cand_draw / mgcn_cand_draw_host; MGCN_OK, or the code with the message set
+int check_draw(const char *what, int64_t batch, const DrawArgs &a) {
+  MGCN_REQUIRE(batch >= 0 && a.n_cand >= 1 && a.num_keys >= 0 && a.n_tails >= 0, "%s: bad sizes (batch = %lld, n_cand = %lld, num_keys = %lld, n_tails = %lld)",
+               what, (long long)batch, (long long)a.n_cand, (long long)a.num_keys, (long long)a.n_tails);
+  MGCN_REQUIRE(a.num_entities >= 1 && a.num_entities <= MAX_ROWS, "%s: num_entities = %lld outside [1, 2^40]", what, (long long)a.num_entities);
+  MGCN_REQUIRE(batch < (int64_t(1) << 31) - 64 && a.n_cand < (int64_t(1) << 31) - 64, "%s: sizes exceed int32", what);
+  MGCN_REQUIRE(a.qkey && a.ptr && a.cand && (a.num_keys == 0 || a.keys) && (a.n_tails == 0 || a.tails), "%s: null pointer", what);
+  MGCN_REQUIRE(a.ldc >= a.n_cand && (!a.label || a.ldl >= a.n_cand), "%s: leading dimension smaller than n_cand = %lld", what, (long long)a.n_cand);
+  const int64_t most = (int64_t(1) << 60) / (batch > 0 ? batch : 1);
+  MGCN_REQUIRE(a.ldc <= most && (!a.label || a.ldl <= most), "%s: batch x leading dimension exceeds 2^60 elements", what);
+  return MGCN_OK;
+}
+
 }  // namespace
+
+extern "C" int mgcn_cand_draw(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
+                              const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails, uint64_t key,
+                              uint64_t row0, int64_t *cand_dev, int64_t ldc, uint8_t *label_dev, int64_t ldl, void *stream) {
+  const char *what = "mgcn_cand_draw";
+  const DrawArgs a = {n_cand, num_entities, qkey_dev, num_keys, keys_dev, ptr_dev, tails_dev, n_tails, key, row0, cand_dev, ldc, label_dev, ldl};
+  if (int rc = check_draw(what, batch, a)) return rc;
+  if (batch == 0) return MGCN_OK;
+  const int32_t npairs = int32_t((n_cand + 1) / 2);
+  draw_kernel<<<dim3(grid_for(batch * npairs)), dim3(TPB), 0, static_cast<hipStream_t>(stream)>>>(batch, npairs, a);
+  MGCN_CHECK_LAUNCH(what);
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_cand_draw_host(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_host, int64_t num_keys,
+                                   const int64_t *keys_host, const int64_t *ptr_host, const int32_t *tails_host, int64_t n_tails,
+                                   uint64_t key, uint64_t row0, int64_t *cand_host, int64_t ldc, uint8_t *label_host, int64_t ldl) {
+  const DrawArgs a = {n_cand, num_entities, qkey_host, num_keys, keys_host, ptr_host, tails_host, n_tails, key, row0, cand_host, ldc, label_host, ldl};
+  if (int rc = check_draw("mgcn_cand_draw_host", batch, a)) return rc;
+  const int64_t npairs = (n_cand + 1) / 2;
+  for (int64_t b = 0; b < batch; ++b)
+    for (int64_t jp = 0; jp < npairs; ++jp) draw_pair(a, b, jp);
+  return MGCN_OK;
+}
 
 extern "C" int mgcn_dropout_apply(int64_t rows, int32_t cols, const float *x_dev, int64_t ldx, float *out_dev, int64_t ldo, uint64_t key,
                                   uint64_t row0, uint32_t threshold, float inv_keep, void *stream) {

@@ -639,6 +639,31 @@ class _ScoreBCEShardFn(torch.autograd.Function):
         return _ScoreBCEFn.backward(ctx, gl) + (None,)
 
 
+class _CandBCEShardFn(torch.autograd.Function):
+    """model._CandBCEFn on this rank's entity rows [row0, row0 + ent.size(0)) (include/mgcn_hip.h (14), the ent_row0 / n_local
+    form): list positions whose id another rank owns are dead here, they write g = 0, add no loss term and still count in the
+    divisor B K, so the ranks' losses and d x add up to the one-rank step's; d ent and d bias are the rank's rows, complete."""
+
+    @staticmethod
+    def forward(ctx, x, ent, bias, cand, label, hot, cold, row0):
+        loss, g = _native.cand_bce_fwd(x, ent, bias, cand, label, hot, cold, ent_row0=row0)
+        perm, ctx.n_live = _native.cand_plan(cand, ent.size(0), ent_row0=row0, count=False)
+        ctx.row0 = int(row0)
+        ctx.save_for_backward(x, ent, cand, g, perm)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        x, ent, cand, g, perm = ctx.saved_tensors
+        g = g * gl                                           # (as model._CandBCEFn: gl = 1 changes no bit of g)
+        gx = _native.cand_bce_bwd_x(g, cand, ent, ent_row0=ctx.row0) if ctx.needs_input_grad[0] else None
+        want = tuple(n for i, n in ((1, 'ent'), (2, 'bias')) if ctx.needs_input_grad[i])
+        d_ent, d_bias = (None, None)
+        if want:
+            d_ent, d_bias = _native.cand_bce_bwd_ent(g, cand, x, perm, ctx.n_live, ent.size(0), ent_row0=ctx.row0, want=want)
+        return (gx, d_ent, d_bias, None, None, None, None, None)
+
+
 def _dropout(x, p, generator):
     """F.dropout with the keep-mask drawn from `generator` (model._drawn_dropout: the one both trunk paths use)."""
     from .model import _drawn_dropout
@@ -815,10 +840,38 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
     forward_loss + backward + clip_grad_norm_ + step bit for bit AT ANY DROPOUT.
     Returns the global loss (0-dim tensor, detached)."""
     import torch.nn.functional as F
+    ex, ent, xt = _sharded_trunk(model, graph, src, rel, optimizer, group, generator, 'train_step_sharded')
+    n0, n1, W = ex.n0, ex.n1, ex.world
+    bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]
+    N = ex.total
+    keys = index.query_keys(src, rel)
+    if _native.score_bce_supported(xt, ent) and n1 > n0:
+        hot, cold = _native.smoothed_targets(lbl_smooth, N)
+        mask = _native.filter_mask(keys, index.keys, index.ptr, index.tails, n1 - n0, ent_row0=n0)
+        loss = _ScoreBCEShardFn.apply(xt, ent, bias, mask, hot, cold, N)
+    elif n1 == n0:      # a rank without entity rows scores nothing, but takes part in the backward's collectives
+        loss = (xt * 0.0).sum()
+    else:               # batch sizes the fused launch does not take: the scores of the rank's entities, then the BCE
+        from .model import _ScoreFn
+        labels = _native.label_rows(keys, index.keys, index.ptr, index.tails, n1 - n0, lbl_smooth=lbl_smooth, num_entities=N,
+                                    ent_row0=n0)
+        scores = _ScoreFn.apply(xt, ent, bias)
+        # one rank: forward_loss's own form (BCELoss's mean); several: the rank's sum over the global count, the ranks' parts add up
+        loss = model.loss_fn(scores, labels) if W == 1 else \
+            F.binary_cross_entropy(scores, labels, reduction='sum') * (1.0 / (xt.size(0) * N))
+    return _sharded_finish(model, ex, loss, optimizer, clip, group)
+
+
+def _sharded_trunk(model, graph, src, rel, optimizer, group, generator, what):
+    """What the sharded steps share up to the scorer: the refusals and setup, the gradients zeroed, the partitioned encoder (per
+    layer: aggregate, train epilogue, dropout, row gather) and the ConvE trunk of the whole batch, its output behind
+    _AllReduceGradFn at W > 1 (every rank's scorer returns a partial d x). Returns (exchange, ent = this rank's rows [n1 - n0, O]
+    of the last layer's output, xt = the trunk's output [B, O])."""
+    import torch.nn.functional as F
     if _native.is_ee16(model.edge_embeddings):
-        raise _native.NativeError('train_step_sharded: this model holds its per-edge tables in bf16 (params.edge_table_dtype), '
-                                  'which is inference-only')
-    csr, ex = _sharded_setup(model, graph, group, 'train_step_sharded')
+        raise _native.NativeError('%s: this model holds its per-edge tables in bf16 (params.edge_table_dtype), '
+                                  'which is inference-only' % what)
+    csr, ex = _sharded_setup(model, graph, group, what)
     n0, n1, W = ex.n0, ex.n1, ex.world
     model.train()
     optimizer.zero_grad()
@@ -828,7 +881,7 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
         bn = layer.ent_bn
         if not (bn.track_running_stats and bn.momentum is not None and bn.affine and
                 _native.matmul_tn_supported(layer.in_channels, layer.out_channels)):
-            raise _native.NativeError('train_step_sharded: layer %s is outside the HIP training path' % (layer,))
+            raise _native.NativeError('%s: layer %s is outside the HIP training path' % (what, layer))
     x, rel_e = model.entity_embedding, model.relation_embedding
     drop_ctx = model._begin_dropout_step()       # (seed, step) with the counter-based dropout on, else None
     for li, (layer, table) in enumerate(zip(layers, tables)):
@@ -861,23 +914,13 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
     xt = _trunk(model.conv2, query_rows(model, x, src), query_rows(model, rel_e, rel), generator)
     if W > 1:
         xt = _AllReduceGradFn.apply(xt, ex)
-    bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]
-    N = ex.total
-    keys = index.query_keys(src, rel)
-    if _native.score_bce_supported(xt, ent) and n1 > n0:
-        hot, cold = _native.smoothed_targets(lbl_smooth, N)
-        mask = _native.filter_mask(keys, index.keys, index.ptr, index.tails, n1 - n0, ent_row0=n0)
-        loss = _ScoreBCEShardFn.apply(xt, ent, bias, mask, hot, cold, N)
-    elif n1 == n0:      # a rank without entity rows scores nothing, but takes part in the backward's collectives
-        loss = (xt * 0.0).sum()
-    else:               # batch sizes the fused launch does not take: the scores of the rank's entities, then the BCE
-        from .model import _ScoreFn
-        labels = _native.label_rows(keys, index.keys, index.ptr, index.tails, n1 - n0, lbl_smooth=lbl_smooth, num_entities=N,
-                                    ent_row0=n0)
-        scores = _ScoreFn.apply(xt, ent, bias)
-        # one rank: forward_loss's own form (BCELoss's mean); several: the rank's sum over the global count, the ranks' parts add up
-        loss = model.loss_fn(scores, labels) if W == 1 else \
-            F.binary_cross_entropy(scores, labels, reduction='sum') * (1.0 / (xt.size(0) * N))
+    return ex, ent, xt
+
+
+def _sharded_finish(model, ex, loss, optimizer, clip, group):
+    """What the sharded steps share after the scorer: the backward into the flat bucket, its one reduction, clipping and the
+    optimizer step, and the ranks' losses added up. Returns the global loss (0-dim tensor, detached)."""
+    W = ex.world
     bucket = _bucket_grads(model) if W > 1 else None
     loss.backward()
     if W > 1:
@@ -913,5 +956,74 @@ def train_epoch_sharded(model, queries, index, graph, optimizer, params, batch_s
         q = queries.index_select(0, order[i:i + batch_size])
         loss = train_step_sharded(model, graph, q[:, 0], q[:, 1], index, optimizer, lbl_smooth=params.lbl_smooth,
                                   clip=params.clip_grad, group=group)
+        loss_avg.update(loss.item())
+    return loss_avg()
+
+
+def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer, labels=None, lbl_smooth=0.0, clip=None, group=None,
+                                  generator=None):
+    """train_step_sharded on per-query candidate lists (MGCN.forward_loss_candidates) in place of the
+    rank's whole entity shard: everything up to and including the ConvE trunk is train_step_sharded's (same refusals, same
+    dropout rules, same collectives), then rank r scores only the list positions whose id lies in its rows [n0, n1). No
+    [B, N_local] block, mask or GEMM over the shard exists; the scoring stage costs B K dim on the ranks together.
+    cand [B, K] int64 global ids: EVERY RANK PASSES THE SAME BLOCK (the caller's contract; harness.draw_candidates gives it
+    without an exchange). `labels` [B, K] uint8 / bool: the global labels of draw_candidates(labels=True), or any block that is
+    right at the positions this rank owns; None: looked up on the device for the rank's rows (_native.cand_labels with
+    ent_row0 = n0). `index` = DataLoader.train_index() on the device (only read without `labels`).
+    The mean runs over all B K positions on every rank (hot / cold smoothed with the GLOBAL entity count): the ranks' losses
+    add up (one all-reduce of the scalar), d x is a partial sum reduced once inside the backward, d ent and d bias are the
+    rank's rows and complete; the flat bucket, clipping and optimizer calls are train_step_sharded's. With one rank the step
+    computes what forward_loss_candidates + backward + clip_grad_norm_ + step compute, bit for bit (at any dropout with
+    params.dropout = 'counter'). A rank without entity rows scores nothing and joins every collective.
+    Returns the global loss (0-dim tensor, detached)."""
+    what = 'train_step_sharded_candidates'
+    if _native.is_ee16(model.edge_embeddings):      # (before the list is looked at: the refusal _sharded_trunk repeats)
+        raise _native.NativeError('%s: this model holds its per-edge tables in bf16 (params.edge_table_dtype), '
+                                  'which is inference-only' % what)
+    cand = model._candidate_block(cand, src.numel())
+    if labels is not None and (labels.dtype not in (torch.uint8, torch.bool) or tuple(labels.shape) != tuple(cand.shape)):
+        raise _native.NativeError('%s: labels must be uint8 / bool %s' % (what, tuple(cand.shape)))
+    if labels is None and index is None:
+        raise _native.NativeError('%s: give index or labels' % what)
+    ex, ent, xt = _sharded_trunk(model, graph, src, rel, optimizer, group, generator, what)
+    n0, n1, W = ex.n0, ex.n1, ex.world
+    if n1 == n0:        # a rank without entity rows scores nothing, but takes part in the backward's collectives
+        loss = (xt * 0.0).sum()
+    else:
+        bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]
+        xt = xt if xt.stride(-1) == 1 else xt.contiguous()
+        if labels is None:
+            labels = _native.cand_labels(index.query_keys(src, rel), index.keys, index.ptr, index.tails, cand, n1 - n0, ent_row0=n0)
+        hot, cold = _native.smoothed_targets(lbl_smooth, ex.total)
+        loss = _CandBCEShardFn.apply(xt, ent, bias, cand, labels, hot, cold, n0)
+    return _sharded_finish(model, ex, loss, optimizer, clip, group)
+
+
+def train_epoch_sharded_candidates(model, queries, index, graph, optimizer, params, batch_size, num_neg, draw_seed, first_step=0,
+                                   generator=None, group=None):
+    """One epoch of train_step_sharded_candidates on counter-drawn lists, as harness.train_sampled_negatives(draw_seed=...): the
+    shuffle of train_epoch_sharded (`generator` seeded identically on every rank, or a seed the group agrees on), the key check
+    once, and per step i the lists and global labels of harness.draw_candidates(q, index, N, num_neg, draw_seed, first_step + i,
+    labels=True), drawn on every rank with no exchange. Every rank passes the same draw_seed and first_step (the steps done in
+    earlier epochs; a checkpoint stores the two). Clips at params.clip_grad, smooths with params.lbl_smooth. Returns the mean of
+    the steps' global losses."""
+    from .harness import check_query_keys, draw_candidates
+    from .utils import RunningAverage
+    world, _ = _world_rank(group)
+    dev = model.entity_embedding.device
+    if generator is None and world > 1:
+        generator = torch.Generator()
+        generator.manual_seed(_agreed_seed(group, dev))
+    model.train()
+    loss_avg = RunningAverage()
+    queries = queries.to(dev)
+    order = torch.randperm(queries.size(0), generator=generator).to(dev)
+    n_ent = model.entity_embedding.size(0)
+    check_query_keys(queries, index)      # every query has a key: checked once, not per step
+    for k, i in enumerate(range(0, queries.size(0), batch_size)):
+        q = queries.index_select(0, order[i:i + batch_size])
+        cand, labels = draw_candidates(q, index, n_ent, num_neg, draw_seed, int(first_step) + k, labels=True)
+        loss = train_step_sharded_candidates(model, graph, q[:, 0], q[:, 1], cand, index, optimizer, labels=labels,
+                                             lbl_smooth=params.lbl_smooth, clip=params.clip_grad, group=group)
         loss_avg.update(loss.item())
     return loss_avg()

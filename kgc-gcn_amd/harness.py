@@ -106,29 +106,69 @@ def sample_candidates(q, index, num_entities, num_neg, generator=None, check=Tru
     return cand
 
 
-def train_sampled_negatives(model, queries, index, graph, optimizer, params, batch_size, num_neg, generator=None):
+def draw_candidates(q, index, num_entities, num_neg, seed, step, labels=False):
+    """sample_candidates without a generator: the lists [B, 1 + num_neg] int64 of the queries q [B, >= 2] on the GPU
+    are a pure function of (seed, step, batch row, list position) and of `index`, drawn by one HIP launch
+    (_native.cand_draw under the key of (seed, step, CAND_DRAW_SITE)): every rank of a sharded step that passes the same q, seed
+    and step holds the same block without an exchange, and a run resumes its stream from (seed, step count). Column 0 is one
+    known tail of the query, or -1 for a query without one (a dead position: it contributes nothing and counts in the mean's
+    divisor; no host read checks it); the other columns are uniform ids in [0, num_entities). labels=True: returns
+    (cand, label [B, 1 + num_neg] uint8), the labels _native.cand_labels gives the drawn list against the whole table, from the
+    same launch: what forward_loss_candidates(labels=...) and dist.train_step_sharded_candidates(labels=...) take."""
+    from . import _native
+    cand, label = _native.cand_draw(index.query_keys(q[:, 0], q[:, 1]).contiguous(), index.keys, index.ptr, index.tails, int(num_entities),
+                                    1 + int(num_neg), _native.dropout_key(seed, step, _native.CAND_DRAW_SITE), labels=labels)
+    return (cand, label) if labels else cand
+
+
+def check_query_keys(queries, index):
+    """ValueError unless every query [Q, >= 2] (src, rel) has a key in `index`: the once-per-epoch check of the sampled-negative
+    loops on drawn lists (two reads back from the device; sample_candidates' own test, without its draw)."""
+    if queries.size(0) == 0:
+        return
+    keys = index.query_keys(queries[:, 0], queries[:, 1])
+    at = torch.searchsorted(index.keys, keys)
+    nk = index.keys.numel()
+    if nk == 0 or bool((at >= nk).any()) or not torch.equal(index.keys[at.clamp(max=nk - 1)], keys):
+        raise ValueError('check_query_keys: a query has no known tail in the index')
+
+
+def train_sampled_negatives(model, queries, index, graph, optimizer, params, batch_size, num_neg, generator=None, draw_seed=None,
+                            first_step=0):
     """One epoch like train_device_labels' eager loop, on sampled negatives: per step the candidate lists of
     sample_candidates (one known tail + num_neg uniform ids per query) and MGCN.forward_loss_candidates over them, so that no
     step touches a [B, N] block. `generator`: a CPU generator (or None: the default one) shuffles as train_device_labels does and
     seeds a generator on params.device that draws the epoch's lists; a generator that lives on params.device draws the lists
-    itself and the shuffle takes the default CPU generator. Same clipping / optimizer calls as main.py:56-70."""
+    itself and the shuffle takes the default CPU generator. Same clipping / optimizer calls as main.py:56-70.
+    draw_seed (None: everything above, unchanged): step i of the epoch takes the lists AND their labels of
+    draw_candidates(..., draw_seed, first_step + i, labels=True) instead; `generator` then only shuffles, no generator is made on
+    the device, and the lists do not depend on any RNG state. A caller that trains several epochs passes the steps done so far as
+    first_step (a checkpoint stores draw_seed and that count)."""
     model.train()
     loss_avg = RunningAverage()
     dev = torch.device(params.device)
     queries = queries.to(dev)
     on_cpu = generator is None or generator.device.type == 'cpu'
     order = torch.randperm(queries.size(0), generator=generator if on_cpu else None).to(dev)
-    if on_cpu and dev.type != 'cpu':
+    if draw_seed is None and on_cpu and dev.type != 'cpu':
         seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator))
         generator = torch.Generator(device=dev)
         generator.manual_seed(seed)
     n_ent = model.entity_embedding.size(0)
-    sample_candidates(queries, index, n_ent, 0, generator=generator)      # every query has a key: checked once, not per step
-    for i in range(0, queries.size(0), batch_size):
+    if draw_seed is None:
+        sample_candidates(queries, index, n_ent, 0, generator=generator)      # every query has a key: checked once, not per step
+    else:
+        check_query_keys(queries, index)
+    for k, i in enumerate(range(0, queries.size(0), batch_size)):
         q = queries.index_select(0, order[i:i + batch_size])
-        cand = sample_candidates(q, index, n_ent, num_neg, generator=generator, check=False)
-        optimizer.zero_grad()
-        loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, index=index, lbl_smooth=params.lbl_smooth)
+        if draw_seed is None:
+            cand = sample_candidates(q, index, n_ent, num_neg, generator=generator, check=False)
+            optimizer.zero_grad()
+            loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, index=index, lbl_smooth=params.lbl_smooth)
+        else:
+            cand, labels = draw_candidates(q, index, n_ent, num_neg, draw_seed, int(first_step) + k, labels=True)
+            optimizer.zero_grad()
+            loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, labels=labels, lbl_smooth=params.lbl_smooth)
         loss.backward()
         if hasattr(optimizer, 'clip_and_step'):          # optim.ClipAdam: norm, clipping and update on the HIP kernels
             optimizer.clip_and_step(params.clip_grad)
