@@ -941,6 +941,71 @@ int mgcn_cand_draw_host(int64_t batch, int64_t n_cand, int64_t num_entities, con
                         const int64_t *keys_host, const int64_t *ptr_host, const int32_t *tails_host, int64_t n_tails, uint64_t key,
                         uint64_t row0, int64_t *cand_host, int64_t ldc, uint8_t *label_host, int64_t ldl);
 
+/* ---------------------------------------------------------------------------------------------
+ * (16) Softmax cross-entropy over per-query candidate lists (csrc/dense.hip) — additive, MGCN_ABI_VERSION stays 4.
+ * The listwise loss (sampled softmax) next to the BCE of (14): the candidates of a query compete, the smoothing is over the list
+ * and not over the table. The forward is three kinds of launch, logits -> merge -> finish; the backward is (14)'s
+ * mgcn_cand_bce_bwd_x / mgcn_cand_bce_bwd_ent on the g this block leaves, unchanged. Nothing has a [B, N] operand or a workspace
+ * of size N, there are no float atomics, every sum has a fixed order: the same inputs give the same bits. No host read.
+ * Liveness is that of (13) / (14): with id = cand[b * ldc + j] and d = uint64(id) - uint64(ent_row0), position (b, j) is LIVE iff
+ * d < n_local, its shard row is o = d; the one unsigned comparison is made before any address of ent or bias is formed, and a
+ * dead position's label is not read. -1, another shard's id, +-2^62 are DEAD.
+ *
+ * The loss. z[b, j] = ent[o,:] . x[b,:] + bias[o] for a live position. Per row b, over the live positions OF ALL SHARDS:
+ *   M = max z,  S = sum exp(z - M),  n_live = their number,  n_pos = the number of them with label != 0.
+ *   q[b, j] = (1 - eps) label[b, j] / n_pos + eps / n_live   (eps = lbl_smooth: several known tails of one list share the mass,
+ *             duplicates are separate positions, the smoothing mass is spread over the LIST)
+ *   lp = (z - M) - log S,  p = exp(lp),  g[b, j] = (p - q) inv_batch,  the position's term is -(q lp);
+ *   loss = inv_batch * the sum of all terms (inv_batch = 1 / B for the mean over queries).
+ * A dead position has g = 0 and no term. A row with n_pos == 0 (its column 0 is the -1 of mgcn_cand_draw, or nothing of it is
+ * live anywhere) has g = 0 everywhere and no term; it still counts in the divisor B: the convention of (14).
+ * The loss is a sum of per-position terms: with the GLOBAL statistics of a row in every shard's finish, the shards' losses add up
+ * to the loss, the shards' g blocks are disjoint, d ent / d bias are local and complete, d x is a sum of partial sums.
+ *
+ * A STATISTIC is a record of four 32-bit words: m (f32), s (f32), n_live (int32), n_pos (int32); arrays of them are passed as
+ * float pointers, record i at words 4 i .. 4 i + 3. The counts are integers, exact at every list length the entry points take.
+ * The empty statistic is (-inf, 0, 0, 0).
+ *
+ * mgcn_cand_ce_partials(batch, n_cand) = batch * ceil(n_cand / 64): the number of units (query, chunk of 64 list positions), the
+ *   records of stat_dev of mgcn_cand_ce_logits and the length of loss_partial of mgcn_cand_ce_finish.
+ * mgcn_cand_ce_logits: one launch with the geometry of (13) (a workgroup of four waves per unit, grid-stride, a wave's tile 16
+ *   gathered rows, each row fetched once). z is the exact-f32 MFMA's k-ordered chain of (13) plus bias[o] -- ALWAYS that family,
+ *   never the six-product split: for a live position, z has the bits of the logit mgcn_cand_bce_fwd feeds its sigmoid
+ *   (16-byte aligned operands with dim % 4 == 0: vector loads; anything else element-wise guarded loads, the same order).
+ *   z[b * ldz + j] is written for every j < n_cand: the logit, or -inf at a dead position. Record b * chunks + ch of stat_dev is
+ *   the unit's statistic: m = the maximum of its live z (-inf without one), s = the sum of exp(z - m) over its live positions
+ *   (lanes: xor tree; then the four waves in wave order), the two counts. It is a function of the unit's own (query, chunk) and
+ *   of nothing else in the launch.
+ * mgcn_cand_ce_merge: out record r (r < batch) = the fold of the `parts` records in[r * row_stride + p * part_stride], p ascending
+ *   (strides in records): M = max m_p; S = 0, then S = S + s_p * exp(m_p - M) for p = 0 .. parts - 1, skipping parts with
+ *   m_p = -inf (a part with m_p == M takes the factor 1); the counts add (the caller's parts partition one list, so the sums
+ *   stay at or below n_cand). parts == 1 copies the record: the identity on bits. A row without a live part gives
+ *   (-inf, 0, 0, 0). Used twice: chunks -> row (parts = chunks, row_stride = chunks, part_stride = 1 on the records of
+ *   mgcn_cand_ce_logits) and ranks -> global (the all-gathered [W, batch] blocks: parts = W, row_stride = 1,
+ *   part_stride = batch). One thread per row. in and out must not be the same block.
+ * mgcn_cand_ce_finish: element-wise over [batch, n_cand], a wave per unit: from z (read only where the position is live: liveness
+ *   is recomputed from cand, never inferred from z), label, the row's statistic stat_dev[b] (batch records), lbl_smooth and
+ *   inv_batch it writes g [batch, n_cand] COMPLETELY (0 at dead positions and in rows with n_pos == 0) and
+ *   loss_partial[b * chunks + ch] = the sum of the unit's terms -(q lp), in the order mgcn_cand_bce_fwd adds its partials (within
+ *   each sixteen positions the xor tree, then the four sixteens in order): a function of the unit's positions and of its row's
+ *   statistic alone. The loss is inv_batch times the sum of the partials.
+ * All checks precede the first launch; a refusal writes nothing. MGCN_EINVAL: a null pointer, a negative size, dim < 1,
+ * ent_row0 < 0, batch / n_cand / n_local / parts at or above 2^31 - 64, ldc / ldl / ldz / ldg < n_cand, ldx / lde < dim,
+ * lbl_smooth outside [0, 1]; merge: parts < 1, a stride < 1 or at or above 2^40, strides under which records of different (row,
+ * part) coincide, in == out. batch == 0, n_cand == 0 or n_local == 0 (merge: batch == 0) return MGCN_OK without a launch and
+ * write nothing: a rank without entity rows holds z = -inf, the empty statistic and g = 0 by the caller's fill.
+ * Domain: finite logits. NOT MEASURED: the kernels' own times (DESIGN §4.13 has the stage's time around device events).
+ */
+int64_t mgcn_cand_ce_partials(int32_t batch, int64_t n_cand);
+int mgcn_cand_ce_logits(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *x_dev,
+                        int64_t ldx, const float *ent_dev, int64_t lde, const float *bias_dev, const int64_t *cand_dev, int64_t ldc,
+                        const uint8_t *label_dev, int64_t ldl, float *z_dev, int64_t ldz, float *stat_dev, void *stream);
+int mgcn_cand_ce_merge(int32_t batch, int64_t parts, const float *stat_in_dev, int64_t row_stride, int64_t part_stride,
+                       float *stat_out_dev, void *stream);
+int mgcn_cand_ce_finish(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, const float *z_dev, int64_t ldz,
+                        const int64_t *cand_dev, int64_t ldc, const uint8_t *label_dev, int64_t ldl, const float *stat_dev,
+                        float lbl_smooth, float inv_batch, float *g_dev, int64_t ldg, float *loss_partial_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

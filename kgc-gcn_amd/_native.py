@@ -92,6 +92,12 @@ _SIGNATURES = {
     'mgcn_cand_bce_bwd_x': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr]),
     'mgcn_cand_bce_bwd_ent': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64,
                                              _ptr, _ptr]),
+    'mgcn_cand_ce_partials': (_i64, [_i32, _i64]),
+    'mgcn_cand_ce_logits': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64,
+                                           _ptr, _ptr]),
+    'mgcn_cand_ce_merge': (ctypes.c_int, [_i32, _i64, _ptr, _i64, _i64, _ptr, _ptr]),
+    'mgcn_cand_ce_finish': (ctypes.c_int, [_i32, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _f32, _f32, _ptr, _i64,
+                                           _ptr, _ptr]),
     'mgcn_conve_packed_bytes': (ctypes.c_size_t, [_i32] * 5),
     'mgcn_conve_pack': (ctypes.c_int, [_i32] * 5 + [_ptr, _ptr, _ptr, _i64, _ptr] + ([_ptr] * 4 + [_f32]) * 3 +
                         [_ptr, ctypes.c_size_t, _ptr]),
@@ -1132,6 +1138,88 @@ def cand_bce_bwd_ent(g, cand, x, perm, n_live, n_local, ent_row0=0, d_ent=None, 
                                            _dev(d_ent, torch.float32, 'd_ent', True), _ld(d_ent) if d_ent is not None else 0,
                                            _dev(d_bias, torch.float32, 'd_bias', True), _stream(g)), 'mgcn_cand_bce_bwd_ent')
     return d_ent, d_bias
+
+
+# ------------------------------------------------------------------------------------------------
+# (16) Softmax cross-entropy over per-query candidate lists. A statistic is a row of four 32-bit words held in a float32 tensor
+# [..., 4]: m, s as f32, n_live, n_pos as int32 (cand_ce_stat_fields reads them).
+def cand_ce_empty_stat(rows, device):
+    """[rows, 4]: the statistic (-inf, 0, 0, 0) of a row without a live position (a rank without entity rows passes it on)."""
+    stat = torch.zeros((int(rows), 4), dtype=torch.float32, device=device)
+    stat[:, 0] = float('-inf')
+    return stat
+
+
+def cand_ce_stat_fields(stat):
+    """(m, s, n_live, n_pos) of a statistics tensor [..., 4]: two float32 and two int32 views."""
+    words = stat.view(torch.int32)
+    return stat[..., 0], stat[..., 1], words[..., 2], words[..., 3]
+
+
+def cand_ce_logits(x, ent, bias, cand, label, ent_row0=0):
+    """(16) One launch: (z [B, K] f32, stat [B, ceil(K / 64), 4]): the logits x[b] . ent[o] + bias[o] of the lists cand [B, K]
+    int64 (-inf at positions whose id is outside [ent_row0, ent_row0 + n_local)) and per (query, 64 list positions) the
+    statistic (max, sum of exp(z - max), live positions, live positions with label set). See mgcn_cand_ce_logits."""
+    B, n, O = _score_args(x, ent, bias)
+    K = _cand_block(cand, B, 'cand_ce_logits')
+    _same_device(x, ent, bias, cand, label)
+    lp, ldl = _cand_rows(label, B, K, torch.uint8, 'cand_ce_logits', 'label')
+    chunks = int(lib().mgcn_cand_ce_partials(B, K)) // B if B and K else 0
+    if not (B and K and n):
+        return (torch.full((B, K), float('-inf'), dtype=torch.float32, device=x.device),
+                cand_ce_empty_stat(B * chunks, x.device).view(B, chunks, 4))
+    z = torch.empty((B, K), dtype=torch.float32, device=x.device)
+    stat = torch.empty((B, chunks, 4), dtype=torch.float32, device=x.device)
+    _check(lib().mgcn_cand_ce_logits(B, K, n, int(ent_row0), O, _dev(x, torch.float32, 'x'), _ld(x), _dev(ent, torch.float32, 'ent'),
+                                     _ld(ent), _dev(bias, torch.float32, 'bias'), _dev(cand, torch.int64, 'cand'), _ld(cand), lp, ldl,
+                                     _dev(z, torch.float32, 'z'), K, _dev(stat, torch.float32, 'stat'), _stream(x)),
+           'mgcn_cand_ce_logits')
+    return z, stat
+
+
+def cand_ce_merge(stat, part_dim=1):
+    """(16) [B, 4]: the statistics of `stat` folded over its parts in part order (see mgcn_cand_ce_merge). stat is contiguous
+    float32 [B, P, 4] (part_dim = 1: the chunks of cand_ce_logits) or [P, B, 4] (part_dim = 0: the ranks' blocks of an
+    all-gather). One part gives the same bits back."""
+    if stat.dim() != 3 or stat.size(2) != 4 or part_dim not in (0, 1) or not stat.is_contiguous():
+        raise NativeError('cand_ce_merge: stat %s must be contiguous [B, P, 4] (part_dim 1) or [P, B, 4] (part_dim 0)' % (tuple(stat.shape),))
+    B, P = stat.size(1 - part_dim), stat.size(part_dim)
+    if P < 1:
+        if B == 0:
+            return cand_ce_empty_stat(0, stat.device)
+        raise NativeError('cand_ce_merge: no part to merge')
+    out = torch.empty((B, 4), dtype=torch.float32, device=stat.device)
+    if B:
+        row_stride, part_stride = (P, 1) if part_dim == 1 else (1, B)
+        _check(lib().mgcn_cand_ce_merge(B, P, _dev(stat, torch.float32, 'stat'), row_stride, part_stride,
+                                        _dev(out, torch.float32, 'out'), _stream(stat)), 'mgcn_cand_ce_merge')
+    return out
+
+
+def cand_ce_finish(z, cand, label, stat, lbl_smooth, n_local, ent_row0=0, inv_batch=None):
+    """(16) One launch: (loss [] f32, g [B, K] f32 = d loss / d logit, loss_partial [B ceil(K / 64)]) of the softmax
+    cross-entropy over the lists, from the logits z of cand_ce_logits and the rows' statistics stat [B, 4] (of the whole row:
+    merged over chunks and, sharded, over ranks). inv_batch: the weight of a query, default 1 / B. Positions whose id is outside
+    [ent_row0, ent_row0 + n_local) and rows without a positive get g = 0 and add nothing. See mgcn_cand_ce_finish."""
+    B = z.size(0)
+    K = _cand_block(cand, B, 'cand_ce_finish')
+    _same_device(z, cand, label, stat)
+    if tuple(stat.shape) != (B, 4) or not stat.is_contiguous():
+        raise NativeError('cand_ce_finish: stat %s must be contiguous (%d, 4)' % (tuple(stat.shape), B))
+    zp, ldz = _cand_rows(z, B, K, torch.float32, 'cand_ce_finish', 'z')
+    lp, ldl = _cand_rows(label, B, K, torch.uint8, 'cand_ce_finish', 'label')
+    inv = 1.0 / float(B) if inv_batch is None else float(inv_batch)
+    n_parts = int(lib().mgcn_cand_ce_partials(B, K))
+    if not (B and K and int(n_local)):
+        g = torch.zeros((B, K), dtype=torch.float32, device=z.device)
+        parts = torch.zeros(n_parts, dtype=torch.float32, device=z.device)
+        return parts.sum() * inv, g, parts
+    g = torch.empty((B, K), dtype=torch.float32, device=z.device)
+    parts = torch.empty(n_parts, dtype=torch.float32, device=z.device)
+    _check(lib().mgcn_cand_ce_finish(B, K, int(n_local), int(ent_row0), zp, ldz, _dev(cand, torch.int64, 'cand'), _ld(cand), lp, ldl,
+                                     _dev(stat, torch.float32, 'stat'), float(lbl_smooth), inv, _dev(g, torch.float32, 'g'), K,
+                                     _dev(parts, torch.float32, 'loss_partial'), _stream(z)), 'mgcn_cand_ce_finish')
+    return parts.sum() * inv, g, parts
 
 
 # ------------------------------------------------------------------------------------------------

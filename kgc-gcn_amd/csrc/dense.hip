@@ -8,7 +8,8 @@
 //   EPI_BCE       training: BCE(sigmoid(score), target) partial sums + d loss / d logit [M, ncols] (main.py:61-66, N3)
 // and, for aligned scoring shapes with K <= 352, score_split_kernel<SIGMOID / TARGET / RANK>: the same three results on
 // the bf16 MFMA from exactly split operands (below); and cand_split_kernel / cand_tile_kernel: score[b, cand[b, j]] for per-query
-// candidate lists, the same two arithmetics over gathered rows (include/mgcn_hip.h (13)).
+// candidate lists, the same two arithmetics over gathered rows (include/mgcn_hip.h (13)); cand_bce_kernel and
+// cand_ce_logits_kernel / cand_ce_merge_kernel / cand_ce_finish_kernel: the two losses of training on such lists ((14), (16)).
 //
 // Geometry. The streamed operand (aggregates [N,3D], or the entity table [N,O]) is always the MFMA A
 // operand and goes global -> registers directly: lane (r = l&15, q = l>>4) loads the 16 bytes
@@ -956,6 +957,177 @@ __global__ __launch_bounds__(CD_THREADS) void cand_bce_kernel(CandBceArgs a) {
   }
 }
 
+// Softmax cross-entropy over candidate lists (include/mgcn_hip.h (16)). A statistic is four 32-bit words: m, s (f32),
+// n_live, n_pos (int32). cand_ce_logits_kernel is cand_bce_kernel's chain (a kernel of its own: cand_bce_kernel keeps its
+// registers) with another epilogue: z of every list position (-inf where dead) and the unit's statistic. The maximum first
+// (lanes: xor tree; the four waves), then s = sum exp(z - m): lanes by xor tree, the four waves in wave order, so a unit's
+// statistic is a function of its (query, chunk) alone. The counts are ballots: integers.
+struct CandCeArgs {
+  CandArgs c;
+  const uint8_t *label;
+  float *z, *stat;
+  int64_t ldl, ldz;
+};
+
+template <bool FAST>
+__global__ __launch_bounds__(CD_THREADS) void cand_ce_logits_kernel(CandCeArgs a) {
+  __shared__ float wmax[CD_WAVES], wsum[CD_WAVES];
+  __shared__ int wlive[CD_WAVES], wpos[CD_WAVES];
+  const CandArgs &p = a.c;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int nkb = (p.k + KS - 1) / KS;
+  const float ninf = -__builtin_inff();
+  for (int64_t u = blockIdx.x; u < p.units; u += gridDim.x) {
+    const int b = int(u / p.chunks);
+    const int64_t j0 = (u - int64_t(b) * p.chunks) * CD_ROWS + wave * 16;
+    float zl = ninf;
+    bool live = false, pos = false;
+    if (j0 < p.n_cand) {   // wave-uniform: a tile past the list has no position
+      bool ok;
+      const int64_t o = cand_row(p, b, j0 + fr, ok);
+      const float *ap = p.ent + o * p.lde + 4 * fq;
+      const float *xp = p.x + int64_t(b) * p.ldx + 4 * fq;
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      float4 a_cur = load4<FAST>(ap, ok, 4 * fq, p.k);
+      float4 x_cur = load4<FAST>(xp, true, 4 * fq, p.k);
+      for (int kb = 0; kb < nkb; ++kb) {
+        float4 a_next = make_float4(0.f, 0.f, 0.f, 0.f), x_next = a_next;
+        if (kb + 1 < nkb) {
+          a_next = load4<FAST>(ap + (kb + 1) * KS, ok, (kb + 1) * KS + 4 * fq, p.k);
+          x_next = load4<FAST>(xp + (kb + 1) * KS, true, (kb + 1) * KS + 4 * fq, p.k);
+        }
+        const float av[4] = {a_cur.x, a_cur.y, a_cur.z, a_cur.w};
+        const float xv[4] = {x_cur.x, x_cur.y, x_cur.z, x_cur.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], xv[i], acc, 0, 0, 0);
+        a_cur = a_next;
+        x_cur = x_next;
+      }
+      // acc[i] = logit of tile row 4 (l >> 4) + i in every column: lanes l & 15 < 4 finish row 4 (l >> 4) + (l & 15)
+      const int row = 4 * fq + (fr & 3);
+      const int64_t orow = __shfl(o, row);
+      const bool okrow = __shfl(int(ok), row) != 0;
+      const int64_t j = j0 + row;
+      if (fr < 4 && j < p.n_cand) {
+        if (okrow) {
+          const float v = fr == 0 ? acc[0] : fr == 1 ? acc[1] : fr == 2 ? acc[2] : acc[3];
+          zl = v + p.bias[orow];
+          live = true;
+          pos = a.label[int64_t(b) * a.ldl + j] != 0;   // (a dead position's label is never read)
+        }
+        a.z[int64_t(b) * a.ldz + j] = zl;
+      }
+    }
+    float v = zl;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v = fmaxf(v, __shfl_xor(v, s));
+    const int nl = __popcll(__ballot(live)), np = __popcll(__ballot(pos));
+    __syncthreads();   // the previous unit's reader is done with the four arrays
+    if (lane == 0) {
+      wmax[wave] = v;
+      wlive[wave] = nl;
+      wpos[wave] = np;
+    }
+    __syncthreads();
+    const float m = fmaxf(fmaxf(fmaxf(wmax[0], wmax[1]), wmax[2]), wmax[3]);
+    float e = live ? expf(zl - m) : 0.f;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) e += __shfl_xor(e, s);
+    if (lane == 0) wsum[wave] = e;
+    __syncthreads();
+    if (tid == 0) {
+      float *st = a.stat + 4 * u;
+      st[0] = m;
+      st[1] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+      reinterpret_cast<int *>(st)[2] = ((wlive[0] + wlive[1]) + wlive[2]) + wlive[3];
+      reinterpret_cast<int *>(st)[3] = ((wpos[0] + wpos[1]) + wpos[2]) + wpos[3];
+    }
+  }
+}
+
+// One thread per row folds its `parts` statistics in part order: M = max m_p, S = sum s_p exp(m_p - M) from 0 over the parts
+// with m_p > -inf (a part at the maximum takes the factor 1 as a constant, not from expf), the counts add. Part p of row r is
+// the record r * row_stride + p * part_stride: chunks of a row lie side by side (row_stride = chunks, part_stride = 1), the
+// ranks' blocks of an all-gather one after the other (row_stride = 1, part_stride = batch). One part: the record is copied.
+__global__ __launch_bounds__(256) void cand_ce_merge_kernel(const float *__restrict__ in, int64_t row_stride, int64_t part_stride,
+                                                            int64_t parts, float *__restrict__ out, int batch) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= batch) return;
+  const float *src = in + 4 * (int64_t(r) * row_stride);
+  float *dst = out + 4 * int64_t(r);
+  if (parts == 1) {   // the identity on bits
+    for (int i = 0; i < 4; ++i) reinterpret_cast<uint32_t *>(dst)[i] = reinterpret_cast<const uint32_t *>(src)[i];
+    return;
+  }
+  const float ninf = -__builtin_inff();
+  float m = ninf;
+  int nl = 0, np = 0;
+  for (int64_t q = 0; q < parts; ++q) {
+    const float *rec = src + 4 * q * part_stride;
+    m = fmaxf(m, rec[0]);
+    nl += reinterpret_cast<const int *>(rec)[2];
+    np += reinterpret_cast<const int *>(rec)[3];
+  }
+  float s = 0.f;
+  for (int64_t q = 0; q < parts; ++q) {
+    const float *rec = src + 4 * q * part_stride;
+    const float mq = rec[0];
+    if (mq == ninf) continue;
+    s = s + rec[1] * (mq == m ? 1.0f : expf(mq - m));
+  }
+  dst[0] = m;
+  dst[1] = s;
+  reinterpret_cast<int *>(dst)[2] = nl;
+  reinterpret_cast<int *>(dst)[3] = np;
+}
+
+// g and the loss partials from z and the rows' statistics. A wave owns a unit (query, 64 list positions), lane l position l of
+// it; liveness is recomputed from cand. The unit's partial is added in cand_bce_kernel's order: there tile w of the unit sits
+// in wave w, its row 4 q + r in lane 16 q + r, so the xor tree adds q-pairs (32, 16), zeros (8, 4), r-pairs (2, 1), and the
+// waves follow in wave order. Here position 16 w + 4 q + r sits in lane 16 w + 4 q + r: the steps 8, 4, 2, 1, then the four
+// sixteens in order.
+struct CandCeFinishArgs {
+  const float *z, *stat;
+  const int64_t *cand;
+  const uint8_t *label;
+  float *g, *loss_partial;
+  int64_t ldz, ldc, ldl, ldg, n_cand, n_local, row0, units;
+  int32_t chunks;
+  float eps, inv_batch;
+};
+
+__global__ __launch_bounds__(CD_THREADS) void cand_ce_finish_kernel(CandCeFinishArgs a) {
+  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  for (int64_t u = int64_t(blockIdx.x) * CD_WAVES + wave; u < a.units; u += int64_t(gridDim.x) * CD_WAVES) {
+    const int64_t b = u / a.chunks;
+    const int64_t j = (u - b * a.chunks) * CD_ROWS + lane;
+    const float *st = a.stat + 4 * b;
+    const float m = st[0], s = st[1];
+    const int nl = reinterpret_cast<const int *>(st)[2], np = reinterpret_cast<const int *>(st)[3];
+    float term = 0.f;
+    if (j < a.n_cand) {
+      float gz = 0.f;
+      const bool live = uint64_t(a.cand[b * a.ldc + j]) - uint64_t(a.row0) < uint64_t(a.n_local);
+      if (live && np > 0) {
+        const float lp = (a.z[b * a.ldz + j] - m) - logf(s);
+        const float pz = expf(lp);
+        float q = a.eps / float(nl);
+        if (a.label[b * a.ldl + j] != 0) q = (1.0f - a.eps) / float(np) + q;
+        gz = (pz - q) * a.inv_batch;
+        term = -(q * lp);
+      }
+      a.g[b * a.ldg + j] = gz;
+    }
+    float v = term;
+#pragma unroll
+    for (int sft = 8; sft >= 1; sft >>= 1) v += __shfl_xor(v, sft);
+    const float w0 = __shfl(v, 0), w1 = __shfl(v, 16), w2 = __shfl(v, 32), w3 = __shfl(v, 48);
+    if (lane == 0) a.loss_partial[u] = ((w0 + w1) + w2) + w3;
+  }
+}
+
 // all_rel = rels_embs @ rels_weight (model.py:107 without the dropped last row): [T, K] x [K, O], T tiny, so
 // the kernel is pure latency. Block = (one output row, 64 columns); its 4 waves split K and keep UNR
 // independent loads in flight per lane; partial sums meet in LDS and are added in wave order.
@@ -1392,5 +1564,84 @@ extern "C" int mgcn_cand_bce_fwd(int32_t batch, int64_t n_cand, int64_t n_local,
     hipLaunchKernelGGL(cand_bce_kernel<false>, dim3(gx), dim3(CD_THREADS), 0, s, a);
   }
   MGCN_CHECK_LAUNCH("cand_bce_kernel");
+  return MGCN_OK;
+}
+
+// (16) Softmax cross-entropy over per-query candidate lists: logits and unit statistics, the merge of statistics, g and loss.
+extern "C" int64_t mgcn_cand_ce_partials(int32_t batch, int64_t n_cand) { return mgcn_cand_bce_partials(batch, n_cand); }
+
+extern "C" int mgcn_cand_ce_logits(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *x_dev,
+                                   int64_t ldx, const float *ent_dev, int64_t lde, const float *bias_dev, const int64_t *cand_dev,
+                                   int64_t ldc, const uint8_t *label_dev, int64_t ldl, float *z_dev, int64_t ldz, float *stat_dev,
+                                   void *stream) {
+  if (int rc = check_common("cand_ce_logits", n_local, dim, batch)) return rc;
+  MGCN_REQUIRE(n_cand >= 0 && ent_row0 >= 0, "cand_ce_logits: bad sizes");
+  MGCN_REQUIRE(n_cand < (int64_t(1) << 31) - 64, "cand_ce_logits: sizes exceed int32");
+  MGCN_REQUIRE(x_dev && ent_dev && bias_dev && cand_dev && label_dev && z_dev && stat_dev, "cand_ce_logits: null pointer");
+  MGCN_REQUIRE(ldx >= dim && lde >= dim && ldc >= n_cand && ldl >= n_cand && ldz >= n_cand,
+               "cand_ce_logits: leading dimension too small");
+  if (batch == 0 || n_cand == 0 || n_local == 0) return MGCN_OK;
+  TileArgs t = {};
+  t.a = ent_dev; t.lda = lde;
+  t.b = x_dev; t.ldb = ldx;
+  set_vec_flags(&t);
+  const bool fast = t.a_vec && t.b_vec && dim % 4 == 0;
+  CandCeArgs a = {};
+  CandArgs &p = a.c;
+  p.x = x_dev; p.ent = ent_dev; p.bias = bias_dev; p.cand = cand_dev;
+  p.ldx = ldx; p.lde = lde; p.ldc = ldc;
+  p.n_cand = n_cand; p.n_local = n_local; p.row0 = ent_row0; p.k = dim;
+  p.chunks = int32_t((n_cand + CD_ROWS - 1) / CD_ROWS);
+  p.units = int64_t(batch) * p.chunks;
+  a.label = label_dev; a.ldl = ldl; a.z = z_dev; a.ldz = ldz; a.stat = stat_dev;
+  const unsigned gx = unsigned(p.units < (int64_t(1) << 22) ? p.units : (int64_t(1) << 22));   // beyond: grid-stride
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (fast) {
+    hipLaunchKernelGGL(cand_ce_logits_kernel<true>, dim3(gx), dim3(CD_THREADS), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(cand_ce_logits_kernel<false>, dim3(gx), dim3(CD_THREADS), 0, s, a);
+  }
+  MGCN_CHECK_LAUNCH("cand_ce_logits_kernel");
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_cand_ce_merge(int32_t batch, int64_t parts, const float *stat_in_dev, int64_t row_stride, int64_t part_stride,
+                                  float *stat_out_dev, void *stream) {
+  MGCN_REQUIRE(batch >= 0 && parts >= 1 && row_stride >= 1 && part_stride >= 1, "cand_ce_merge: bad sizes");
+  MGCN_REQUIRE(batch < (int64_t(1) << 31) - 64 && parts < (int64_t(1) << 31) - 64, "cand_ce_merge: sizes exceed int32");
+  MGCN_REQUIRE(row_stride < (int64_t(1) << 40) && part_stride < (int64_t(1) << 40), "cand_ce_merge: stride too large");
+  MGCN_REQUIRE((row_stride >= parts && part_stride == 1) || (part_stride >= batch && row_stride == 1) || batch <= 1 || parts == 1,
+               "cand_ce_merge: records overlap (row_stride >= parts with part_stride 1, or part_stride >= batch with row_stride 1)");
+  MGCN_REQUIRE(stat_in_dev && stat_out_dev, "cand_ce_merge: null pointer");
+  MGCN_REQUIRE(stat_in_dev != stat_out_dev, "cand_ce_merge: in place");
+  if (batch == 0) return MGCN_OK;
+  hipLaunchKernelGGL(cand_ce_merge_kernel, dim3((unsigned(batch) + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     stat_in_dev, row_stride, part_stride, parts, stat_out_dev, int(batch));
+  MGCN_CHECK_LAUNCH("cand_ce_merge_kernel");
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_cand_ce_finish(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, const float *z_dev, int64_t ldz,
+                                   const int64_t *cand_dev, int64_t ldc, const uint8_t *label_dev, int64_t ldl,
+                                   const float *stat_dev, float lbl_smooth, float inv_batch, float *g_dev, int64_t ldg,
+                                   float *loss_partial_dev, void *stream) {
+  MGCN_REQUIRE(batch >= 0 && n_cand >= 0 && n_local >= 0 && ent_row0 >= 0, "cand_ce_finish: bad sizes");
+  MGCN_REQUIRE(batch < (int64_t(1) << 31) - 64 && n_cand < (int64_t(1) << 31) - 64 && n_local < (int64_t(1) << 31) - 64,
+               "cand_ce_finish: sizes exceed int32");
+  MGCN_REQUIRE(lbl_smooth >= 0.0f && lbl_smooth <= 1.0f, "cand_ce_finish: lbl_smooth outside [0, 1]");
+  MGCN_REQUIRE(z_dev && cand_dev && label_dev && stat_dev && g_dev && loss_partial_dev, "cand_ce_finish: null pointer");
+  MGCN_REQUIRE(ldz >= n_cand && ldc >= n_cand && ldl >= n_cand && ldg >= n_cand, "cand_ce_finish: leading dimension too small");
+  if (batch == 0 || n_cand == 0 || n_local == 0) return MGCN_OK;
+  CandCeFinishArgs a = {};
+  a.z = z_dev; a.stat = stat_dev; a.cand = cand_dev; a.label = label_dev; a.g = g_dev; a.loss_partial = loss_partial_dev;
+  a.ldz = ldz; a.ldc = ldc; a.ldl = ldl; a.ldg = ldg;
+  a.n_cand = n_cand; a.n_local = n_local; a.row0 = ent_row0;
+  a.chunks = int32_t((n_cand + CD_ROWS - 1) / CD_ROWS);
+  a.units = int64_t(batch) * a.chunks;
+  a.eps = lbl_smooth; a.inv_batch = inv_batch;
+  const int64_t groups = (a.units + CD_WAVES - 1) / CD_WAVES;
+  const unsigned gx = unsigned(groups < (int64_t(1) << 22) ? groups : (int64_t(1) << 22));   // beyond: grid-stride
+  hipLaunchKernelGGL(cand_ce_finish_kernel, dim3(gx), dim3(CD_THREADS), 0, static_cast<hipStream_t>(stream), a);
+  MGCN_CHECK_LAUNCH("cand_ce_finish_kernel");
   return MGCN_OK;
 }

@@ -664,6 +664,36 @@ class _CandBCEShardFn(torch.autograd.Function):
         return (gx, d_ent, d_bias, None, None, None, None, None)
 
 
+class _CandCEShardFn(torch.autograd.Function):
+    """model._CandCEFn on this rank's entity rows [row0, row0 + ent.size(0)) (include/mgcn_hip.h (16)): the rank's logits and
+    row statistics, ONE all-gather of the [B, 4] statistics, their merge over the ranks in rank order (the same kernel that
+    merged the chunks), and the finish with the global statistics. The rank's loss is the sum of its own positions' terms, so
+    the ranks' losses and d x add up to the one-rank step's; d ent and d bias are the rank's rows, complete. A rank without
+    rows contributes the empty statistic and joins the all-gather. With one rank there is no collective and no second merge:
+    model._CandCEFn's launches."""
+
+    @staticmethod
+    def forward(ctx, x, ent, bias, cand, label, eps, row0, ex):
+        B, n = x.size(0), ent.size(0)
+        if n:
+            z, stat = _native.cand_ce_logits(x, ent, bias, cand, label, ent_row0=row0)
+            stat = _native.cand_ce_merge(stat)
+        else:
+            z = torch.full(tuple(cand.shape), float('-inf'), dtype=torch.float32, device=x.device)
+            stat = _native.cand_ce_empty_stat(B, x.device)
+        if ex.world > 1:
+            stat = _native.cand_ce_merge(_gather(stat, ex.group, ex.world).view(ex.world, B, 4), part_dim=0)
+        loss, g, _ = _native.cand_ce_finish(z, cand, label, stat, eps, n, ent_row0=row0)
+        perm, ctx.n_live = _native.cand_plan(cand, n, ent_row0=row0, count=False)
+        ctx.row0 = int(row0)
+        ctx.save_for_backward(x, ent, cand, g, perm)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        return _CandBCEShardFn.backward(ctx, gl)
+
+
 def _dropout(x, p, generator):
     """F.dropout with the keep-mask drawn from `generator` (model._drawn_dropout: the one both trunk paths use)."""
     from .model import _drawn_dropout
@@ -961,7 +991,7 @@ def train_epoch_sharded(model, queries, index, graph, optimizer, params, batch_s
 
 
 def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer, labels=None, lbl_smooth=0.0, clip=None, group=None,
-                                  generator=None):
+                                  generator=None, loss='bce'):
     """train_step_sharded on per-query candidate lists (MGCN.forward_loss_candidates) in place of the
     rank's whole entity shard: everything up to and including the ConvE trunk is train_step_sharded's (same refusals, same
     dropout rules, same collectives), then rank r scores only the list positions whose id lies in its rows [n0, n1). No
@@ -975,8 +1005,13 @@ def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer
     rank's rows and complete; the flat bucket, clipping and optimizer calls are train_step_sharded's. With one rank the step
     computes what forward_loss_candidates + backward + clip_grad_norm_ + step compute, bit for bit (at any dropout with
     params.dropout = 'counter'). A rank without entity rows scores nothing and joins every collective.
+    loss = 'softmax': the softmax cross-entropy over each list instead (forward_loss_candidates(loss='softmax')):
+    a row's maximum, sum and counts span the ranks, so the step makes one more collective, an all-gather of the [B, 4] row
+    statistics (_CandCEShardFn); lbl_smooth is spread over the list; the ranks' losses add up as above.
     Returns the global loss (0-dim tensor, detached)."""
     what = 'train_step_sharded_candidates'
+    if loss not in ('bce', 'softmax'):
+        raise _native.NativeError("%s: loss must be 'bce' or 'softmax', got %r" % (what, loss))
     if _native.is_ee16(model.edge_embeddings):      # (before the list is looked at: the refusal _sharded_trunk repeats)
         raise _native.NativeError('%s: this model holds its per-edge tables in bf16 (params.edge_table_dtype), '
                                   'which is inference-only' % what)
@@ -987,7 +1022,13 @@ def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer
         raise _native.NativeError('%s: give index or labels' % what)
     ex, ent, xt = _sharded_trunk(model, graph, src, rel, optimizer, group, generator, what)
     n0, n1, W = ex.n0, ex.n1, ex.world
-    if n1 == n0:        # a rank without entity rows scores nothing, but takes part in the backward's collectives
+    if loss == 'softmax':       # (a rank without entity rows passes the empty statistic on: it joins the all-gather)
+        bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]
+        xt = xt if xt.stride(-1) == 1 else xt.contiguous()
+        if labels is None:
+            labels = _native.cand_labels(index.query_keys(src, rel), index.keys, index.ptr, index.tails, cand, n1 - n0, ent_row0=n0)
+        loss = _CandCEShardFn.apply(xt, ent, bias, cand, labels, float(lbl_smooth), n0, ex)
+    elif n1 == n0:      # a rank without entity rows scores nothing, but takes part in the backward's collectives
         loss = (xt * 0.0).sum()
     else:
         bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]
@@ -1000,14 +1041,15 @@ def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer
 
 
 def train_epoch_sharded_candidates(model, queries, index, graph, optimizer, params, batch_size, num_neg, draw_seed, first_step=0,
-                                   generator=None, group=None):
+                                   generator=None, group=None, loss='bce'):
     """One epoch of train_step_sharded_candidates on counter-drawn lists, as harness.train_sampled_negatives(draw_seed=...): the
     shuffle of train_epoch_sharded (`generator` seeded identically on every rank, or a seed the group agrees on), the key check
     once, and per step i the lists and global labels of harness.draw_candidates(q, index, N, num_neg, draw_seed, first_step + i,
     labels=True), drawn on every rank with no exchange. Every rank passes the same draw_seed and first_step (the steps done in
     earlier epochs; a checkpoint stores the two). Clips at params.clip_grad, smooths with params.lbl_smooth. Returns the mean of
-    the steps' global losses."""
+    the steps' global losses. loss: 'bce' or 'softmax', handed to every step."""
     from .harness import check_query_keys, draw_candidates
+    kind = loss             # (`loss` below is a step's result)
     from .utils import RunningAverage
     world, _ = _world_rank(group)
     dev = model.entity_embedding.device
@@ -1024,6 +1066,6 @@ def train_epoch_sharded_candidates(model, queries, index, graph, optimizer, para
         q = queries.index_select(0, order[i:i + batch_size])
         cand, labels = draw_candidates(q, index, n_ent, num_neg, draw_seed, int(first_step) + k, labels=True)
         loss = train_step_sharded_candidates(model, graph, q[:, 0], q[:, 1], cand, index, optimizer, labels=labels,
-                                             lbl_smooth=params.lbl_smooth, clip=params.clip_grad, group=group)
+                                             lbl_smooth=params.lbl_smooth, clip=params.clip_grad, group=group, loss=kind)
         loss_avg.update(loss.item())
     return loss_avg()

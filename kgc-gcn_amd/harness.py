@@ -134,7 +134,7 @@ def check_query_keys(queries, index):
 
 
 def train_sampled_negatives(model, queries, index, graph, optimizer, params, batch_size, num_neg, generator=None, draw_seed=None,
-                            first_step=0):
+                            first_step=0, loss='bce'):
     """One epoch like train_device_labels' eager loop, on sampled negatives: per step the candidate lists of
     sample_candidates (one known tail + num_neg uniform ids per query) and MGCN.forward_loss_candidates over them, so that no
     step touches a [B, N] block. `generator`: a CPU generator (or None: the default one) shuffles as train_device_labels does and
@@ -143,7 +143,9 @@ def train_sampled_negatives(model, queries, index, graph, optimizer, params, bat
     draw_seed (None: everything above, unchanged): step i of the epoch takes the lists AND their labels of
     draw_candidates(..., draw_seed, first_step + i, labels=True) instead; `generator` then only shuffles, no generator is made on
     the device, and the lists do not depend on any RNG state. A caller that trains several epochs passes the steps done so far as
-    first_step (a checkpoint stores draw_seed and that count)."""
+    first_step (a checkpoint stores draw_seed and that count).
+    loss: 'bce' or 'softmax', handed to forward_loss_candidates (the softmax cross-entropy over each list)."""
+    kind = loss             # (`loss` below is a step's result)
     model.train()
     loss_avg = RunningAverage()
     dev = torch.device(params.device)
@@ -164,11 +166,11 @@ def train_sampled_negatives(model, queries, index, graph, optimizer, params, bat
         if draw_seed is None:
             cand = sample_candidates(q, index, n_ent, num_neg, generator=generator, check=False)
             optimizer.zero_grad()
-            loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, index=index, lbl_smooth=params.lbl_smooth)
+            loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, index=index, lbl_smooth=params.lbl_smooth, loss=kind)
         else:
             cand, labels = draw_candidates(q, index, n_ent, num_neg, draw_seed, int(first_step) + k, labels=True)
             optimizer.zero_grad()
-            loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, labels=labels, lbl_smooth=params.lbl_smooth)
+            loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, labels=labels, lbl_smooth=params.lbl_smooth, loss=kind)
         loss.backward()
         if hasattr(optimizer, 'clip_and_step'):          # optim.ClipAdam: norm, clipping and update on the HIP kernels
             optimizer.clip_and_step(params.clip_grad)

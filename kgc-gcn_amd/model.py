@@ -355,6 +355,24 @@ class _CandBCEFn(torch.autograd.Function):
         return (gx, d_ent, d_bias, None, None, None, None)
 
 
+class _CandCEFn(torch.autograd.Function):
+    """softmax cross-entropy over per-query candidate lists (include/mgcn_hip.h (16)): logits and per-chunk statistics, their
+    merge per row, then d loss / d logit [B, K] and the loss partials; the backward is _CandBCEFn's, on that g. `eps` smooths
+    over the list. Nothing of size [B, N] exists; no float atomics."""
+
+    @staticmethod
+    def forward(ctx, x, ent, bias, cand, label, eps):
+        z, stat = _native.cand_ce_logits(x, ent, bias, cand, label)
+        loss, g, _ = _native.cand_ce_finish(z, cand, label, _native.cand_ce_merge(stat), eps, ent.size(0))
+        perm, ctx.n_live = _native.cand_plan(cand, ent.size(0), count=False)
+        ctx.save_for_backward(x, ent, cand, g, perm)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        return _CandBCEFn.backward(ctx, gl)[:6]
+
+
 class MGCNConv(nn.Module):
     """One relational layer (model.py:47-127). Parameter names are the reference's."""
 
@@ -1010,7 +1028,7 @@ class MGCN(nn.Module):
         labels = _native.label_rows(keys, index.keys, index.ptr, index.tails, n_ent, lbl_smooth=lbl_smooth)
         return self.loss_fn(_ScoreFn.apply(x, ent, self.conv2.bias), labels)
 
-    def forward_loss_candidates(self, src, rel, cand, data, index=None, labels=None, lbl_smooth=0.0):
+    def forward_loss_candidates(self, src, rel, cand, data, index=None, labels=None, lbl_smooth=0.0, loss='bce'):
         """forward_loss with a per-query candidate list in place of the entity table (training on sampled negatives): the mean
         BCE of the scores of cand [B, K] int64 (the true tails plus sampled negatives, e.g. harness.sample_candidates) against
         targets that are hot at the known tails and cold elsewhere, smoothed with 1/N as forward_loss smooths. Exactly one of
@@ -1018,8 +1036,13 @@ class MGCN(nn.Module):
         `labels` ([B, K] uint8 / bool). The mean runs over ALL B K list positions (inv_count = 1 / (B K)): an id outside [0, N)
         (-1 padding) contributes zero to the loss and to every gradient but still counts in the divisor. The scoring stage costs
         B K dim, not N: no [B, N] block, mask or GEMM over the table; its backward has a fixed summation order. Everything
-        upstream (encoder, query rows, trunk and their switches) is forward_loss's."""
+        upstream (encoder, query rows, trunk and their switches) is forward_loss's.
+        loss: 'bce' (the above) or 'softmax': the softmax cross-entropy over each query's list (sampled softmax, include/mgcn_hip.h
+        (16)): the target mass (1 - lbl_smooth) is shared by the list's known tails and lbl_smooth is spread over the list's live
+        positions, the mean runs over the B queries; a query whose list names no known tail adds nothing and counts in B."""
         self._refuse_training_ee16('MGCN.forward_loss_candidates')
+        if loss not in ('bce', 'softmax'):
+            raise _native.NativeError("forward_loss_candidates: loss must be 'bce' or 'softmax', got %r" % (loss,))
         if (index is None) == (labels is None):
             raise _native.NativeError('forward_loss_candidates: give exactly one of index / labels')
         cand = self._candidate_block(cand, src.numel())
@@ -1032,6 +1055,8 @@ class MGCN(nn.Module):
             labels = _native.cand_labels(index.query_keys(src, rel), index.keys, index.ptr, index.tails, cand, n_ent)
         elif labels.dtype not in (torch.uint8, torch.bool) or tuple(labels.shape) != tuple(cand.shape):
             raise _native.NativeError('forward_loss_candidates: labels must be uint8 / bool %s' % (tuple(cand.shape),))
+        if loss == 'softmax':
+            return _CandCEFn.apply(x, ent, self.conv2.bias, cand, labels, float(lbl_smooth))
         hot, cold = _native.smoothed_targets(lbl_smooth, n_ent)
         return _CandBCEFn.apply(x, ent, self.conv2.bias, cand, labels, hot, cold)
 
