@@ -408,8 +408,13 @@ int mgcn_bn_tanh_train_bwd(int64_t num_rows, int32_t dim_out, const float *z_dev
 /* (4s) (4t) split into stages around an exchange, for the destination partition's training step: each rank holds num_rows rows of
  * the layer and reduces them in the same fixed 128-row blocks as (4t); between the stages the caller gathers every rank's per-block
  * partials ([ceil(num_rows / 128), O] each) and passes them all, rank after rank, as num_blocks rows; total_rows = the rows of all
- * ranks. The folds add the blocks in the order given, so every rank computes the same statistics; when every rank's first row is a
- * multiple of 128 (always with one rank) they are bit-identical to (4t)'s.
+ * ranks. The folds add the blocks in the order given, so every rank, a rank without rows included, computes the same bits for mean,
+ * rstd, ggamma, gbeta and (from the same starting values) the running statistics. When every rank's first row is a multiple of 128
+ * (always with one rank) the blocks are (4t)'s blocks and all results are bit-identical to (4t)'s. At any other cut -- a rank counts
+ * its blocks from ITS first row, so a boundary that is no multiple of 128 leaves a short last block on one rank and shifts the blocks
+ * of the next -- the sums are associated differently: still the same bits on every rank, and within the float64 bars that hold for
+ * (4t) (tests/dense_ref.py: train_bars), but not (4t)'s bits. z is row-local and equals (4t)'s z at every cut.
+ * z_dev, y_dev, gy_dev are contiguous [num_rows, O] (there is no leading dimension); every per-column vector has O elements.
  *   stage_sum:    z (as (4t)) and its per-block column sums -> part [nblk, O];
  *   stage_center: mean = (sum of the blocks) / total_rows, then the per-block sums of (z - mean)^2 -> part [nblk, O];
  *   stage_finish: rstd and the running statistics from the blocks of stage_center, then y = tanh(BN(z));

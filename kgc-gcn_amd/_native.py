@@ -720,14 +720,38 @@ def matmul_tn_supported(m, n):
     return m <= 208 and n <= 256
 
 
+def _bn_block(t, n, O, what, name):
+    """z / y of the training epilogue: the kernels index t[r * O + col] and take no leading dimension, so anything but a contiguous
+    [n, O] block (a column window of a wider tensor, say) would be read at the wrong stride. Refused, never copied."""
+    if t is None or t.dim() != 2 or tuple(t.shape) != (n, O) or not t.is_contiguous():
+        raise NativeError('%s: %s must be contiguous [%d, %d], got %s with strides %s'
+                          % (what, name, n, O, None if t is None else tuple(t.shape), None if t is None else tuple(t.stride())))
+
+
+def _bn_grad(gy, n, O, what):
+    """gy as autograd hands it over: [n, O] in any layout, made contiguous here."""
+    if gy is None or tuple(gy.shape) != (n, O):
+        raise NativeError('%s: gy must be [%d, %d], got %s' % (what, n, O, None if gy is None else tuple(gy.shape)))
+    return gy.contiguous()
+
+
+def _bn_vecs(O, what, **vecs):
+    """Per-column vectors (None = not given): O contiguous elements each, or the kernels read past their end."""
+    for name, v in vecs.items():
+        if v is not None and (v.numel() != O or not v.is_contiguous()):
+            raise NativeError('%s: %s must be contiguous with %d elements, got %s' % (what, name, O, tuple(v.shape)))
+
+
 def bn_tanh_train_fwd(u_in, u_out, u_loop, bias, gamma, beta, running_mean, running_var, momentum, eps):
     """(4t) z = (u_in + u_out + u_loop) / 3 (+ bias); y = tanh(BN_batch(z)). Returns (y, z, save_mean, save_rstd); updates
-    the running statistics in place when given."""
+    the running statistics in place when given. The products may be column windows (one common row stride); bias, gamma, beta
+    and the running statistics must have O elements: a wrong length is refused before any launch."""
     N, O = u_in.shape
     _same_device(u_in, u_out, u_loop, bias, gamma, beta, running_mean, running_var)
     for t in (u_in, u_out, u_loop):
         if tuple(t.shape) != (N, O) or t.stride(1) != 1 or t.stride(0) != u_in.stride(0):
             raise NativeError('bn_tanh_train_fwd: the three products must be [N, O] with the same row stride')
+    _bn_vecs(O, 'bn_tanh_train_fwd', bias=bias, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var)
     z = torch.empty((N, O), dtype=torch.float32, device=u_in.device)
     y = torch.empty_like(z)
     mean = torch.empty(O, dtype=torch.float32, device=u_in.device)
@@ -744,10 +768,14 @@ def bn_tanh_train_fwd(u_in, u_out, u_loop, bias, gamma, beta, running_mean, runn
 
 
 def bn_tanh_train_bwd(z, y, gy, mean, rstd, gamma):
-    """Backward of bn_tanh_train_fwd: (gz [N, O], gu = gz / 3, ggamma [O], gbeta [O])."""
+    """Backward of bn_tanh_train_fwd: (gz [N, O], gu = gz / 3, ggamma [O], gbeta [O]). z and y are the forward's own outputs:
+    contiguous [N, O] (refused otherwise, not copied); gy [N, O] in any layout; mean, rstd, gamma with O elements."""
     N, O = z.shape
     _same_device(z, y, gy, mean, rstd, gamma)
-    gy = gy.contiguous()
+    _bn_block(z, N, O, 'bn_tanh_train_bwd', 'z')
+    _bn_block(y, N, O, 'bn_tanh_train_bwd', 'y')
+    gy = _bn_grad(gy, N, O, 'bn_tanh_train_bwd')
+    _bn_vecs(O, 'bn_tanh_train_bwd', mean=mean, rstd=rstd, gamma=gamma)
     gz, gu = torch.empty_like(z), torch.empty_like(z)
     gg, gb = torch.empty_like(mean), torch.empty_like(mean)
     nbytes = lib().mgcn_bn_tanh_train_workspace(N, O)
@@ -773,6 +801,12 @@ def _bn_parts(parts, O, what):
     return parts.size(0)
 
 
+# (4s) The split stages below take this rank's rows [n, O] (n may be 0) and ALL ranks' block partials in rank-then-block order.
+# Each rank cuts ITS rows into 128-row blocks from its own first row, so at rank boundaries that are not multiples of 128 (the
+# ones GraphCSR.balanced_bounds produces) the blocks are not those of bn_tanh_train_fwd / _bwd: every rank still gets the same
+# bits for mean, rstd, ggamma, gbeta and the running statistics (same partials, same fold order), and the results meet the
+# float64 bars of (4t), but they are not (4t)'s bits. z, y must be contiguous [n, O] and every per-column vector must have O
+# elements: anything else is refused before a launch, never copied (gy alone is taken in any layout).
 def bn_train_stage_sum(u_in, u_out, u_loop, bias):
     """(4s) stage 1: z = (u_in + u_out + u_loop) / 3 (+ bias) of this rank's rows and its per-block column sums [bn_blocks(n), O]."""
     n, O = u_in.shape
@@ -780,8 +814,7 @@ def bn_train_stage_sum(u_in, u_out, u_loop, bias):
     for t in (u_in, u_out, u_loop):
         if tuple(t.shape) != (n, O) or (n > 0 and (t.stride(1) != 1 or t.stride(0) != u_in.stride(0))):
             raise NativeError('bn_train_stage_sum: the three products must be [N, O] with the same row stride')
-    if bias is not None and bias.numel() != O:
-        raise NativeError('bn_train_stage_sum: bias must have %d elements' % O)
+    _bn_vecs(O, 'bn_train_stage_sum', bias=bias)
     z = torch.empty((n, O), dtype=torch.float32, device=u_in.device)
     part = torch.empty((bn_blocks(n), O), dtype=torch.float32, device=u_in.device)
     if n > 0:
@@ -793,9 +826,11 @@ def bn_train_stage_sum(u_in, u_out, u_loop, bias):
 
 
 def bn_train_stage_center(z, sum_parts, total_rows):
-    """(4s) stage 2: mean [O] from ALL ranks' stage-1 blocks (rank, then block order) and this rank's blocks of (z - mean)^2."""
+    """(4s) stage 2: mean [O] from ALL ranks' stage-1 blocks (rank, then block order) and this rank's blocks of (z - mean)^2.
+    z: contiguous [n, O] (stage 1's own output)."""
     n, O = z.shape
     _same_device(z, sum_parts)
+    _bn_block(z, n, O, 'bn_train_stage_center', 'z')
     nb = _bn_parts(sum_parts, O, 'bn_train_stage_center')
     mean = torch.empty(O, dtype=torch.float32, device=z.device)
     part = torch.empty((bn_blocks(n), O), dtype=torch.float32, device=z.device)
@@ -807,13 +842,13 @@ def bn_train_stage_center(z, sum_parts, total_rows):
 
 
 def bn_train_stage_finish(z, sq_parts, total_rows, mean, gamma, beta, running_mean, running_var, momentum, eps):
-    """(4s) stage 3: rstd [O] (and the running statistics, in place) from ALL ranks' stage-2 blocks, then y = tanh(BN(z))."""
+    """(4s) stage 3: rstd [O] (and the running statistics, in place) from ALL ranks' stage-2 blocks, then y = tanh(BN(z)).
+    z: contiguous [n, O]; mean, gamma, beta and the running statistics: O elements."""
     n, O = z.shape
     _same_device(z, sq_parts, mean, gamma, beta, running_mean, running_var)
+    _bn_block(z, n, O, 'bn_train_stage_finish', 'z')
     nb = _bn_parts(sq_parts, O, 'bn_train_stage_finish')
-    for v in (mean, gamma, beta) + tuple(t for t in (running_mean, running_var) if t is not None):
-        if v.numel() != O or not v.is_contiguous():
-            raise NativeError('bn_train_stage_finish: per-column vectors must be contiguous with %d elements' % O)
+    _bn_vecs(O, 'bn_train_stage_finish', mean=mean, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var)
     y = torch.empty_like(z)
     rstd = torch.empty(O, dtype=torch.float32, device=z.device)
     _check(lib().mgcn_bn_train_stage_finish(
@@ -826,10 +861,14 @@ def bn_train_stage_finish(z, sq_parts, total_rows, mean, gamma, beta, running_me
 
 
 def bn_train_bwd_stage_sums(z, y, gy, mean, rstd):
-    """(4s) backward stage 1: this rank's per-block sums of g_pre and g_pre * xhat, as one [2, bn_blocks(n), O] tensor."""
+    """(4s) backward stage 1: this rank's per-block sums of g_pre and g_pre * xhat, as one [2, bn_blocks(n), O] tensor.
+    z, y: contiguous [n, O]; gy [n, O] in any layout; mean, rstd: O elements."""
     n, O = z.shape
     _same_device(z, y, gy, mean, rstd)
-    gy = gy.contiguous()
+    _bn_block(z, n, O, 'bn_train_bwd_stage_sums', 'z')
+    _bn_block(y, n, O, 'bn_train_bwd_stage_sums', 'y')
+    gy = _bn_grad(gy, n, O, 'bn_train_bwd_stage_sums')
+    _bn_vecs(O, 'bn_train_bwd_stage_sums', mean=mean, rstd=rstd)
     part = torch.empty((2, bn_blocks(n), O), dtype=torch.float32, device=z.device)
     if n > 0:
         _check(lib().mgcn_bn_train_bwd_stage_sums(n, O, _dev(z, torch.float32, 'z'), _dev(y, torch.float32, 'y'),
@@ -840,13 +879,17 @@ def bn_train_bwd_stage_sums(z, y, gy, mean, rstd):
 
 
 def bn_train_bwd_stage_apply(z, y, gy, mean, rstd, gamma, g_parts, gx_parts, total_rows):
-    """(4s) backward stage 2: (gz, gu = gz / 3, ggamma, gbeta) with ggamma / gbeta folded from ALL ranks' blocks."""
+    """(4s) backward stage 2: (gz, gu = gz / 3, ggamma, gbeta) with ggamma / gbeta folded from ALL ranks' blocks.
+    z, y: contiguous [n, O]; gy [n, O] in any layout; mean, rstd, gamma: O elements."""
     n, O = z.shape
     _same_device(z, y, gy, mean, rstd, gamma, g_parts, gx_parts)
+    _bn_block(z, n, O, 'bn_train_bwd_stage_apply', 'z')
+    _bn_block(y, n, O, 'bn_train_bwd_stage_apply', 'y')
+    gy = _bn_grad(gy, n, O, 'bn_train_bwd_stage_apply')
+    _bn_vecs(O, 'bn_train_bwd_stage_apply', mean=mean, rstd=rstd, gamma=gamma)
     nb = _bn_parts(g_parts, O, 'bn_train_bwd_stage_apply')
     if _bn_parts(gx_parts, O, 'bn_train_bwd_stage_apply') != nb:
         raise NativeError('bn_train_bwd_stage_apply: g / gx partials differ in blocks')
-    gy = gy.contiguous()
     gz, gu = torch.empty_like(z), torch.empty_like(z)
     gg, gb = torch.empty_like(mean), torch.empty_like(mean)
     live = n > 0

@@ -10,7 +10,12 @@ The grids are built from the kernels' own tiling constants (k-blocks of 32 / sla
 tiles of 16 / 32, pick_nt's switches at 32 / 64 / 128 / 208 columns, 128-row statistic blocks, 256-column trips). Each
 case carries a LABEL naming the path it is meant to take. The labels are test data written by hand from pick_nt,
 split_scoring, launch and mgcn_matmul_f32 in csrc/dense.hip, not a second dispatcher; the host test only checks that no
-label of its list has dropped out of the grids."""
+label of its list has dropped out of the grids.
+
+The training epilogue's bars (train_bars) serve both its unsplit form (4t) and its split stages (4s) at the ragged rank
+boundaries of TRAIN_RAGGED_CASES: emul_train_split_f32 restates the stages' association in f32 and the host test shows that
+it stays inside those bars, and that per-rank statistics do not."""
+import functools
 import math
 
 import torch
@@ -534,6 +539,186 @@ def train_inputs(n, o, with_bias, with_running):
     rv = torch.rand((o,), generator=g) + 0.5 if with_running else None
     gy = randn_scaled((n, o), g, 1.0)
     return u, bias, gamma, beta, rm, rv, gy
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# (4t) / (4s): the bars of the training epilogue, shared by the unsplit test and the split stages at ragged cuts. A partition
+# changes the association of the sums, not what is computed: one float64 reference, one set of bars.
+def train_bars(inputs, r64, cpu_err):
+    """{name: bar} for z, mean, rstd, y, gz, gu, ggamma, gbeta (and rm, rv when running statistics are given), in the order
+    the tests report them. inputs = train_inputs(...), r64 = ref_train_epilogue(...) in float64, cpu_err = {name: max |torch-CPU
+    f32 autograd - r64|}. z: two adds, a division, an add, each within u / 2 of its result (elementwise). The others:
+    derived_bar(cpu_err, floor, today) with floor = 8 u x the result and the largest term of its last additions and today =
+    the bar of test_training_layer_kernels_vs_torch_autograd (None: none)."""
+    u, bias, gamma, beta, rm, rv, gy = inputs
+    zmag = sum(t.double().abs() for t in u) + (bias.double().abs() if bias is not None else 0.0)
+    z64 = r64['z']
+    zabs = float(z64.abs().max())
+    rstd_max = float(r64['rstd'].max())
+    S = float((gamma.double().abs() * r64['rstd']).max())                       # |d y / d z| <= |gamma| rstd
+    gp = gy.double() * (1 - r64['y'] ** 2)
+    gp_max = float(gp.abs().max())
+    xh_max = float(((z64 - r64['mean']) * r64['rstd']).abs().max())
+    table = {
+        # name: (floor = 8 u x the result and the largest term of its last additions, today's bar or None)
+        'mean': (8 * U * zabs, None),
+        'rstd': (8 * U * rstd_max, None),
+        'y': (8 * U, 2e-6),
+        'gz': (8 * U * S * gp_max * (1 + xh_max * xh_max), 2e-5 * float(r64['gz'].abs().max())),
+        'gu': (8 * U * S * gp_max * (1 + xh_max * xh_max) / 3, 2e-5 * float(r64['gu'].abs().max())),
+        'ggamma': (8 * U * (float(r64['ggamma'].abs().max()) + gp_max * xh_max), 2e-5 * float(r64['ggamma'].abs().max())),
+        'gbeta': (8 * U * (float(r64['gbeta'].abs().max()) + gp_max), 2e-5 * float(r64['gbeta'].abs().max())),
+    }
+    if rm is not None:
+        table['rm'] = (8 * U * float(r64['rm'].abs().max()), 1e-7)
+        table['rv'] = (8 * U * float(r64['rv'].abs().max()), 1e-5 * float(r64['rv'].abs().min()) + 1e-7)
+    bars = {'z': 2 * U * zmag + 1e-45}
+    for name, (floor, today) in table.items():
+        bars[name] = derived_bar(cpu_err[name], floor, today)
+    return bars
+
+
+@functools.lru_cache(maxsize=3)
+def train_reference(n, o, with_bias, with_running):
+    """(inputs, r64, bars) of train_inputs(n, o, ...), on the CPU: computed once for all the partitions of one shape and shared
+    (treat it as read-only)."""
+    inputs = train_inputs(n, o, with_bias, with_running)
+    u, bias, gamma, beta, rm, rv, gy = inputs
+    r64 = ref_train_epilogue(*u, bias, gamma, beta, rm, rv, BN_MOMENTUM, BN_EPS, gy)
+    r32 = ref_train_epilogue(*u, bias, gamma, beta, rm, rv, BN_MOMENTUM, BN_EPS, gy, dtype=torch.float32)
+    cpu_err = {k: float((r32[k].double() - r64[k]).abs().max()) for k in r64 if r64[k] is not None}
+    return inputs, r64, train_bars(inputs, r64, cpu_err)
+
+
+def train_ratios(got, r64, bars):
+    """{name: max |got - float64| / bar} over the names of `bars`."""
+    return {name: max_ratio(got[name].cpu(), r64[name], bar) for name, bar in bars.items()}
+
+
+RB = 128                            # rows per statistic block (csrc/train_layer.hip)
+
+
+def rank_blocks(cuts):
+    """[(first row, end row)] of the 128-row blocks of the ranks [cuts[r], cuts[r + 1]), each rank counting from ITS first
+    row, in rank-then-block order: the order in which the stages fold them."""
+    out = []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        out.extend((r, min(r + RB, b)) for r in range(a, b, RB))
+    return out
+
+
+def _chain_fold_f32(terms, blocks):
+    """Column sums of the f32 `terms` [N, O] the way the kernels form them: one sequential f32 chain per block, the blocks'
+    sums added in the order given. (Short blocks are padded with +0 terms, which change no partial sum.)"""
+    longest = max(b - a for a, b in blocks)
+    pad = torch.zeros((len(blocks), longest, terms.shape[1]), dtype=torch.float32)
+    for i, (a, b) in enumerate(blocks):
+        pad[i, :b - a] = terms[a:b]
+    s = torch.zeros((len(blocks), terms.shape[1]), dtype=torch.float32)
+    for i in range(longest):
+        s = s + pad[:, i]
+    f = torch.zeros(terms.shape[1], dtype=torch.float32)
+    for i in range(len(blocks)):
+        f = f + s[i]
+    return f
+
+
+def emul_train_split_f32(inputs, cuts, wrong=None):
+    """The five stages of (4s) restated in f32 on the CPU (torch f32 elementwise arithmetic: every operation rounded on its
+    own) for ranks [cuts[r], cuts[r + 1]): per-rank 128-row blocks, a sequential chain inside a block, blocks folded in
+    rank-then-block order, mean = sum x (1 / float(N)), var = sum / float(N), and rstd, the running statistics, y, gz, gu,
+    ggamma, gbeta by the kernels' formulas. Not bit-exact to the device (an fma contracts differently): it shows what an f32
+    evaluation in this association is off by. Returns the dict of ref_train_epilogue.
+    wrong (the vacuity check of the host test; the statistics returned are those of the rank with the most rows, the hardest
+    to tell from right):
+      'own_mean'   every rank centres on the mean of its own rows,
+      'own_count'  every rank divides the global sums by its own row count."""
+    u, bias, gamma, beta, rm, rv, gy = inputs
+    n, o = u[0].shape
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    three = f32(3.0)
+    z = (u[0] + u[1] + u[2]) / three
+    if bias is not None:
+        z = z + bias
+    ranks = [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+    assert cuts[0] == 0 and cuts[-1] == n and all(b >= a for a, b in zip(cuts[:-1], cuts[1:]))
+    blocks = rank_blocks(cuts)
+    big = max(ranks, key=lambda ab: ab[1] - ab[0])
+
+    def stats(a, b):
+        """(mean, count as the kernel's float(n)) that the rank [a, b) uses."""
+        if wrong == 'own_mean':
+            return _chain_fold_f32(z, rank_blocks([a, b])) * (f32(1.0) / f32(float(b - a))), n
+        if wrong == 'own_count':
+            return _chain_fold_f32(z, blocks) * (f32(1.0) / f32(float(b - a))), b - a
+        return _chain_fold_f32(z, blocks) * (f32(1.0) / f32(float(n))), n
+
+    mean_rows = torch.empty_like(z)                         # the mean each row is centred on (one value unless `wrong`)
+    for a, b in ranks:
+        mean_rows[a:b] = stats(a, b)[0]
+    d = z - mean_rows
+    q = _chain_fold_f32(d * d, blocks)
+    mean, count = stats(*big)
+    var = q / f32(float(count))
+    rstd = f32(1.0) / torch.sqrt(var + f32(BN_EPS))
+    rstd_rows = rstd
+    if wrong == 'own_count':
+        rstd_rows = torch.empty_like(z)
+        for a, b in ranks:
+            rstd_rows[a:b] = f32(1.0) / torch.sqrt(q / f32(float(b - a)) + f32(BN_EPS))
+    new_rm = new_rv = None
+    if rm is not None:
+        unbiased = q / f32(float(count - 1)) if count > 1 else var
+        keep, mom = f32(1.0) - f32(BN_MOMENTUM), f32(BN_MOMENTUM)
+        new_rm, new_rv = keep * rm + mom * mean, keep * rv + mom * unbiased
+    xhat = d * rstd_rows
+    y = torch.tanh(xhat * gamma + beta)
+    gp = gy * (f32(1.0) - y * y)
+    gbeta, ggamma = _chain_fold_f32(gp, blocks), _chain_fold_f32(gp * xhat, blocks)
+    inv_n = f32(1.0) / f32(float(n))
+    gz = torch.empty_like(z)
+    for a, b in ranks:
+        inv = f32(1.0) / f32(float(b - a)) if wrong == 'own_count' else inv_n
+        rs = rstd_rows[a:b] if rstd_rows.dim() == 2 else rstd_rows
+        gz[a:b] = (gamma * rs) * (gp[a:b] - gbeta * inv - xhat[a:b] * (ggamma * inv))
+    return dict(z=z, y=y, mean=mean, rstd=rstd, rm=new_rm, rv=new_rv, gz=gz, gu=gz / three, ggamma=ggamma, gbeta=gbeta)
+
+
+def _each(n):
+    return tuple(range(n + 1))      # one row per rank
+
+
+EIGHT_RANKS_5003 = (0, 640, 1312, 1888, 2496, 3104, 3744, 4352, 5003)      # cuts at multiples of 32, as GraphCSR.balanced_bounds
+# (4s) at the cuts training produces: (N, O, bias given, running statistics given, cuts). Cuts that are no multiples of 128:
+# a short last block on one rank, a first block that starts mid-way on the next; ranks without rows first, in the middle and
+# last; ranks of one row, of 127, 128 and 129; one row per rank up to N = 129 (beyond that the emulation itself nears the bar:
+# 0.88 at N = 300 -- every one-row block is one more rounding of the fold).
+TRAIN_RAGGED_CASES = [
+    (2, 257, False, False, (0, 1, 2)), (2, 257, False, False, (0, 0, 2, 2)),
+    (127, 3, False, True, (0, 1, 127)), (127, 3, False, True, (0, 32, 96, 96, 127)), (127, 3, False, True, _each(127)),
+    (129, 257, True, True, (0, 1, 129)), (129, 257, True, True, (0, 128, 129)), (129, 257, True, True, (0, 32, 64, 129)),
+    (129, 257, True, True, (0, 0, 129, 129)), (129, 257, True, True, _each(129)),
+    (300, 200, True, True, (0, 96, 96, 224, 300)), (300, 200, True, True, (0, 127, 255, 300)), (300, 200, True, True, (0, 129, 300)),
+    (1000, 200, True, True, (0, 160, 352, 352, 608, 1000)), (1000, 200, True, True, (0, 999, 1000)), (1000, 200, True, True, (0, 1, 1000)),
+    (5003, 200, True, True, EIGHT_RANKS_5003), (5003, 200, True, True, (0, 5002, 5003)),
+    (5003, 513, True, True, (0, 1696, 3296, 5003)),
+]
+# extra floats of ldu (the products as column windows of wider tensors, NaN in the spare columns) for some of them
+TRAIN_RAGGED_LDU_EXTRA = {(300, 200, (0, 129, 300)): 5, (129, 257, (0, 32, 64, 129)): 3}
+# worst |emul_train_split_f32 - float64| / bar over TRAIN_RAGGED_CASES (y at N = 300, cuts 0-127-255-300): a record that
+# tests/test_dense_ref_host.py recomputes (stale beyond a factor 2), not the source of any bar.
+TRAIN_RAGGED_EMUL_WORST_RATIO_MEASURED = 0.65
+# ill-conditioned columns (ill_conditioned_z) on ragged cuts: (N, O, cuts)
+TRAIN_RAGGED_ILL_CASES = [(129, 257, (0, 32, 96, 129)), (129, 257, (0, 1, 129)), (5003, 300, (0, 1696, 3296, 5003)),
+                          (5003, 300, EIGHT_RANKS_5003)]
+# zero-row ranks first and last at block-aligned cuts: bit-identical to (4t). (N, O, cuts)
+TRAIN_SPLIT_EMPTY_ENDS = (1000, 257, (0, 0, 128, 1000, 1000))
+
+
+def ragged_id(case):
+    cuts = case[-1]
+    tail = 'each1' if len(cuts) > 9 else 'cuts' + '_'.join(str(c) for c in cuts)
+    return case_id(case[:-1]) + '-' + tail
 
 
 def bce_inputs(batch, n_local, dim, logit_scale=None):

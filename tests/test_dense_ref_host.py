@@ -259,6 +259,87 @@ def test_training_bars_are_not_looser_than_the_existing_test_at_its_shape():
     assert R.derived_bar(1e-6, 1e-9, 2e-6) == 4e-6                       # and does not apply where f32 cannot
 
 
+def test_ragged_cuts_are_the_ones_training_produces():
+    """TRAIN_RAGGED_CASES: well-formed partitions that between them hold a cut that is no multiple of 128 in every case but
+    the all-in-one-rank ones, ranks without rows first, in the middle and last, a rank of one row, of exactly 128 and of 129,
+    one row per rank, NULL running statistics, no bias, and widths on both sides of the 256-column trip."""
+    seen = set()
+    for N, O, wb, wr, cuts in R.TRAIN_RAGGED_CASES:
+        assert cuts[0] == 0 and cuts[-1] == N and all(b >= a for a, b in zip(cuts[:-1], cuts[1:])), cuts
+        rows = [b - a for a, b in zip(cuts[:-1], cuts[1:])]
+        live = [n for n in rows if n > 0]
+        assert sum(len(range(0, n, R.RB)) for n in rows) == len(R.rank_blocks(cuts))
+        if len(live) > 1:
+            assert any(c % R.RB for c in cuts[1:-1]) or 128 in rows, cuts
+        seen.update(k for k, hit in (('first', rows[0] == 0), ('last', rows[-1] == 0), ('middle', 0 in rows[1:-1]),
+                                     ('one', 1 in rows), ('128', 128 in rows), ('129', 129 in rows), ('each', len(rows) == N),
+                                     ('norun', not wr), ('nobias', not wb), ('wide', O > 256), ('narrow', O <= 256),
+                                     ('ldu', (N, O, cuts) in R.TRAIN_RAGGED_LDU_EXTRA)) if hit)
+    assert seen == {'first', 'last', 'middle', 'one', '128', '129', 'each', 'norun', 'nobias', 'wide', 'narrow', 'ldu'}, seen
+    assert all(any((n, o, c) == k for n, o, _, _, c in R.TRAIN_RAGGED_CASES) for k in R.TRAIN_RAGGED_LDU_EXTRA)
+    assert R.rank_blocks((0, 0, 130, 130, 300)) == [(0, 128), (128, 130), (130, 258), (258, 300)]
+
+
+def _live_ranks(cuts):
+    return sum(1 for a, b in zip(cuts[:-1], cuts[1:]) if b > a)
+
+
+def test_split_stage_emulation_meets_the_4t_bars_on_ragged_cuts():
+    """(4s) at cuts that are no multiples of 128: the f32 restatement of the stages (per-rank blocks, rank-then-block fold)
+    against float64 under the UNCHANGED bars of (4t), dense_ref.train_bars. A partition moves the association of the sums, and
+    the bars -- derived from torch-CPU f32 in yet another association -- have room for it. The worst ratio is recorded next
+    to the cases and must not go stale."""
+    worst, where = 0.0, None
+    for case in R.TRAIN_RAGGED_CASES:
+        N, O, wb, wr, cuts = case
+        inputs, r64, bars = R.train_reference(N, O, wb, wr)
+        ratios = R.train_ratios(R.emul_train_split_f32(inputs, cuts), r64, bars)
+        name = max(ratios, key=ratios.get)
+        print('EMUL %s worst %s %.4f' % (R.ragged_id(case), name, ratios[name]))
+        assert ratios[name] <= 1.0, (R.ragged_id(case), ratios)
+        if ratios[name] > worst:
+            worst, where = ratios[name], (R.ragged_id(case), name)
+    print('EMUL worst ratio %.4f at %s (recorded %.4f)' % (worst, where, R.TRAIN_RAGGED_EMUL_WORST_RATIO_MEASURED))
+    assert R.TRAIN_RAGGED_EMUL_WORST_RATIO_MEASURED / 2 <= worst <= R.TRAIN_RAGGED_EMUL_WORST_RATIO_MEASURED * 2, \
+        'the recorded worst ratio went stale'
+
+
+def test_split_stage_bars_notice_per_rank_statistics():
+    """Vacuity: the two mistakes a split epilogue can make without any test at aligned cuts noticing -- a rank that centres on
+    the mean of ITS rows, a rank that divides by ITS row count -- are outside the bars on every case with two ranks that have
+    rows, even judged by the rank with the most rows (5002 of 5003)."""
+    for case in R.TRAIN_RAGGED_CASES:
+        N, O, wb, wr, cuts = case
+        if _live_ranks(cuts) < 2:
+            continue
+        inputs, r64, bars = R.train_reference(N, O, wb, wr)
+        for wrong in ('own_mean', 'own_count'):
+            ratios = R.train_ratios(R.emul_train_split_f32(inputs, cuts, wrong=wrong), r64, bars)
+            assert ratios['z'] <= 1.0                                     # z is row-local: neither mistake touches it
+            stat = max(ratios['mean'], ratios['rstd'])
+            print('WRONG %s %s: statistics %.3g, y %.3g, gz %.3g x their bars' % (wrong, R.ragged_id(case), stat, ratios['y'], ratios['gz']))
+            assert stat > 1.0 and ratios['y'] > 1.0 and ratios['gz'] > 1.0, (wrong, R.ragged_id(case), ratios)
+
+
+def test_split_stage_emulation_on_ill_conditioned_columns():
+    """Columns with mean 100 and spread 1e-2 at ragged cuts: the emulated mean within colsum_bar, rstd within ill_rstd_bar
+    (both taken on the z the stages return, as the device test does)."""
+    w_mean, w_rstd = 0.0, 0.0
+    for N, O, cuts in R.TRAIN_RAGGED_ILL_CASES:
+        g = R.gen(R.seed_of(6, N, O))
+        zin = R.ill_conditioned_z(N, O, g)
+        gamma, beta = R.pm_uniform((O,), g) * 1.5, R.randn_scaled((O,), g, 0.1)
+        e = R.emul_train_split_f32(([zin, zin, zin], None, gamma, beta, None, None, torch.zeros_like(zin)), cuts)
+        z64 = e['z'].double()
+        r_mean = R.max_ratio(e['mean'], z64.mean(0), R.colsum_bar(z64.abs().sum(0) / N, N))
+        rstd64 = 1 / torch.sqrt(z64.var(0, unbiased=False) + R.BN_EPS)
+        r_rstd = R.max_ratio(e['rstd'], rstd64, R.ill_rstd_bar(e['z'], R.BN_EPS) * rstd64)
+        print('ILL N = %d, %d ranks: mean %.3f of colsum_bar, rstd %.3f of ill_rstd_bar' % (N, len(cuts) - 1, r_mean, r_rstd))
+        assert r_mean <= 1.0 and r_rstd <= 1.0
+        w_mean, w_rstd = max(w_mean, r_mean), max(w_rstd, r_rstd)
+    print('ILL worst: mean %.3f, rstd %.3f' % (w_mean, w_rstd))
+
+
 def test_layouts_and_guards():
     t = torch.arange(15, dtype=torch.float32).reshape(3, 5)
     for kind in R.LAYOUTS:

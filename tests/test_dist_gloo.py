@@ -153,3 +153,78 @@ def test_gather_helper_gloo():
         assert keys == [('gloo', 'cpu')]
         assert ints.tolist() == [0, 7, 1, 8]
         assert raised
+
+
+# ------------------------------------------------------------------------------------------------
+# _Exchange.gather_rows / gather_blocks: the padding bookkeeping that puts ragged ranks' rows and BN block partials in fold order
+EXCHANGE_BOUNDS = {
+    # ranks without rows first / in the middle / last, ranks under 128 rows, of exactly 128, of 129, and equal chunks with a short
+    # last rank (gather_rows' slice-only path)
+    2: [[0, 0, 130], [0, 128, 128], [0, 97, 300], [0, 129, 257], [0, 200, 300]],
+    3: [[0, 0, 128, 200], [0, 100, 100, 357], [0, 33, 161, 161], [0, 300, 301, 430], [0, 128, 256, 300]],
+    4: [[0, 0, 96, 96, 224], [0, 32, 160, 160, 500], [0, 127, 255, 300, 300], [0, 1, 2, 3, 400], [0, 0, 0, 0, 129]],
+}
+EXCHANGE_O = 5
+
+
+def _exchange_input(cfg, rank, kind, shape):
+    """What rank `rank` puts into collective `kind` of bounds list `cfg`: seeded by the rank, so every process can form it."""
+    g = torch.Generator().manual_seed(100000 * cfg + 100 * rank + kind)
+    return torch.randn(shape, generator=g) + 1000.0 * (rank + 1)          # (no zero: padding that leaked would show)
+
+
+def _exchange_worker(rank, world, port, q):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    pkg = load_pkg()
+    out = []
+    for cfg, b in enumerate(EXCHANGE_BOUNDS[world]):
+        ex = pkg.dist._Exchange(b, rank, None, world)
+        n = b[rank + 1] - b[rank]
+        nb = pkg._native.bn_blocks(n)
+        rows = ex.gather_rows(_exchange_input(cfg, rank, 0, (n, EXCHANGE_O)))
+        flat = ex.gather_blocks(_exchange_input(cfg, rank, 1, (nb, EXCHANGE_O)))
+        pair = ex.gather_blocks(_exchange_input(cfg, rank, 2, (2, nb, EXCHANGE_O)))
+        # (as numpy arrays: pickled by value, so the parent can read them after this process has gone)
+        out.append((rows.numpy().copy(), flat.numpy().copy(), pair.numpy().copy(), pair.is_contiguous() and flat.is_contiguous(),
+                    (list(ex.rows), ex.chunk, ex.total, ex.n0, ex.n1)))
+    q.put((rank, out))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize('world', [2, 3, 4])
+def test_exchange_gathers_ragged_rows_and_blocks_in_rank_order_gloo(pkg, world):
+    """Every rank gets exactly the concatenation, in rank order, of what each rank put in: the rows [N, O], the block partials
+    [blocks, O] and the stacked pair [2, blocks, O] (concatenated along the blocks) -- no padding row left in, none of a rank's
+    rows dropped, a rank without rows or blocks contributing nothing -- and rows / chunk / total follow the bounds."""
+    port = 29500 + (os.getpid() + 131 * world + 300) % 2000
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_exchange_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    got = dict(q.get(timeout=120) for _ in range(world))
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    blocks = pkg._native.bn_blocks
+    for cfg, b in enumerate(EXCHANGE_BOUNDS[world]):
+        n = [b[r + 1] - b[r] for r in range(world)]
+        want_rows = torch.cat([_exchange_input(cfg, r, 0, (n[r], EXCHANGE_O)) for r in range(world)])
+        want_flat = torch.cat([_exchange_input(cfg, r, 1, (blocks(n[r]), EXCHANGE_O)) for r in range(world)])
+        want_pair = torch.cat([_exchange_input(cfg, r, 2, (2, blocks(n[r]), EXCHANGE_O)) for r in range(world)], dim=1)
+        assert want_rows.size(0) == b[-1] and want_flat.size(0) == sum(blocks(v) for v in n)
+        for r in range(world):
+            rows, flat, pair, contiguous, book = got[r][cfg]
+            rows, flat, pair = torch.from_numpy(rows), torch.from_numpy(flat), torch.from_numpy(pair)
+            assert torch.equal(rows, want_rows), (b, r)
+            assert torch.equal(flat, want_flat), (b, r)
+            assert torch.equal(pair, want_pair), (b, r)
+            assert contiguous                                               # the stages take the partials as contiguous blocks
+            assert book == (n, max(n), b[-1], b[r], b[r + 1]), (b, r, book)
+    # one rank: no collective, the input itself
+    ex = pkg.dist._Exchange([0, 130], 0, None, 1)
+    t = torch.randn(130, EXCHANGE_O)
+    assert ex.gather_rows(t) is t and ex.gather_blocks(t[:2]) is not None and (ex.rows, ex.chunk, ex.total) == ([130], 130, 130)
