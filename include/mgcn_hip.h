@@ -914,7 +914,8 @@ int mgcn_cand_bce_bwd_ent(int32_t batch, int64_t n_cand, int64_t n_local, int64_
  * (seed, step, global batch row, list position) and of the index: every rank of a sharded step draws the same [B, K] block
  * without an exchange, and a checkpoint restores the stream from (seed, step count). Integers only, so the bits are exact.
  *
- *   - key = sm(sm(sm(seed) ^ step) ^ site) of (12) with the site id 0x2000; the host forms it and passes it by value.
+ *   - key = sm(sm(sm(seed) ^ step) ^ site) of (12) with the site id 0x2000; the host forms it and passes it by value
+ *     (mgcn_cand_draw), or the lanes form its last step from a word in device memory (mgcn_cand_draw_dev, below).
  *   - For list position (b, j), with the 64-bit global batch row row = row0 + b: the words w0..w3 are Philox4x32-10 of (12) with
  *     key words (key & 0xffffffff, key >> 32) and counter (row_lo, row_hi, j >> 1, 0); r = w0 | w1 << 32 for even j,
  *     r = w2 | w3 << 32 for odd j. One Philox call serves two positions.
@@ -932,6 +933,13 @@ int mgcn_cand_bce_bwd_ent(int32_t batch, int64_t n_cand, int64_t n_local, int64_
  *
  * mgcn_cand_draw: one launch, at most 2048 workgroups of 256 threads grid-striding over (b, j >> 1); no LDS, no atomics, 64-bit
  *   index arithmetic. Columns n_cand .. ldc of a padded row are not touched. ptr holds num_keys + 1 entries, tails n_tails.
+ * mgcn_cand_draw_dev: mgcn_cand_draw with the key read from device memory, as the _dev forms of (12): step_key_dev points at ONE
+ *   64-bit word in device memory that holds sm(sm(seed) ^ step), `site` is the site id (0x2000), and every thread forms
+ *   key = sm(*step_key_dev ^ site) once, ahead of its grid-stride loop, and hands it to the same inline function. The word is read
+ *   when the kernel RUNS, not when it is enqueued: a launch captured into a hipGraph draws, on every replay, the lists of the word
+ *   it finds (captured.CapturedCandidateStep writes the word ahead of each replay). Same geometry, same checks, same bits as
+ *   mgcn_cand_draw under the key of that word. A null step_key_dev, or one not aligned to 8 bytes, is MGCN_EINVAL before any other
+ *   check and at batch == 0 too.
  * mgcn_cand_draw_host: the same block on the CPU over host pointers, from the SAME inline function the kernel calls: test
  *   infrastructure, the role mgcn_dropout_mask_host plays in (12).
  * MGCN_EINVAL, nothing launched and nothing written (all checks precede the first HIP call): a null qkey / ptr / cand, a null
@@ -942,6 +950,10 @@ int mgcn_cand_bce_bwd_ent(int32_t batch, int64_t n_cand, int64_t n_local, int64_
 int mgcn_cand_draw(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
                    const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails, uint64_t key,
                    uint64_t row0, int64_t *cand_dev, int64_t ldc, uint8_t *label_dev, int64_t ldl, void *stream);
+int mgcn_cand_draw_dev(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
+                       const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails,
+                       const uint64_t *step_key_dev, uint64_t site, uint64_t row0, int64_t *cand_dev, int64_t ldc, uint8_t *label_dev,
+                       int64_t ldl, void *stream);
 int mgcn_cand_draw_host(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_host, int64_t num_keys,
                         const int64_t *keys_host, const int64_t *ptr_host, const int32_t *tails_host, int64_t n_tails, uint64_t key,
                         uint64_t row0, int64_t *cand_host, int64_t ldc, uint8_t *label_host, int64_t ldl);

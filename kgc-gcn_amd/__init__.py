@@ -3,7 +3,7 @@ aggregation, the dense layer epilogue, full-graph scoring and filtered ranking, 
 model.py / data_loader.py surface. The directory name is not a Python identifier: import it with
 importlib.import_module('kgc-gcn_amd')."""
 from . import _native, captured, data_loader, dist, dropin, graph, harness, model, optim, utils  # noqa: F401
-from .captured import CapturedTrainStep  # noqa: F401
+from .captured import CapturedCandidateStep, CapturedTrainStep  # noqa: F401
 from .data_loader import DataLoader, KBDataset  # noqa: F401
 from .graph import Graph, GraphCSR  # noqa: F401
 from .model import MGCN, ConvE, MGCNConv  # noqa: F401

@@ -130,6 +130,7 @@ _SIGNATURES = {
     'mgcn_dropout_mask_dev': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _u64, _u64, _u32, _ptr]),
     'mgcn_dropout_mask_host': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _u64, _u64, _u32]),
     'mgcn_cand_draw': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _u64, _u64, _ptr, _i64, _ptr, _i64, _ptr]),
+    'mgcn_cand_draw_dev': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64, _ptr]),
     'mgcn_cand_draw_host': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _u64, _u64, _ptr, _i64, _ptr, _i64]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
@@ -1788,7 +1789,10 @@ def _cand_draw(fn, what, on_gpu, qkey, keys, ptr, tails, num_entities, n_cand, k
         label = torch.empty((B, max(K, 0)), dtype=torch.uint8, device=dev)
     if not labels:
         label = None
-    _same_device(qkey, keys, ptr, tails, cand, label)
+    dev_key = isinstance(key, DeviceKey)
+    if dev_key and not on_gpu:
+        raise NativeError('%s: a DeviceKey is for the GPU launch' % what)
+    _same_device(qkey, keys, ptr, tails, cand, label, key.word if dev_key else None)
 
     def block(t, dtype, name):
         if t.dim() != 2 or tuple(t.shape) != (B, K) or (t.dtype != dtype and not (dtype == torch.uint8 and t.dtype == torch.bool)) \
@@ -1806,17 +1810,20 @@ def _cand_draw(fn, what, on_gpu, qkey, keys, ptr, tails, num_entities, n_cand, k
     lp, ldl = (block(label, torch.uint8, 'label') if K >= 1 else (label.data_ptr(), 0)) if label is not None else (None, 0)
     args = [B, K, int(num_entities), arr(qkey, torch.int64, 'qkey') if B else qkey.new_zeros(1).data_ptr(), keys.numel(),
             arr(keys, torch.int64, 'keys'), arr(ptr, torch.int64, 'ptr'), arr(tails, torch.int32, 'tails'), tails.numel(),
-            int(key) & _M64, int(row0) & _M64, cp, ldc, lp, ldl]
+            ] + ([key.word.data_ptr(), key.site] if dev_key else [int(key) & _M64]) + [int(row0) & _M64, cp, ldc, lp, ldl]
     _check(fn(*(args + ([_stream(cand)] if on_gpu else []))), what)
     return cand, label
 
 
 def cand_draw(qkey, keys, ptr, tails, num_entities, n_cand, key, row0=0, labels=True, out=None):
     """(15) (cand [B, n_cand] int64, label [B, n_cand] uint8 or None): the candidate lists of the queries with keys qkey [B] under
-    `key` (dropout_key(seed, step, CAND_DRAW_SITE)), row b being global batch row row0 + b. Column 0 is one known tail of the query
+    `key` (dropout_key(seed, step, CAND_DRAW_SITE); or a DeviceKey(word, CAND_DRAW_SITE), whose word on the tensors' device holds
+    dropout_step_key(seed, step) when the kernel RUNS: mgcn_cand_draw_dev, what a captured launch needs), row b being global batch row row0 + b. Column 0 is one known tail of the query
     drawn from its run in the keys / ptr / tails arrays of filter_mask() (-1 for a query without one), the other columns are ids
     in [0, num_entities); label is cand_labels() of the drawn list against the whole table. One launch (see mgcn_cand_draw).
     out: a cand tensor, or (cand, label), to write into (padded row views are fine)."""
+    if isinstance(key, DeviceKey):
+        return _cand_draw(lib().mgcn_cand_draw_dev, 'mgcn_cand_draw_dev', True, qkey, keys, ptr, tails, num_entities, n_cand, key, row0, labels, out)
     return _cand_draw(lib().mgcn_cand_draw, 'mgcn_cand_draw', True, qkey, keys, ptr, tails, num_entities, n_cand, key, row0, labels, out)
 
 

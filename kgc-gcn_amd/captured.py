@@ -11,6 +11,9 @@ device that the host computes in the eager step, so the trajectory is the eager 
 reproducible (the HIP trunk and query path). A scheduler's lr, load_dropout_state, a changed seed and model.load_state_dict (an
 in-place copy) take effect on the next replay without a new capture.
 
+CapturedCandidateStep, at the end of the module, is the same wrapper around the sampled-negative step: its lists are
+drawn inside the graph by mgcn_cand_draw_dev from a second device word that travels in the same copy.
+
 Out of scope: dist.train_step_sharded (its collectives would sit inside the capture), harness.train (its label rows are built on
 the host) and torch-drawn dropout (a generator's state does not advance in a replay): the wrapper refuses a dropout site with
 p > 0 unless params.dropout is 'counter'.
@@ -24,6 +27,7 @@ After a replay every .grad is one of the graph's static tensors (contents unspec
 private pool keeps the step's activations, gradients and workspaces alive for as long as the wrapper lives.
 """
 import logging
+import operator
 import os
 import types
 
@@ -123,6 +127,11 @@ class CapturedTrainStep(object):
         if any(p > 0 for p in self._dropout_ps()) and not _counter_dropout_wanted(m.params):
             raise _native.NativeError('CapturedTrainStep: a dropout site has p > 0 and params.dropout is not \'counter\': masks drawn '
                                       'from a torch generator would be frozen into the graph')
+        self._refuse_batch(src)
+
+    def _refuse_batch(self, src):
+        """The batch the step's scoring launch does not take (here: the full-table score + loss launch)."""
+        m = self.model
         B, O = int(src.numel()), int(m.params.gcn_out_dim)
         probe = torch.empty((B, O), dtype=torch.float32, device=m.entity_embedding.device)
         if B == 0 or not _native.score_bce_supported(probe, probe):
@@ -153,20 +162,23 @@ class CapturedTrainStep(object):
         return bool(with_grad) and all(len(opt.state.get(p, ())) > 0 for p in with_grad)
 
     # -- staging of the step scalars ---------------------------------------------------------------
+    _WORDS = 1     # 64-bit words at the head of the staging buffer: the dropout step word (a subclass may add its own after it)
+
     def _staging(self, device, rows):
         """The device buffer the captured launches read (8 bytes: the dropout step word; then `rows` float pairs: Adam's
         step_size and bc2_sqrt per group) and a ring of pinned host images of it."""
         st = self._stage
         if st is None or st.device != device or st.rows != rows:
-            nbytes = 8 + 8 * rows
+            head = 8 * self._WORDS
+            nbytes = head + 8 * rows
             dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
-            st = types.SimpleNamespace(device=device, rows=rows, dev=dev, word=dev[:8].view(torch.int64),
-                                       hyper=dev[8:].view(torch.float32).view(rows, 2), slots=[], next=0)
+            st = types.SimpleNamespace(device=device, rows=rows, dev=dev, word=dev[:8].view(torch.int64), words=dev[:head].view(torch.int64),
+                                       hyper=dev[head:].view(torch.float32).view(rows, 2), slots=[], next=0)
             st.hyper.fill_(1.0)
             for _ in range(_RING):
                 host = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
                 image = host.numpy()
-                st.slots.append(types.SimpleNamespace(host=host, word=image[:8].view(np.uint64), hyper=image[8:].view(np.float32),
+                st.slots.append(types.SimpleNamespace(host=host, word=image[:head].view(np.uint64), hyper=image[head:].view(np.float32),
                                                       event=torch.cuda.Event(), used=False))
             self._stage = st
         return st
@@ -180,11 +192,15 @@ class CapturedTrainStep(object):
         if slot.used:
             slot.event.synchronize()                  # (its copy of _RING replays ago has long run: this returns at once)
         slot.word[0] = _native.dropout_step_key(m.dropout_seed, m.dropout_step)
+        self._stage_words(slot)
         for k, (step_size, bc2_sqrt) in enumerate(self.optimizer.hyper_values(hit.rows)):
             slot.hyper[2 * k], slot.hyper[2 * k + 1] = step_size, bc2_sqrt     # doubles rounded to float, as the by-value call
         st.dev.copy_(slot.host, non_blocking=True)
         slot.event.record()
         slot.used = True
+
+    def _stage_words(self, slot):
+        """The words of a subclass (slot.word[1:]), written into the same pinned image: still one copy per replay."""
 
     def _warm_kernels(self, st):
         """One launch of the device-scalar entry points on scratch tensors, once per wrapper, outside the capture; leaves no
@@ -283,3 +299,93 @@ class CapturedTrainStep(object):
             if hit is None:
                 return self._eager(src, rel)
         return self._replay(hit, src, rel)
+
+
+class CapturedCandidateStep(CapturedTrainStep):
+    """step = CapturedCandidateStep(model, graph, index, optimizer, num_neg, draw_seed, draw_step=0, loss='bce', lbl_smooth=0.0,
+    clip=None, warmup=2); loss = step(src, rel).
+
+    CapturedTrainStep for the sampled-negative step: one step of harness.train_sampled_negatives(draw_seed=...) --
+    zero_grad, harness.draw_candidates(..., labels=True), MGCN.forward_loss_candidates(labels=..., loss=...), backward,
+    ClipAdam.clip_and_step -- with everything the parent says about warm-up, other batch sizes, re-captures, counters and the
+    fall-back to eager. `draw_seed` and `draw_step` are plain int attributes: every call, eager or replayed, draws the lists of
+    (draw_seed, draw_step) and then adds one to draw_step; both may be set at any time (a run resumes from a checkpoint's
+    draw_seed and step count) and act on the next call without a new capture. Eager calls pass the list key by value. The
+    captured draw (mgcn_cand_draw_dev) reads a second device word, dropout_step_key(draw_seed, draw_step), which the wrapper
+    writes next to the dropout step word and the Adam pairs in the same pinned image: a replay still costs ONE host-to-device copy
+    of scalars. `num_neg` and `loss` are plain attributes held by value in the graph: changing one re-captures. `cand` is the
+    [B, 1 + num_neg] block of the last call (after a replay: the graph's static tensor, overwritten by the next replay).
+
+    Raises NativeError, before anything is captured, for what the parent refuses (but the scoring stage takes any batch >= 1),
+    for num_neg < 0, a loss other than 'bce' / 'softmax' and an index that is not on the model's device."""
+
+    _WORDS = 2     # the dropout step word, then the draw word
+
+    def __init__(self, model, graph, index, optimizer, num_neg, draw_seed, draw_step=0, loss='bce', lbl_smooth=0.0, clip=None, warmup=2):
+        super().__init__(model, graph, index, optimizer, lbl_smooth=lbl_smooth, clip=clip, warmup=warmup)
+        self.num_neg, self.draw_seed, self.draw_step, self.loss = num_neg, int(draw_seed), int(draw_step), loss
+        self.cand = None
+
+    def _body(self, src, rel):
+        from .harness import draw_candidates
+        m, opt = self.model, self.optimizer
+        # while the parent captures, the model holds the dropout step word: the draw then reads ITS word, the one next to it
+        word = self._stage.words[1:2] if m._step_key_dev is not None else None
+        opt.zero_grad(set_to_none=True)
+        cand, labels = draw_candidates(torch.stack((src.reshape(-1), rel.reshape(-1)), 1), self.index, m.entity_embedding.size(0), self.num_neg,
+                                       self.draw_seed, self.draw_step, labels=True, step_key_dev=word)
+        self.draw_step += 1
+        loss = m.forward_loss_candidates(src, rel, cand, self.graph, labels=labels, lbl_smooth=self.lbl_smooth, loss=self.loss)
+        loss.backward()
+        opt.clip_and_step(self.clip)
+        self.cand = cand
+        return loss.detach()
+
+    def _refuse(self, src):
+        super()._refuse(src)
+        try:
+            bad = operator.index(self.num_neg) < 0
+        except TypeError:
+            bad = True
+        if bad:
+            raise _native.NativeError('CapturedCandidateStep: num_neg must be an int >= 0, got %r' % (self.num_neg,))
+        if self.loss not in ('bce', 'softmax'):
+            raise _native.NativeError("CapturedCandidateStep: loss must be 'bce' or 'softmax', got %r" % (self.loss,))
+        dev = self.model.entity_embedding.device
+        if any(t.device != dev for t in (self.index.keys, self.index.ptr, self.index.tails)):
+            raise _native.NativeError('CapturedCandidateStep: the index is not on the model\'s device (%s)' % (dev,))
+
+    def _refuse_batch(self, src):
+        if int(src.numel()) == 0:
+            raise _native.NativeError('CapturedCandidateStep: an empty batch')
+
+    def _key(self):
+        ix = self.index       # (the parent's key holds the index tensors' addresses too: here the draw reads them as well)
+        return super()._key() + (self.num_neg, self.loss, ix.keys.data_ptr(), ix.ptr.data_ptr(), ix.tails.data_ptr())
+
+    def _stage_words(self, slot):
+        slot.word[1] = _native.dropout_step_key(self.draw_seed, self.draw_step)
+
+    def _warm_kernels(self, st):
+        if not self._warmed:                           # the _dev draw, once, on scratch tensors (see the parent's)
+            one = torch.zeros(1, dtype=torch.int64, device=st.device)
+            for labels in (True, False):
+                _native.cand_draw(one, one, torch.zeros(2, dtype=torch.int64, device=st.device), torch.zeros(1, dtype=torch.int32, device=st.device),
+                                  1, 2, _native.DeviceKey(st.words[1:2], _native.CAND_DRAW_SITE), labels=labels)
+        super()._warm_kernels(st)
+
+    def _capture(self, src, rel, key):
+        saved = self.draw_step                         # capturing runs _body's Python, not its launches
+        try:
+            hit = super()._capture(src, rel, key)
+        finally:
+            self.draw_step = saved
+        if hit is not None:
+            hit.cand = self.cand                       # the graph's static list block
+        return hit
+
+    def _replay(self, hit, src, rel):
+        loss = super()._replay(hit, src, rel)          # (its _upload staged the word of draw_step)
+        self.draw_step += 1
+        self.cand = hit.cand
+        return loss

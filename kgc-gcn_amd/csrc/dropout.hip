@@ -5,7 +5,7 @@
 // and leading dimensions allow it and takes the element-wise path otherwise (same bits). No atomics, no LDS, no inline assembly;
 // all index arithmetic is 64-bit.
 // The same Philox function also draws the candidate lists of sampled-negative training (include/mgcn_hip.h (15)):
-// mgcn_cand_draw and its host twin, at the end of the anonymous namespace.
+// mgcn_cand_draw, its device-key form and its host twin, at the end of the anonymous namespace.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -288,7 +288,7 @@ struct DrawArgs {
   const int64_t *keys, *ptr;
   const int32_t *tails;
   int64_t n_tails;
-  uint64_t key, row0;
+  uint64_t key, row0;      // key: the list key, or the site id in mgcn_cand_draw_dev (draw_kernel forms the key from it)
   int64_t *cand;
   int64_t ldc;
   uint8_t *label;      // null: no labels, and no key lookup for the pairs that hold negatives only
@@ -349,8 +349,12 @@ __host__ __device__ inline void draw_pair(const DrawArgs &a, int64_t b, int64_t 
   }
 }
 
-__global__ __launch_bounds__(TPB) void draw_kernel(int64_t batch, int32_t npairs, DrawArgs a) {
+// KD false: a.key is the list key. KD true (mgcn_cand_draw_dev): a.key is the site id, and every thread forms the key once, ahead of
+// its loop, from the step word in device memory, so a captured launch draws under the word it finds when it RUNS.
+template <bool KD>
+__global__ __launch_bounds__(TPB) void draw_kernel(int64_t batch, int32_t npairs, DrawArgs a, const uint64_t *__restrict__ step_key) {
   const int64_t units = batch * npairs, stride = int64_t(gridDim.x) * TPB;
+  a.key = site_key<KD>(a.key, step_key);
   for (int64_t u = int64_t(blockIdx.x) * TPB + threadIdx.x; u < units; u += stride) {
     int64_t b;
     int32_t jp;
@@ -359,7 +363,7 @@ __global__ __launch_bounds__(TPB) void draw_kernel(int64_t batch, int32_t npairs
   }
 }
 
-// every check of mgcn_cand_draw / mgcn_cand_draw_host; MGCN_OK, or the code with the message set
+// every check of mgcn_cand_draw / mgcn_cand_draw_dev / mgcn_cand_draw_host; MGCN_OK, or the code with the message set
 int check_draw(const char *what, int64_t batch, const DrawArgs &a) {
   MGCN_REQUIRE(batch >= 0 && a.n_cand >= 1 && a.num_keys >= 0 && a.n_tails >= 0, "%s: bad sizes (batch = %lld, n_cand = %lld, num_keys = %lld, n_tails = %lld)",
                what, (long long)batch, (long long)a.n_cand, (long long)a.num_keys, (long long)a.n_tails);
@@ -372,19 +376,38 @@ int check_draw(const char *what, int64_t batch, const DrawArgs &a) {
   return MGCN_OK;
 }
 
+// both device entries: step_key_dev == nullptr: a.key is the key (by value); otherwise it is the site id
+int draw_launch(const char *what, int64_t batch, const DrawArgs &a, const uint64_t *step_key_dev, void *stream) {
+  if (int rc = check_draw(what, batch, a)) return rc;
+  if (batch == 0) return MGCN_OK;
+  const int32_t npairs = int32_t((a.n_cand + 1) / 2);
+  const dim3 grid(grid_for(batch * npairs)), block(TPB);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (step_key_dev)
+    draw_kernel<true><<<grid, block, 0, st>>>(batch, npairs, a, step_key_dev);
+  else
+    draw_kernel<false><<<grid, block, 0, st>>>(batch, npairs, a, nullptr);
+  MGCN_CHECK_LAUNCH(what);
+  return MGCN_OK;
+}
+
 }  // namespace
 
 extern "C" int mgcn_cand_draw(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
                               const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails, uint64_t key,
                               uint64_t row0, int64_t *cand_dev, int64_t ldc, uint8_t *label_dev, int64_t ldl, void *stream) {
-  const char *what = "mgcn_cand_draw";
   const DrawArgs a = {n_cand, num_entities, qkey_dev, num_keys, keys_dev, ptr_dev, tails_dev, n_tails, key, row0, cand_dev, ldc, label_dev, ldl};
-  if (int rc = check_draw(what, batch, a)) return rc;
-  if (batch == 0) return MGCN_OK;
-  const int32_t npairs = int32_t((n_cand + 1) / 2);
-  draw_kernel<<<dim3(grid_for(batch * npairs)), dim3(TPB), 0, static_cast<hipStream_t>(stream)>>>(batch, npairs, a);
-  MGCN_CHECK_LAUNCH(what);
-  return MGCN_OK;
+  return draw_launch("mgcn_cand_draw", batch, a, nullptr, stream);
+}
+
+extern "C" int mgcn_cand_draw_dev(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
+                                  const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails,
+                                  const uint64_t *step_key_dev, uint64_t site, uint64_t row0, int64_t *cand_dev, int64_t ldc,
+                                  uint8_t *label_dev, int64_t ldl, void *stream) {
+  const char *what = "mgcn_cand_draw_dev";
+  if (int rc = check_step_key(what, step_key_dev)) return rc;
+  const DrawArgs a = {n_cand, num_entities, qkey_dev, num_keys, keys_dev, ptr_dev, tails_dev, n_tails, site, row0, cand_dev, ldc, label_dev, ldl};
+  return draw_launch(what, batch, a, step_key_dev, stream);
 }
 
 extern "C" int mgcn_cand_draw_host(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_host, int64_t num_keys,

@@ -106,7 +106,7 @@ def sample_candidates(q, index, num_entities, num_neg, generator=None, check=Tru
     return cand
 
 
-def draw_candidates(q, index, num_entities, num_neg, seed, step, labels=False):
+def draw_candidates(q, index, num_entities, num_neg, seed, step, labels=False, step_key_dev=None):
     """sample_candidates without a generator: the lists [B, 1 + num_neg] int64 of the queries q [B, >= 2] on the GPU
     are a pure function of (seed, step, batch row, list position) and of `index`, drawn by one HIP launch
     (_native.cand_draw under the key of (seed, step, CAND_DRAW_SITE)): every rank of a sharded step that passes the same q, seed
@@ -114,10 +114,13 @@ def draw_candidates(q, index, num_entities, num_neg, seed, step, labels=False):
     known tail of the query, or -1 for a query without one (a dead position: it contributes nothing and counts in the mean's
     divisor; no host read checks it); the other columns are uniform ids in [0, num_entities). labels=True: returns
     (cand, label [B, 1 + num_neg] uint8), the labels _native.cand_labels gives the drawn list against the whole table, from the
-    same launch: what forward_loss_candidates(labels=...) and dist.train_step_sharded_candidates(labels=...) take."""
+    same launch: what forward_loss_candidates(labels=...) and dist.train_step_sharded_candidates(labels=...) take.
+    step_key_dev: a one-element int64 tensor on q's device that holds _native.dropout_step_key(seed, step) when the launch RUNS
+    (captured.CapturedCandidateStep's second word); `seed` and `step` are then unused."""
     from . import _native
+    key = _native.dropout_key(seed, step, _native.CAND_DRAW_SITE) if step_key_dev is None else _native.DeviceKey(step_key_dev, _native.CAND_DRAW_SITE)
     cand, label = _native.cand_draw(index.query_keys(q[:, 0], q[:, 1]).contiguous(), index.keys, index.ptr, index.tails, int(num_entities),
-                                    1 + int(num_neg), _native.dropout_key(seed, step, _native.CAND_DRAW_SITE), labels=labels)
+                                    1 + int(num_neg), key, labels=labels)
     return (cand, label) if labels else cand
 
 
@@ -134,7 +137,7 @@ def check_query_keys(queries, index):
 
 
 def train_sampled_negatives(model, queries, index, graph, optimizer, params, batch_size, num_neg, generator=None, draw_seed=None,
-                            first_step=0, loss='bce'):
+                            first_step=0, loss='bce', captured=None):
     """One epoch like train_device_labels' eager loop, on sampled negatives: per step the candidate lists of
     sample_candidates (one known tail + num_neg uniform ids per query) and MGCN.forward_loss_candidates over them, so that no
     step touches a [B, N] block. `generator`: a CPU generator (or None: the default one) shuffles as train_device_labels does and
@@ -144,8 +147,16 @@ def train_sampled_negatives(model, queries, index, graph, optimizer, params, bat
     draw_candidates(..., draw_seed, first_step + i, labels=True) instead; `generator` then only shuffles, no generator is made on
     the device, and the lists do not depend on any RNG state. A caller that trains several epochs passes the steps done so far as
     first_step (a checkpoint stores draw_seed and that count).
-    loss: 'bce' or 'softmax', handed to forward_loss_candidates (the softmax cross-entropy over each list)."""
+    loss: 'bce' or 'softmax', handed to forward_loss_candidates (the softmax cross-entropy over each list).
+    captured: a captured.CapturedCandidateStep built for this model, graph, index and optimizer (or True: one is built with
+    params.lbl_smooth / params.clip_grad and kept on the model for the following epochs); needs draw_seed. Every step is then one
+    call of it (a replay of the captured step once it is warm), its draw_seed / num_neg / loss are set from the arguments and its
+    draw_step to first_step, the per-step losses stay on the device, and the epoch reads them ONCE at its end into the same
+    RunningAverage. None (the default): the loop below, unchanged."""
     kind = loss             # (`loss` below is a step's result)
+    if captured is not None and captured is not False and draw_seed is None:
+        from . import _native
+        raise _native.NativeError('train_sampled_negatives: a captured step draws its lists from (draw_seed, step): give draw_seed')
     model.train()
     loss_avg = RunningAverage()
     dev = torch.device(params.device)
@@ -161,6 +172,17 @@ def train_sampled_negatives(model, queries, index, graph, optimizer, params, bat
         sample_candidates(queries, index, n_ent, 0, generator=generator)      # every query has a key: checked once, not per step
     else:
         check_query_keys(queries, index)
+    if captured is not None and captured is not False:
+        step = _captured_cand_step(model, graph, index, optimizer, params) if captured is True else captured
+        step.num_neg, step.loss, step.draw_seed, step.draw_step = int(num_neg), kind, int(draw_seed), int(first_step)
+        starts = range(0, queries.size(0), batch_size)
+        losses = torch.empty(len(starts), dtype=torch.float32, device=dev)
+        for k, i in enumerate(starts):
+            q = queries.index_select(0, order[i:i + batch_size])
+            losses[k].copy_(step(q[:, 0], q[:, 1]))     # (the step's loss tensor is overwritten by the next call)
+        for v in losses.tolist():                        # the epoch's one host read
+            loss_avg.update(v)
+        return loss_avg()
     for k, i in enumerate(range(0, queries.size(0), batch_size)):
         q = queries.index_select(0, order[i:i + batch_size])
         if draw_seed is None:
@@ -188,6 +210,18 @@ def _captured_step(model, graph, index, optimizer, params):
     if hit is None or hit.graph is not graph or hit.index is not index or hit.optimizer is not optimizer:
         hit = CapturedTrainStep(model, graph, index, optimizer)
         object.__setattr__(model, '_captured_train_step', hit)
+    hit.lbl_smooth, hit.clip = float(params.lbl_smooth), params.clip_grad
+    return hit
+
+
+def _captured_cand_step(model, graph, index, optimizer, params):
+    """The CapturedCandidateStep of train_sampled_negatives(captured=True): built once per (graph, index, optimizer) and kept on
+    the model; the epoch sets its num_neg, loss, draw_seed and draw_step."""
+    from .captured import CapturedCandidateStep
+    hit = getattr(model, '_captured_cand_train_step', None)
+    if hit is None or hit.graph is not graph or hit.index is not index or hit.optimizer is not optimizer:
+        hit = CapturedCandidateStep(model, graph, index, optimizer, 0, 0)
+        object.__setattr__(model, '_captured_cand_train_step', hit)
     hit.lbl_smooth, hit.clip = float(params.lbl_smooth), params.clip_grad
     return hit
 
