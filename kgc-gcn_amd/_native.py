@@ -1373,7 +1373,8 @@ def conve_train_fwd(geom, s, r, conv_w, conv_b, fc_w, fc_b, bn0, bn1, keep, inv_
 
 def conve_train_bwd(geom, s, r, conv_w, fc_w, bn0_weight, bn0_bias, bn1_weight, bn1_bias, keep, inv_keep, saved, ws, gz, want):
     """The gradients named in `want` (a set of 's', 'r', 'conv_w', 'conv_b', 'g0', 'b0', 'g1', 'b1', 'fc_w', 'fc_b') as a
-    dict; `ws` is the forward's workspace, untouched."""
+    dict; `ws` is the forward's workspace: its first section c [B, F H W] is read and keeps its bits, every later section is this
+    call's scratch and is overwritten (include/mgcn_hip.h (9)), with the same bits whenever the call is repeated on the same inputs."""
     geom = tuple(int(v) for v in geom)
     k_w, k_h, ks, F, O = geom
     B = int(s.size(0))

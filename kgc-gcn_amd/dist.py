@@ -491,7 +491,8 @@ def _mm_tn(a, b):
 
 class _ShardAggregateFn(torch.autograd.Function):
     """In / out aggregates [n1 - n0, 2D] of this rank's destinations from its table shard; backward by mgcn_aggregate_bwd_shard
-    (gee complete, grel and gx partial: the ranks' sums add up)."""
+    (gee complete, grel and gx partial: the ranks' sums add up). The incoming gradient goes through .contiguous(): a contiguous
+    one is passed through, every other layout is copied."""
 
     @staticmethod
     def forward(ctx, x, rels, ee_shard, csr, n0, n1):
@@ -515,7 +516,8 @@ class _ShardLayerTrainFn(torch.autograd.Function):
     csrc/train_layer.hip (4s) and every rank's per-block partials are all-gathered between them (forward: column sums, then
     centred sums; backward: the g_pre / g_pre * xhat sums). Dropout keep-masks are the rank's own for its rows, or, with
     `drop_keys` = (key_in, key_out, row0 = n0), the counter-based ones of csrc/dropout.hip: the bits of the GLOBAL rows, the same
-    on any partition, recomputed in the backward instead of saved."""
+    on any partition, recomputed in the backward instead of saved. The incoming gradient goes through .contiguous(): a contiguous
+    one is passed through, every other layout is copied."""
 
     @staticmethod
     def forward(ctx, agg, a_loop, w_in, w_out, w_loop, bias, gamma, beta, running_mean, running_var, momentum, eps, p_drop, ex,
@@ -577,7 +579,9 @@ class _ShardLayerTrainFn(torch.autograd.Function):
 
 class _GatherRowsFn(torch.autograd.Function):
     """Layer output rows -> [N, O] on every rank. Backward: the rank's rows of the incoming gradient, all-reduced first when it
-    holds partials (`reduce`: a layer the next layer reads, whose gx is a partial [N, O] on every rank)."""
+    holds partials (`reduce`: a layer the next layer reads, whose gx is a partial [N, O] on every rank). The incoming gradient
+    goes through .contiguous(): a contiguous one is passed through (and, with `reduce` on more than one rank, all-reduced in
+    place), every other layout is copied."""
 
     @staticmethod
     def forward(ctx, y, ex, reduce):
@@ -596,7 +600,8 @@ class _GatherRowsFn(torch.autograd.Function):
 
 
 class _AllReduceGradFn(torch.autograd.Function):
-    """Identity; the gradient is summed over the ranks (d x_trunk = sum_r G_r^T ent_r: each rank scores its own entities)."""
+    """Identity; the gradient is summed over the ranks (d x_trunk = sum_r G_r^T ent_r: each rank scores its own entities).
+    The incoming gradient is always copied, whatever its layout: the result is a contiguous tensor with a storage of its own."""
 
     @staticmethod
     def forward(ctx, x, ex):
@@ -611,7 +616,8 @@ class _AllReduceGradFn(torch.autograd.Function):
 
 class _RankZeroGradFn(torch.autograd.Function):
     """Identity; only rank 0 passes the gradient on: a gradient that every rank computes in full (a replicated computation on
-    complete inputs) joins partial ones, and the sum over the ranks must count it once."""
+    complete inputs) joins partial ones, and the sum over the ranks must count it once. The incoming gradient is passed through
+    as it is on rank 0, in any layout; no kernel reads it."""
 
     @staticmethod
     def forward(ctx, x, ex):
@@ -625,7 +631,7 @@ class _RankZeroGradFn(torch.autograd.Function):
 
 class _ScoreBCEShardFn(torch.autograd.Function):
     """model._ScoreBCEFn on this rank's entity rows: the mean runs over B x the GLOBAL entity count, so the ranks' losses and
-    gradients add up to the whole table's."""
+    gradients add up to the whole table's. The incoming scalar gradient is handled as in model._ScoreBCEFn."""
 
     @staticmethod
     def forward(ctx, x, ent, bias, mask, hot, cold, num_entities):
@@ -642,7 +648,8 @@ class _ScoreBCEShardFn(torch.autograd.Function):
 class _CandBCEShardFn(torch.autograd.Function):
     """model._CandBCEFn on this rank's entity rows [row0, row0 + ent.size(0)) (include/mgcn_hip.h (14), the ent_row0 / n_local
     form): list positions whose id another rank owns are dead here, they write g = 0, add no loss term and still count in the
-    divisor B K, so the ranks' losses and d x add up to the one-rank step's; d ent and d bias are the rank's rows, complete."""
+    divisor B K, so the ranks' losses and d x add up to the one-rank step's; d ent and d bias are the rank's rows, complete.
+    The incoming scalar gradient is handled as in model._CandBCEFn."""
 
     @staticmethod
     def forward(ctx, x, ent, bias, cand, label, hot, cold, row0):
@@ -670,7 +677,7 @@ class _CandCEShardFn(torch.autograd.Function):
     merged the chunks), and the finish with the global statistics. The rank's loss is the sum of its own positions' terms, so
     the ranks' losses and d x add up to the one-rank step's; d ent and d bias are the rank's rows, complete. A rank without
     rows contributes the empty statistic and joins the all-gather. With one rank there is no collective and no second merge:
-    model._CandCEFn's launches."""
+    model._CandCEFn's launches. The incoming scalar gradient is handled as in model._CandBCEFn."""
 
     @staticmethod
     def forward(ctx, x, ent, bias, cand, label, eps, row0, ex):

@@ -54,7 +54,8 @@ def _word_of(drop_ctx):
 
 
 class _AggregateFn(torch.autograd.Function):
-    """A[:, :D] / A[:, D:2D] = in-/out-half aggregates; gradients by the HIP backward kernels."""
+    """A[:, :D] / A[:, D:2D] = in-/out-half aggregates; gradients by the HIP backward kernels.
+    The incoming gradient goes through .contiguous(): a contiguous one is passed through, every other layout is copied."""
 
     @staticmethod
     def forward(ctx, x, rel, ee_slot, csr):
@@ -79,7 +80,8 @@ class _LayerTrainFn(torch.autograd.Function):
     backward on the two-stage reduction kernels of csrc/train_layer.hip; the running statistics are updated in place.
     Dropout masks come from torch's generator (Bernoulli keep-masks scaled by 1 / keep, as F.dropout), or, with `drop_keys` =
     (key_in, key_out, row0), from the counter-based definition of csrc/dropout.hip: one pair launch in place on the
-    two products, no mask saved, and one pair launch in the backward that forms both gradients from gu."""
+    two products, no mask saved, and one pair launch in the backward that forms both gradients from gu.
+    The incoming gradient is taken in any layout (_native._bn_grad): a contiguous one is passed through, every other one is copied."""
 
     @staticmethod
     def forward(ctx, agg, a_loop, w_in, w_out, w_loop, bias, gamma, beta, running_mean, running_var, momentum, eps, p_drop,
@@ -140,7 +142,9 @@ class _TrunkTrainFn(torch.autograd.Function):
     """Training-mode ConvE trunk from the gathered rows to the fc output (model.py:164-171 under .train()) on the kernels of
     csrc/conve_train.hip: z = fc(feature_drop(relu(bn1(conv_e(bn0(image(s, r))))))) with batch statistics, and its backward.
     Saves the workspace that holds the pre-BN convolution output c, the bool keep-mask (1 byte per element, scaled by
-    1 / keep at use) and the batch statistics; the running statistics of bn0 / bn1 are updated in place."""
+    1 / keep at use) and the batch statistics; the running statistics of bn0 / bn1 are updated in place.
+    The incoming gradient is passed through when its last stride is 1 and its rows are at least O apart (contiguous, row windows,
+    column windows at any offset); transposed and expanded ones (row stride 0) are copied."""
 
     @staticmethod
     def forward(ctx, s, r, conv_w, conv_b, fc_w, fc_b, g0, b0, g1, b1, bn0_stats, bn1_stats, keep, inv_keep, geom):
@@ -157,7 +161,9 @@ class _TrunkTrainFn(torch.autograd.Function):
         want = {n for i, n in enumerate(names) if ctx.needs_input_grad[i]}
         want -= set() if ctx.has_conv_bias else {'conv_b'}
         want -= set() if ctx.has_fc_bias else {'fc_b'}
-        gz = gz if gz.stride(-1) == 1 else gz.contiguous()
+        # rows at least O apart, the rule of _QueryRowsFn / _TrunkTailFn: a row-expanded gradient (strides (0, 1), what a
+        # y.sum(0) downstream hands over) has a unit last stride and a leading dimension of 0, which the kernels refuse
+        gz = gz if (gz.stride(1) == 1 and gz.stride(0) >= gz.size(1)) else gz.contiguous()
         g = _native.conve_train_bwd(ctx.geom, s, r, conv_w, fc_w, g0, b0, g1, b1, keep, ctx.inv_keep, saved, ws, gz, want)
         return tuple(g.get(n) for n in names) + (None,) * 5
 
@@ -165,7 +171,8 @@ class _TrunkTrainFn(torch.autograd.Function):
 class _QueryRowsFn(torch.autograd.Function):
     """table[idx] (model.py:35-36). The forward stays torch.index_select (a copy); the backward is the fixed-order row sum of
     csrc/query_train.hip, bit for bit the sequential loop d table[idx[b]] += g[b] in ascending b, instead of index_add_'s float
-    atomics."""
+    atomics. The incoming gradient is passed through when its last stride is 1 and its rows are at least dim apart (contiguous,
+    row windows, column windows at any offset); transposed and expanded ones are copied."""
 
     @staticmethod
     def forward(ctx, table, idx):
@@ -183,7 +190,9 @@ class _QueryRowsFn(torch.autograd.Function):
 class _TrunkTailFn(torch.autograd.Function):
     """The trunk's tail x = relu(bn2(z keep inv_keep)) with batch statistics (model.py:173-175 under .train()) on the kernels of
     csrc/query_train.hip, one launch forward and one backward. Saves z, the bool keep-mask, the batch statistics and the output
-    (the backward reads the relu mask from it); bn2's running statistics are updated in place."""
+    (the backward reads the relu mask from it); bn2's running statistics are updated in place.
+    The incoming gradient is passed through when its last stride is 1 and its rows are at least O apart (contiguous, row windows,
+    column windows at any offset); transposed and expanded ones are copied."""
 
     @staticmethod
     def forward(ctx, z, gamma, beta, running_mean, running_var, momentum, eps, keep, inv_keep):
@@ -245,7 +254,9 @@ def edge_table_dtype(params):
 
 class _CounterDropoutFn(torch.autograd.Function):
     """Dropout of a matrix [rows, cols] whose keep bits are the counter-based ones of csrc/dropout.hip: a pure
-    function of (key, row0 + row, col). Forward and backward are the same launch; nothing is saved but the scalars."""
+    function of (key, row0 + row, col). Forward and backward are the same launch; nothing is saved but the scalars.
+    The incoming gradient is passed through where _native.dropout_supported takes it (last stride 1, rows at least cols apart:
+    contiguous, row and column windows; a misaligned one takes the kernel's scalar path); transposed and expanded ones are copied."""
 
     @staticmethod
     def forward(ctx, x, key, row0, p):
@@ -281,7 +292,9 @@ def candidate_counts(scores, cand, obj, target):
 
 
 class _ScoreFn(torch.autograd.Function):
-    """sigmoid(x @ ent^T + bias): forward and both backward products on the HIP f32 MFMA tile kernel."""
+    """sigmoid(x @ ent^T + bias): forward and both backward products on the HIP f32 MFMA tile kernel.
+    The incoming gradient is read by torch's elementwise gs * s * (1 - s) in any layout; the kernels see that product's contiguous
+    result only."""
 
     @staticmethod
     def forward(ctx, x, ent, bias):
@@ -308,7 +321,9 @@ class _ScoreFn(torch.autograd.Function):
 class _ScoreBCEFn(torch.autograd.Function):
     """mean BCE(sigmoid(x @ ent^T + bias), targets) in ONE launch: the scores and the [B, N] targets are
     never materialised; the launch leaves d loss / d logits [N, B], the backward is two products on the HIP MFMA kernels
-    (G x on the tile kernel, G^T ent on the split-K transposed kernel) and a row sum."""
+    (G x on the tile kernel, G^T ent on the split-K transposed kernel) and a row sum.
+    The incoming gradient is a scalar (a Python-scalar loss weight arrives as a 0-dim tensor, in any 0-dim view): it multiplies the
+    three results by broadcasting and reaches no kernel."""
 
     @staticmethod
     def forward(ctx, x, ent, bias, mask, hot, cold):
@@ -331,7 +346,9 @@ class _ScoreBCEFn(torch.autograd.Function):
 class _CandBCEFn(torch.autograd.Function):
     """mean BCE over per-query candidate lists (include/mgcn_hip.h (14)): one launch leaves the loss partials and d loss / d logit
     [B, K]; the backward is two fixed-order sums on the kernels of csrc/query_train.hip, d x over the gathered entity rows and
-    d ent / d bias over the runs of a sorted plan into a zeroed block. Nothing of size [B, N] exists; no float atomics."""
+    d ent / d bias over the runs of a sorted plan into a zeroed block. Nothing of size [B, N] exists; no float atomics.
+    The incoming gradient is a scalar in any 0-dim view: it is folded into g [B, K] by broadcasting (g * gl, a fresh contiguous
+    tensor) and reaches no kernel itself."""
 
     @staticmethod
     def forward(ctx, x, ent, bias, cand, label, hot, cold):
@@ -358,7 +375,7 @@ class _CandBCEFn(torch.autograd.Function):
 class _CandCEFn(torch.autograd.Function):
     """softmax cross-entropy over per-query candidate lists (include/mgcn_hip.h (16)): logits and per-chunk statistics, their
     merge per row, then d loss / d logit [B, K] and the loss partials; the backward is _CandBCEFn's, on that g. `eps` smooths
-    over the list. Nothing of size [B, N] exists; no float atomics."""
+    over the list. Nothing of size [B, N] exists; no float atomics. The incoming scalar gradient is handled as in _CandBCEFn."""
 
     @staticmethod
     def forward(ctx, x, ent, bias, cand, label, eps):
