@@ -1023,6 +1023,51 @@ int mgcn_cand_ce_finish(int32_t batch, int64_t n_cand, int64_t n_local, int64_t 
                         const int64_t *cand_dev, int64_t ldc, const uint8_t *label_dev, int64_t ldl, const float *stat_dev,
                         float lbl_smooth, float inv_batch, float *g_dev, int64_t ldg, float *loss_partial_dev, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (17) Weighted candidate lists: negatives drawn by entity weight through an alias table (csrc/csr_build.cpp builds the table,
+ * csrc/dropout.hip draws) — additive, MGCN_ABI_VERSION stays 4. The draw of (15) with one more operand: the key,
+ * the Philox counter layout (one call per two positions), column 0 (the known tail), the optional labels and every check are
+ * those of (15); only the id of a negative changes. Integers only: a pure function of (seed, step, global batch row, list
+ * position), of the index and of the table; the same bits on any rank, at any launch geometry, eager or replayed.
+ *
+ * THE TABLE. table[n] (n < num_entities) is one int64 word, alias[n] << 32 | thr[n]: thr a 32-bit threshold, alias in
+ * [0, num_entities). mgcn_alias_build_host builds it on the CPU from int64 weights w[n] in [0, 2^32), W = sum w >= 1, by Vose's
+ * method on the integers m[n] = w[n] * num_entities compared against W (64-bit; the threshold's product is 128-bit; no floating
+ * point anywhere):
+ *   - an entry with m == W is finished: thr = 0xffffffff, alias = n (both branches of the draw return n);
+ *   - the smalls (m < W) wait in a FIFO that starts as their ascending ids; the larges (m > W) are taken in ascending id;
+ *   - the small s at the head of the FIFO gets thr[s] = floor(m[s] * 2^32 / W) and alias[s] = L, the current large, which loses
+ *     exactly W - m[s]; if that leaves m[L] == W it is finished as above, if it leaves m[L] < W it joins the BACK of the FIFO;
+ *     in both cases the next large in ascending id becomes current. Sums are exact, so the FIFO and the larges run out together.
+ *   The table realises cnt[n] = thr[n] + the sum of (2^32 - thr[m]) over every m with alias[m] == n (m == n included), and
+ *   Q(n) = cnt[n] / (num_entities * 2^32), an exact rational: sum cnt = num_entities * 2^32, w[n] == 0 gives cnt[n] == 0, and
+ *   |cnt[n] W - w[n] num_entities 2^32| <= (1 + indeg[n]) W. Equal weights give n << 32 | 0xffffffff.
+ *   MGCN_EINVAL, nothing written: a null pointer, num_entities outside [1, 2^31 - 1], a weight outside [0, 2^32), W == 0.
+ *
+ * THE DRAW. For j >= 1, with the r of (15): slot = (r * num_entities) >> 64, the high half of the 128-bit product; u = the upper
+ * 32 bits of the LOW half of the same product (the position inside the slot: no second random word is spent); t = table[slot],
+ * one 8-byte load; id = u < uint32(t) ? slot : uint64(t) >> 32; an alias at or above num_entities is written as -1 (a dead
+ * position of (14) / (16)). slot < num_entities always and the alias is compared before it is written: a corrupt table yields
+ * dead positions downstream, never an address. With the equal-weights table the block is that of mgcn_cand_draw, bit for bit.
+ * mgcn_cand_draw_alias / _dev / _host are mgcn_cand_draw / _dev / _host with table [num_entities] after n_tails: the same grid
+ * rule (at most 2048 workgroups of 256 threads over (b, j >> 1)), no LDS, no atomics, plain vector stores; n_cand == 1 never
+ * reads the table. MGCN_EINVAL on top of (15)'s cases, nothing launched and nothing written: a null table, a table not aligned
+ * to 8 bytes, num_entities > 2^31 - 1. NOT MEASURED: the kernel's own time (DESIGN §4.15 times the call).
+ */
+int mgcn_alias_build_host(int64_t num_entities, const int64_t *w_host, int64_t *table_host);
+int mgcn_cand_draw_alias(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
+                         const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails,
+                         const int64_t *table_dev, uint64_t key, uint64_t row0, int64_t *cand_dev, int64_t ldc, uint8_t *label_dev,
+                         int64_t ldl, void *stream);
+int mgcn_cand_draw_alias_dev(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
+                             const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails,
+                             const int64_t *table_dev, const uint64_t *step_key_dev, uint64_t site, uint64_t row0, int64_t *cand_dev,
+                             int64_t ldc, uint8_t *label_dev, int64_t ldl, void *stream);
+int mgcn_cand_draw_alias_host(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_host, int64_t num_keys,
+                              const int64_t *keys_host, const int64_t *ptr_host, const int32_t *tails_host, int64_t n_tails,
+                              const int64_t *table_host, uint64_t key, uint64_t row0, int64_t *cand_host, int64_t ldc,
+                              uint8_t *label_host, int64_t ldl);
+
 #ifdef __cplusplus
 }
 #endif

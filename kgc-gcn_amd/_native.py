@@ -132,6 +132,11 @@ _SIGNATURES = {
     'mgcn_cand_draw': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _u64, _u64, _ptr, _i64, _ptr, _i64, _ptr]),
     'mgcn_cand_draw_dev': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64, _ptr]),
     'mgcn_cand_draw_host': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _u64, _u64, _ptr, _i64, _ptr, _i64]),
+    'mgcn_alias_build_host': (ctypes.c_int, [_i64, _ptr, _ptr]),
+    'mgcn_cand_draw_alias': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64, _ptr]),
+    'mgcn_cand_draw_alias_dev': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64,
+                                                _ptr]),
+    'mgcn_cand_draw_alias_host': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
     'mgcn_ingest_count': (_i64, [_ptr, _i32]),
@@ -1776,7 +1781,7 @@ def dropout_mask_host(rows, cols, key, row0, p):
 CAND_DRAW_SITE = 0x2000
 
 
-def _cand_draw(fn, what, on_gpu, qkey, keys, ptr, tails, num_entities, n_cand, key, row0, labels, out):
+def _cand_draw(fn, what, on_gpu, qkey, keys, ptr, tails, num_entities, n_cand, key, row0, labels, out, table=None):
     B, K = qkey.numel(), int(n_cand)
     dev = qkey.device
     if dev.type != ('cuda' if on_gpu else 'cpu'):
@@ -1793,7 +1798,9 @@ def _cand_draw(fn, what, on_gpu, qkey, keys, ptr, tails, num_entities, n_cand, k
     dev_key = isinstance(key, DeviceKey)
     if dev_key and not on_gpu:
         raise NativeError('%s: a DeviceKey is for the GPU launch' % what)
-    _same_device(qkey, keys, ptr, tails, cand, label, key.word if dev_key else None)
+    _same_device(qkey, keys, ptr, tails, cand, label, key.word if dev_key else None, table)
+    if table is not None and (table.dtype != torch.int64 or table.dim() != 1 or table.numel() != int(num_entities) or not table.is_contiguous()):
+        raise NativeError('%s: table must be a contiguous int64 [%d] (sampling.NegativeSampler.table)' % (what, int(num_entities)))
 
     def block(t, dtype, name):
         if t.dim() != 2 or tuple(t.shape) != (B, K) or (t.dtype != dtype and not (dtype == torch.uint8 and t.dtype == torch.bool)) \
@@ -1811,27 +1818,45 @@ def _cand_draw(fn, what, on_gpu, qkey, keys, ptr, tails, num_entities, n_cand, k
     lp, ldl = (block(label, torch.uint8, 'label') if K >= 1 else (label.data_ptr(), 0)) if label is not None else (None, 0)
     args = [B, K, int(num_entities), arr(qkey, torch.int64, 'qkey') if B else qkey.new_zeros(1).data_ptr(), keys.numel(),
             arr(keys, torch.int64, 'keys'), arr(ptr, torch.int64, 'ptr'), arr(tails, torch.int32, 'tails'), tails.numel(),
-            ] + ([key.word.data_ptr(), key.site] if dev_key else [int(key) & _M64]) + [int(row0) & _M64, cp, ldc, lp, ldl]
+            ] + ([table.data_ptr()] if table is not None else []) + ([key.word.data_ptr(), key.site] if dev_key else [int(key) & _M64]) + [int(row0) & _M64, cp, ldc, lp, ldl]
     _check(fn(*(args + ([_stream(cand)] if on_gpu else []))), what)
     return cand, label
 
 
-def cand_draw(qkey, keys, ptr, tails, num_entities, n_cand, key, row0=0, labels=True, out=None):
+def cand_draw(qkey, keys, ptr, tails, num_entities, n_cand, key, row0=0, labels=True, out=None, table=None):
     """(15) (cand [B, n_cand] int64, label [B, n_cand] uint8 or None): the candidate lists of the queries with keys qkey [B] under
     `key` (dropout_key(seed, step, CAND_DRAW_SITE); or a DeviceKey(word, CAND_DRAW_SITE), whose word on the tensors' device holds
     dropout_step_key(seed, step) when the kernel RUNS: mgcn_cand_draw_dev, what a captured launch needs), row b being global batch row row0 + b. Column 0 is one known tail of the query
     drawn from its run in the keys / ptr / tails arrays of filter_mask() (-1 for a query without one), the other columns are ids
     in [0, num_entities); label is cand_labels() of the drawn list against the whole table. One launch (see mgcn_cand_draw).
-    out: a cand tensor, or (cand, label), to write into (padded row views are fine)."""
+    out: a cand tensor, or (cand, label), to write into (padded row views are fine).
+    table (None: the uniform draw above, unchanged): an alias table [num_entities] int64 on the tensors' device
+    (sampling.NegativeSampler.table): (17), the negatives follow the table's distribution (mgcn_cand_draw_alias / _alias_dev);
+    an alias outside the table is written as -1."""
+    tag = '' if table is None else '_alias'
     if isinstance(key, DeviceKey):
-        return _cand_draw(lib().mgcn_cand_draw_dev, 'mgcn_cand_draw_dev', True, qkey, keys, ptr, tails, num_entities, n_cand, key, row0, labels, out)
-    return _cand_draw(lib().mgcn_cand_draw, 'mgcn_cand_draw', True, qkey, keys, ptr, tails, num_entities, n_cand, key, row0, labels, out)
+        what = 'mgcn_cand_draw%s_dev' % tag
+    else:
+        what = 'mgcn_cand_draw%s' % tag
+    return _cand_draw(getattr(lib(), what), what, True, qkey, keys, ptr, tails, num_entities, n_cand, key, row0, labels, out, table)
 
 
-def cand_draw_host(qkey, keys, ptr, tails, num_entities, n_cand, key, row0=0, labels=True, out=None):
-    """(15) cand_draw on CPU tensors, from the same inline function the kernel calls: test infrastructure."""
-    return _cand_draw(lib().mgcn_cand_draw_host, 'mgcn_cand_draw_host', False, qkey, keys, ptr, tails, num_entities, n_cand, key, row0,
-                      labels, out)
+def cand_draw_host(qkey, keys, ptr, tails, num_entities, n_cand, key, row0=0, labels=True, out=None, table=None):
+    """(15) / (17) cand_draw on CPU tensors, from the same inline function the kernel calls: test infrastructure."""
+    what = 'mgcn_cand_draw_host' if table is None else 'mgcn_cand_draw_alias_host'
+    return _cand_draw(getattr(lib(), what), what, False, qkey, keys, ptr, tails, num_entities, n_cand, key, row0, labels, out, table)
+
+
+def alias_build_host(w):
+    """(17) The alias table [N] int64 (alias << 32 | threshold) of the int64 weights w [N] in [0, 2^32), built on the CPU in exact
+    integers (mgcn_alias_build_host). A host tensor; what sampling.NegativeSampler wraps."""
+    w = w.detach().to('cpu', torch.int64).contiguous()
+    if w.dim() != 1:
+        raise NativeError('alias_build_host: w must be an int64 [N]')
+    table = torch.empty(w.numel(), dtype=torch.int64)
+    _check(lib().mgcn_alias_build_host(w.numel(), w.data_ptr() if w.numel() else None, table.data_ptr() if w.numel() else None),
+           'mgcn_alias_build_host')
+    return table
 
 
 class IngestUnsupported(NativeError):

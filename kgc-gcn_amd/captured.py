@@ -321,9 +321,11 @@ class CapturedCandidateStep(CapturedTrainStep):
 
     _WORDS = 2     # the dropout step word, then the draw word
 
-    def __init__(self, model, graph, index, optimizer, num_neg, draw_seed, draw_step=0, loss='bce', lbl_smooth=0.0, clip=None, warmup=2):
+    def __init__(self, model, graph, index, optimizer, num_neg, draw_seed, draw_step=0, loss='bce', lbl_smooth=0.0, clip=None, warmup=2,
+                 sampler=None):
         super().__init__(model, graph, index, optimizer, lbl_smooth=lbl_smooth, clip=clip, warmup=warmup)
         self.num_neg, self.draw_seed, self.draw_step, self.loss = num_neg, int(draw_seed), int(draw_step), loss
+        self.sampler = sampler
         self.cand = None
 
     def _body(self, src, rel):
@@ -333,9 +335,10 @@ class CapturedCandidateStep(CapturedTrainStep):
         word = self._stage.words[1:2] if m._step_key_dev is not None else None
         opt.zero_grad(set_to_none=True)
         cand, labels = draw_candidates(torch.stack((src.reshape(-1), rel.reshape(-1)), 1), self.index, m.entity_embedding.size(0), self.num_neg,
-                                       self.draw_seed, self.draw_step, labels=True, step_key_dev=word)
+                                       self.draw_seed, self.draw_step, labels=True, step_key_dev=word, sampler=self.sampler)
         self.draw_step += 1
-        loss = m.forward_loss_candidates(src, rel, cand, self.graph, labels=labels, lbl_smooth=self.lbl_smooth, loss=self.loss)
+        logq = self.sampler.logq if self.sampler is not None and self.loss == 'softmax' else None
+        loss = m.forward_loss_candidates(src, rel, cand, self.graph, labels=labels, lbl_smooth=self.lbl_smooth, loss=self.loss, logq=logq)
         loss.backward()
         opt.clip_and_step(self.clip)
         self.cand = cand
@@ -354,6 +357,10 @@ class CapturedCandidateStep(CapturedTrainStep):
         dev = self.model.entity_embedding.device
         if any(t.device != dev for t in (self.index.keys, self.index.ptr, self.index.tails)):
             raise _native.NativeError('CapturedCandidateStep: the index is not on the model\'s device (%s)' % (dev,))
+        sm = self.sampler
+        if sm is not None and (sm.device != dev or sm.num_entities != self.model.entity_embedding.size(0)):
+            raise _native.NativeError('CapturedCandidateStep: the sampler must hold the model\'s %d entities on its device (%s)'
+                                      % (self.model.entity_embedding.size(0), dev))
 
     def _refuse_batch(self, src):
         if int(src.numel()) == 0:
@@ -361,7 +368,9 @@ class CapturedCandidateStep(CapturedTrainStep):
 
     def _key(self):
         ix = self.index       # (the parent's key holds the index tensors' addresses too: here the draw reads them as well)
-        return super()._key() + (self.num_neg, self.loss, ix.keys.data_ptr(), ix.ptr.data_ptr(), ix.tails.data_ptr())
+        sm = self.sampler     # (its tensors are persistent: their addresses are what the graph holds)
+        return super()._key() + (self.num_neg, self.loss, ix.keys.data_ptr(), ix.ptr.data_ptr(), ix.tails.data_ptr()) + \
+            (() if sm is None else (sm.table.data_ptr(), sm.logq.data_ptr()))
 
     def _stage_words(self, slot):
         slot.word[1] = _native.dropout_step_key(self.draw_seed, self.draw_step)
@@ -372,6 +381,8 @@ class CapturedCandidateStep(CapturedTrainStep):
             for labels in (True, False):
                 _native.cand_draw(one, one, torch.zeros(2, dtype=torch.int64, device=st.device), torch.zeros(1, dtype=torch.int32, device=st.device),
                                   1, 2, _native.DeviceKey(st.words[1:2], _native.CAND_DRAW_SITE), labels=labels)
+                _native.cand_draw(one, one, torch.zeros(2, dtype=torch.int64, device=st.device), torch.zeros(1, dtype=torch.int32, device=st.device),
+                                  1, 2, _native.DeviceKey(st.words[1:2], _native.CAND_DRAW_SITE), labels=labels, table=one)
         super()._warm_kernels(st)
 
     def _capture(self, src, rel, key):

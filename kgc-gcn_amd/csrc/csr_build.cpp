@@ -176,3 +176,53 @@ extern "C" int mgcn_csr_live_view_host(int64_t num_nodes, const int32_t *rowptr_
   }
   return MGCN_OK;
 }
+
+// The alias table of the weighted candidate draw (include/mgcn_hip.h (17)): Vose's method on the integers
+// m[n] = w[n] * N against W = sum w, no floating point. The pairing order is the header's: the smalls wait in a FIFO that starts
+// as the ascending ids with m < W, the larges are taken in ascending id; the small at the head is filled up by the current large,
+// which loses exactly W - m; a large that drops below W joins the BACK of the FIFO, one that lands on W is finished, and either
+// way the next large in ascending id takes over. m <= 2^63 and never grows, so it fits 64 bits; the threshold's product is 128-bit.
+extern "C" int mgcn_alias_build_host(int64_t num_entities, const int64_t *w_host, int64_t *table_host) {
+  const int64_t N = num_entities;
+  MGCN_REQUIRE(N >= 1 && N <= (int64_t(1) << 31) - 1, "mgcn_alias_build_host: num_entities = %lld outside [1, 2^31 - 1]", (long long)N);
+  MGCN_REQUIRE(w_host && table_host, "mgcn_alias_build_host: null pointer");
+  uint64_t W = 0;
+  for (int64_t n = 0; n < N; ++n) {
+    MGCN_REQUIRE(w_host[n] >= 0 && w_host[n] < (int64_t(1) << 32), "mgcn_alias_build_host: w[%lld] = %lld outside [0, 2^32)", (long long)n,
+                 (long long)w_host[n]);
+    W += uint64_t(w_host[n]);
+  }
+  MGCN_REQUIRE(W >= 1, "mgcn_alias_build_host: the weights sum to zero");
+  std::vector<uint64_t> m(N);
+  std::vector<int64_t> small;      // the FIFO: `head` walks it, demoted larges are appended
+  small.reserve(size_t(N));
+  for (int64_t n = 0; n < N; ++n) {
+    m[n] = uint64_t(w_host[n]) * uint64_t(N);
+    if (m[n] < W) small.push_back(n);
+  }
+  const uint64_t full = 0xffffffffull;
+  auto word = [](int64_t alias, uint64_t thr) { return int64_t(uint64_t(alias) << 32 | thr); };
+  auto next_large = [&](int64_t from) {
+    while (from < N && m[from] <= W) ++from;      // (an id that started at or below W is never a large)
+    return from;
+  };
+  // an entry that sits at W from the start is finished as it is
+  for (int64_t n = 0; n < N; ++n)
+    if (m[n] == W) table_host[n] = word(n, full);
+  size_t head = 0;
+  int64_t L = next_large(0);
+  while (head < small.size() && L < N) {
+    const int64_t s = small[head++];
+    table_host[s] = word(L, uint64_t((static_cast<unsigned __int128>(m[s]) << 32) / W));
+    m[L] -= W - m[s];
+    if (m[L] <= W) {
+      if (m[L] == W) table_host[L] = word(L, full); else small.push_back(L);
+      L = next_large(L + 1);
+    }
+  }
+  // exact integers leave nothing over (the remaining m always sum to W times their number); were it otherwise, an entry left
+  // here keeps its own id on both branches
+  for (; head < small.size(); ++head) table_host[small[head]] = word(small[head], full);
+  for (; L < N; L = next_large(L + 1)) table_host[L] = word(L, full);
+  return MGCN_OK;
+}

@@ -5,7 +5,8 @@
 // and leading dimensions allow it and takes the element-wise path otherwise (same bits). No atomics, no LDS, no inline assembly;
 // all index arithmetic is 64-bit.
 // The same Philox function also draws the candidate lists of sampled-negative training (include/mgcn_hip.h (15)):
-// mgcn_cand_draw, its device-key form and its host twin, at the end of the anonymous namespace.
+// mgcn_cand_draw, its device-key form and its host twin, at the end of the anonymous namespace, and their weighted forms
+// (include/mgcn_hip.h (17)), which read one alias-table word per negative.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -304,8 +305,30 @@ __host__ __device__ inline uint64_t mul_hi64(uint64_t r, uint64_t m) {
 #endif
 }
 
-// Positions 2 jp and 2 jp + 1 of row b. The ONE definition: draw_kernel and mgcn_cand_draw_host both call it.
-__host__ __device__ inline void draw_pair(const DrawArgs &a, int64_t b, int64_t jp) {
+// The id of a negative from its 64-bit value r. NoTable: uniform, the high half of r N. AliasTable (include/mgcn_hip.h (17)): the
+// high half is the slot, the upper 32 bits of the LOW half are the position inside the slot, and one 8-byte word of the table
+// (alias << 32 | threshold) decides between the slot and its alias. slot < N by construction; an alias outside [0, N) is written
+// as -1 and never followed.
+struct NoTable {};
+struct AliasTable {
+  const uint64_t *word;      // [num_entities]
+};
+
+__host__ __device__ inline int64_t negative_id(uint64_t r, uint64_t n, NoTable) { return int64_t(mul_hi64(r, n)); }
+
+__host__ __device__ inline int64_t negative_id(uint64_t r, uint64_t n, AliasTable t) {
+  const uint64_t slot = mul_hi64(r, n);
+  const uint32_t u = uint32_t((r * n) >> 32);
+  const uint64_t w = t.word[slot];
+  if (u < uint32_t(w)) return int64_t(slot);
+  const uint64_t alias = w >> 32;
+  return alias < n ? int64_t(alias) : int64_t(-1);
+}
+
+// Positions 2 jp and 2 jp + 1 of row b. The ONE definition: the draw kernels and the host twins all call it, T saying where a
+// negative's id comes from.
+template <class T>
+__host__ __device__ inline void draw_pair(const DrawArgs &a, T table, int64_t b, int64_t jp) {
   uint32_t w[4];
   dropout_words(a.key, a.row0 + uint64_t(b), uint32_t(jp), w);
   const uint64_t r[2] = {uint64_t(w[0]) | uint64_t(w[1]) << 32, uint64_t(w[2]) | uint64_t(w[3]) << 32};
@@ -331,7 +354,7 @@ __host__ __device__ inline void draw_pair(const DrawArgs &a, int64_t b, int64_t 
     if (j == 0)
       id = hi > lo ? int64_t(a.tails[lo + int64_t(mul_hi64(r[0], uint64_t(hi - lo)))]) : int64_t(-1);
     else
-      id = int64_t(mul_hi64(r[h], uint64_t(a.num_entities)));
+      id = negative_id(r[h], uint64_t(a.num_entities), table);
     a.cand[b * a.ldc + j] = id;
     if (a.label) {
       // the GLOBAL label, mgcn_cand_labels' for the shard [0, num_entities): the id is an entity and is found in the run
@@ -359,7 +382,22 @@ __global__ __launch_bounds__(TPB) void draw_kernel(int64_t batch, int32_t npairs
     int64_t b;
     int32_t jp;
     unit_of(u, npairs, b, jp);
-    draw_pair(a, b, jp);
+    draw_pair(a, NoTable(), b, jp);
+  }
+}
+
+// draw_kernel with the alias table of (17): the same units, the same grid rule, one more 8-byte load per negative
+template <bool KD>
+__global__ __launch_bounds__(TPB) void draw_alias_kernel(int64_t batch, int32_t npairs, DrawArgs a, const uint64_t *__restrict__ table,
+                                                         const uint64_t *__restrict__ step_key) {
+  const int64_t units = batch * npairs, stride = int64_t(gridDim.x) * TPB;
+  a.key = site_key<KD>(a.key, step_key);
+  const AliasTable t = {table};
+  for (int64_t u = int64_t(blockIdx.x) * TPB + threadIdx.x; u < units; u += stride) {
+    int64_t b;
+    int32_t jp;
+    unit_of(u, npairs, b, jp);
+    draw_pair(a, t, b, jp);
   }
 }
 
@@ -376,14 +414,32 @@ int check_draw(const char *what, int64_t batch, const DrawArgs &a) {
   return MGCN_OK;
 }
 
-// both device entries: step_key_dev == nullptr: a.key is the key (by value); otherwise it is the site id
-int draw_launch(const char *what, int64_t batch, const DrawArgs &a, const uint64_t *step_key_dev, void *stream) {
+// what the weighted forms check on top of check_draw: the table, and a table small enough for a 31-bit alias
+int check_table(const char *what, const DrawArgs &a, const int64_t *table) {
+  MGCN_REQUIRE(table && mgcn::aligned8(table), "%s: null or misaligned pointer (table: num_entities 64-bit words)", what);
+  MGCN_REQUIRE(a.num_entities <= (int64_t(1) << 31) - 1, "%s: num_entities = %lld above 2^31 - 1 (the alias is 31 bits)", what,
+               (long long)a.num_entities);
+  return MGCN_OK;
+}
+
+// the device entries: step_key_dev == nullptr: a.key is the key (by value); otherwise it is the site id. alias: the weighted forms,
+// table_dev their table
+int draw_launch(const char *what, int64_t batch, const DrawArgs &a, const uint64_t *step_key_dev, void *stream, bool alias = false,
+                const int64_t *table_dev = nullptr) {
   if (int rc = check_draw(what, batch, a)) return rc;
+  if (alias)
+    if (int rc = check_table(what, a, table_dev)) return rc;
   if (batch == 0) return MGCN_OK;
   const int32_t npairs = int32_t((a.n_cand + 1) / 2);
   const dim3 grid(grid_for(batch * npairs)), block(TPB);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (step_key_dev)
+  if (alias) {
+    const uint64_t *t = reinterpret_cast<const uint64_t *>(table_dev);
+    if (step_key_dev)
+      draw_alias_kernel<true><<<grid, block, 0, st>>>(batch, npairs, a, t, step_key_dev);
+    else
+      draw_alias_kernel<false><<<grid, block, 0, st>>>(batch, npairs, a, t, nullptr);
+  } else if (step_key_dev)
     draw_kernel<true><<<grid, block, 0, st>>>(batch, npairs, a, step_key_dev);
   else
     draw_kernel<false><<<grid, block, 0, st>>>(batch, npairs, a, nullptr);
@@ -417,7 +473,40 @@ extern "C" int mgcn_cand_draw_host(int64_t batch, int64_t n_cand, int64_t num_en
   if (int rc = check_draw("mgcn_cand_draw_host", batch, a)) return rc;
   const int64_t npairs = (n_cand + 1) / 2;
   for (int64_t b = 0; b < batch; ++b)
-    for (int64_t jp = 0; jp < npairs; ++jp) draw_pair(a, b, jp);
+    for (int64_t jp = 0; jp < npairs; ++jp) draw_pair(a, NoTable(), b, jp);
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_cand_draw_alias(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
+                                    const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails,
+                                    const int64_t *table_dev, uint64_t key, uint64_t row0, int64_t *cand_dev, int64_t ldc,
+                                    uint8_t *label_dev, int64_t ldl, void *stream) {
+  const DrawArgs a = {n_cand, num_entities, qkey_dev, num_keys, keys_dev, ptr_dev, tails_dev, n_tails, key, row0, cand_dev, ldc, label_dev, ldl};
+  return draw_launch("mgcn_cand_draw_alias", batch, a, nullptr, stream, true, table_dev);
+}
+
+extern "C" int mgcn_cand_draw_alias_dev(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
+                                        const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails,
+                                        const int64_t *table_dev, const uint64_t *step_key_dev, uint64_t site, uint64_t row0,
+                                        int64_t *cand_dev, int64_t ldc, uint8_t *label_dev, int64_t ldl, void *stream) {
+  const char *what = "mgcn_cand_draw_alias_dev";
+  if (int rc = check_step_key(what, step_key_dev)) return rc;
+  const DrawArgs a = {n_cand, num_entities, qkey_dev, num_keys, keys_dev, ptr_dev, tails_dev, n_tails, site, row0, cand_dev, ldc, label_dev, ldl};
+  return draw_launch(what, batch, a, step_key_dev, stream, true, table_dev);
+}
+
+extern "C" int mgcn_cand_draw_alias_host(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_host, int64_t num_keys,
+                                         const int64_t *keys_host, const int64_t *ptr_host, const int32_t *tails_host, int64_t n_tails,
+                                         const int64_t *table_host, uint64_t key, uint64_t row0, int64_t *cand_host, int64_t ldc,
+                                         uint8_t *label_host, int64_t ldl) {
+  const char *what = "mgcn_cand_draw_alias_host";
+  const DrawArgs a = {n_cand, num_entities, qkey_host, num_keys, keys_host, ptr_host, tails_host, n_tails, key, row0, cand_host, ldc, label_host, ldl};
+  if (int rc = check_draw(what, batch, a)) return rc;
+  if (int rc = check_table(what, a, table_host)) return rc;
+  const AliasTable t = {reinterpret_cast<const uint64_t *>(table_host)};
+  const int64_t npairs = (n_cand + 1) / 2;
+  for (int64_t b = 0; b < batch; ++b)
+    for (int64_t jp = 0; jp < npairs; ++jp) draw_pair(a, t, b, jp);
   return MGCN_OK;
 }
 

@@ -730,6 +730,26 @@ def _agreed_seed(group, device):
     return int(t.item())
 
 
+def broadcast_sampler(sampler, group=None, device=None):
+    """The sampling.NegativeSampler of rank 0 on every rank of `group`, once, ahead of training: the table is DATA, so no rank
+    depends on its own pow; nothing is exchanged per step afterwards. Rank 0 passes its sampler, the others pass
+    None (or anything: it is ignored). Two broadcasts, the length and then the table, on `device` (default: rank 0's sampler's
+    device there, the current GPU elsewhere); the result lives on that device. A collective. Without a process group: the
+    sampler itself."""
+    from .sampling import NegativeSampler
+    world, rank = _world_rank(group)
+    if world == 1:
+        return sampler if device is None else sampler.to(device)
+    if device is None:
+        device = sampler.device if rank == 0 and sampler is not None and sampler.device.type == 'cuda' else torch.device('cuda', torch.cuda.current_device())
+    src = dist.get_global_rank(group, 0) if group is not None else 0
+    n = torch.tensor([sampler.num_entities if rank == 0 else 0], dtype=torch.int64).to(device)
+    dist.broadcast(n, src=src, group=group)
+    table = sampler.table.to(device) if rank == 0 else torch.empty(int(n.item()), dtype=torch.int64, device=device)
+    dist.broadcast(table, src=src, group=group)
+    return NegativeSampler(table)
+
+
 def _world_rank(group):
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     return world, (dist.get_rank(group) if world > 1 else 0)
@@ -998,7 +1018,7 @@ def train_epoch_sharded(model, queries, index, graph, optimizer, params, batch_s
 
 
 def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer, labels=None, lbl_smooth=0.0, clip=None, group=None,
-                                  generator=None, loss='bce'):
+                                  generator=None, loss='bce', logq=None):
     """train_step_sharded on per-query candidate lists (MGCN.forward_loss_candidates) in place of the
     rank's whole entity shard: everything up to and including the ConvE trunk is train_step_sharded's (same refusals, same
     dropout rules, same collectives), then rank r scores only the list positions whose id lies in its rows [n0, n1). No
@@ -1015,10 +1035,18 @@ def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer
     loss = 'softmax': the softmax cross-entropy over each list instead (forward_loss_candidates(loss='softmax')):
     a row's maximum, sum and counts span the ranks, so the step makes one more collective, an all-gather of the [B, 4] row
     statistics (_CandCEShardFn); lbl_smooth is spread over the list; the ranks' losses add up as above.
+    logq (None: the above, unchanged): f32 [N] over the WHOLE table, sampling.NegativeSampler.logq on the device, softmax only
+    (forward_loss_candidates(logq=...)): the rank hands its scoring stage bias[n0:n1] - logq[n0:n1].
     Returns the global loss (0-dim tensor, detached)."""
     what = 'train_step_sharded_candidates'
     if loss not in ('bce', 'softmax'):
         raise _native.NativeError("%s: loss must be 'bce' or 'softmax', got %r" % (what, loss))
+    if logq is not None:
+        if loss != 'softmax':
+            raise _native.NativeError("%s: logq corrects the softmax only; loss='bce' takes weighted lists as they are" % what)
+        n = model.entity_embedding.size(0)
+        if logq.dtype != torch.float32 or tuple(logq.shape) != (n,) or logq.device != model.conv2.bias.device:
+            raise _native.NativeError('%s: logq must be f32 [%d] on %s' % (what, n, model.conv2.bias.device))
     if _native.is_ee16(model.edge_embeddings):      # (before the list is looked at: the refusal _sharded_trunk repeats)
         raise _native.NativeError('%s: this model holds its per-edge tables in bf16 (params.edge_table_dtype), '
                                   'which is inference-only' % what)
@@ -1031,6 +1059,8 @@ def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer
     n0, n1, W = ex.n0, ex.n1, ex.world
     if loss == 'softmax':       # (a rank without entity rows passes the empty statistic on: it joins the all-gather)
         bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]
+        if logq is not None:
+            bias = bias - (logq if W == 1 else logq[n0:n1])
         xt = xt if xt.stride(-1) == 1 else xt.contiguous()
         if labels is None:
             labels = _native.cand_labels(index.query_keys(src, rel), index.keys, index.ptr, index.tails, cand, n1 - n0, ent_row0=n0)
@@ -1048,13 +1078,16 @@ def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer
 
 
 def train_epoch_sharded_candidates(model, queries, index, graph, optimizer, params, batch_size, num_neg, draw_seed, first_step=0,
-                                   generator=None, group=None, loss='bce'):
+                                   generator=None, group=None, loss='bce', sampler=None):
     """One epoch of train_step_sharded_candidates on counter-drawn lists, as harness.train_sampled_negatives(draw_seed=...): the
     shuffle of train_epoch_sharded (`generator` seeded identically on every rank, or a seed the group agrees on), the key check
     once, and per step i the lists and global labels of harness.draw_candidates(q, index, N, num_neg, draw_seed, first_step + i,
     labels=True), drawn on every rank with no exchange. Every rank passes the same draw_seed and first_step (the steps done in
     earlier epochs; a checkpoint stores the two). Clips at params.clip_grad, smooths with params.lbl_smooth. Returns the mean of
-    the steps' global losses. loss: 'bce' or 'softmax', handed to every step."""
+    the steps' global losses. loss: 'bce' or 'softmax', handed to every step.
+    sampler (None: uniform negatives, unchanged): a sampling.NegativeSampler on the device, THE SAME TABLE ON EVERY RANK
+    (broadcast_sampler gives it): the negatives follow its table, and the softmax steps take its logq; nothing is exchanged per
+    step."""
     from .harness import check_query_keys, draw_candidates
     kind = loss             # (`loss` below is a step's result)
     from .utils import RunningAverage
@@ -1071,8 +1104,9 @@ def train_epoch_sharded_candidates(model, queries, index, graph, optimizer, para
     check_query_keys(queries, index)      # every query has a key: checked once, not per step
     for k, i in enumerate(range(0, queries.size(0), batch_size)):
         q = queries.index_select(0, order[i:i + batch_size])
-        cand, labels = draw_candidates(q, index, n_ent, num_neg, draw_seed, int(first_step) + k, labels=True)
+        cand, labels = draw_candidates(q, index, n_ent, num_neg, draw_seed, int(first_step) + k, labels=True, sampler=sampler)
         loss = train_step_sharded_candidates(model, graph, q[:, 0], q[:, 1], cand, index, optimizer, labels=labels,
-                                             lbl_smooth=params.lbl_smooth, clip=params.clip_grad, group=group, loss=kind)
+                                             lbl_smooth=params.lbl_smooth, clip=params.clip_grad, group=group, loss=kind,
+                                             logq=sampler.logq if sampler is not None and kind == 'softmax' else None)
         loss_avg.update(loss.item())
     return loss_avg()

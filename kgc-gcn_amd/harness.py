@@ -106,7 +106,7 @@ def sample_candidates(q, index, num_entities, num_neg, generator=None, check=Tru
     return cand
 
 
-def draw_candidates(q, index, num_entities, num_neg, seed, step, labels=False, step_key_dev=None):
+def draw_candidates(q, index, num_entities, num_neg, seed, step, labels=False, step_key_dev=None, sampler=None):
     """sample_candidates without a generator: the lists [B, 1 + num_neg] int64 of the queries q [B, >= 2] on the GPU
     are a pure function of (seed, step, batch row, list position) and of `index`, drawn by one HIP launch
     (_native.cand_draw under the key of (seed, step, CAND_DRAW_SITE)): every rank of a sharded step that passes the same q, seed
@@ -116,11 +116,17 @@ def draw_candidates(q, index, num_entities, num_neg, seed, step, labels=False, s
     (cand, label [B, 1 + num_neg] uint8), the labels _native.cand_labels gives the drawn list against the whole table, from the
     same launch: what forward_loss_candidates(labels=...) and dist.train_step_sharded_candidates(labels=...) take.
     step_key_dev: a one-element int64 tensor on q's device that holds _native.dropout_step_key(seed, step) when the launch RUNS
-    (captured.CapturedCandidateStep's second word); `seed` and `step` are then unused."""
+    (captured.CapturedCandidateStep's second word); `seed` and `step` are then unused.
+    sampler (None: uniform negatives, unchanged): a sampling.NegativeSampler on q's device: the negatives are drawn through its
+    alias table instead (mgcn_cand_draw_alias), with every promise above kept. The list BCE trains on such lists
+    as they are (the word2vec convention); the softmax wants sampler.logq (forward_loss_candidates(logq=...))."""
     from . import _native
+    if sampler is not None and (sampler.num_entities != int(num_entities) or sampler.device != q.device):
+        raise _native.NativeError('draw_candidates: the sampler holds %d entities on %s, the draw is over %d on %s'
+                                  % (sampler.num_entities, sampler.device, int(num_entities), q.device))
     key = _native.dropout_key(seed, step, _native.CAND_DRAW_SITE) if step_key_dev is None else _native.DeviceKey(step_key_dev, _native.CAND_DRAW_SITE)
     cand, label = _native.cand_draw(index.query_keys(q[:, 0], q[:, 1]).contiguous(), index.keys, index.ptr, index.tails, int(num_entities),
-                                    1 + int(num_neg), key, labels=labels)
+                                    1 + int(num_neg), key, labels=labels, table=None if sampler is None else sampler.table)
     return (cand, label) if labels else cand
 
 
@@ -137,7 +143,7 @@ def check_query_keys(queries, index):
 
 
 def train_sampled_negatives(model, queries, index, graph, optimizer, params, batch_size, num_neg, generator=None, draw_seed=None,
-                            first_step=0, loss='bce', captured=None):
+                            first_step=0, loss='bce', captured=None, sampler=None):
     """One epoch like train_device_labels' eager loop, on sampled negatives: per step the candidate lists of
     sample_candidates (one known tail + num_neg uniform ids per query) and MGCN.forward_loss_candidates over them, so that no
     step touches a [B, N] block. `generator`: a CPU generator (or None: the default one) shuffles as train_device_labels does and
@@ -152,8 +158,16 @@ def train_sampled_negatives(model, queries, index, graph, optimizer, params, bat
     params.lbl_smooth / params.clip_grad and kept on the model for the following epochs); needs draw_seed. Every step is then one
     call of it (a replay of the captured step once it is warm), its draw_seed / num_neg / loss are set from the arguments and its
     draw_step to first_step, the per-step losses stay on the device, and the epoch reads them ONCE at its end into the same
-    RunningAverage. None (the default): the loop below, unchanged."""
+    RunningAverage. None (the default): the loop below, unchanged.
+    sampler (None: uniform negatives, unchanged): a sampling.NegativeSampler on params.device; needs draw_seed (the generator
+    route stays uniform and refuses a sampler). The negatives follow its table; loss='softmax' subtracts its logq from every
+    candidate's logit, loss='bce' takes the weighted lists without a correction (the word2vec convention). A
+    checkpoint stores sampler.state_dict() next to draw_seed and the step count."""
     kind = loss             # (`loss` below is a step's result)
+    if sampler is not None and draw_seed is None:
+        from . import _native
+        raise _native.NativeError('train_sampled_negatives: a sampler draws through the counter-based draw: give draw_seed')
+    logq = sampler.logq if sampler is not None and kind == 'softmax' else None
     if captured is not None and captured is not False and draw_seed is None:
         from . import _native
         raise _native.NativeError('train_sampled_negatives: a captured step draws its lists from (draw_seed, step): give draw_seed')
@@ -175,6 +189,7 @@ def train_sampled_negatives(model, queries, index, graph, optimizer, params, bat
     if captured is not None and captured is not False:
         step = _captured_cand_step(model, graph, index, optimizer, params) if captured is True else captured
         step.num_neg, step.loss, step.draw_seed, step.draw_step = int(num_neg), kind, int(draw_seed), int(first_step)
+        step.sampler = sampler
         starts = range(0, queries.size(0), batch_size)
         losses = torch.empty(len(starts), dtype=torch.float32, device=dev)
         for k, i in enumerate(starts):
@@ -190,9 +205,10 @@ def train_sampled_negatives(model, queries, index, graph, optimizer, params, bat
             optimizer.zero_grad()
             loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, index=index, lbl_smooth=params.lbl_smooth, loss=kind)
         else:
-            cand, labels = draw_candidates(q, index, n_ent, num_neg, draw_seed, int(first_step) + k, labels=True)
+            cand, labels = draw_candidates(q, index, n_ent, num_neg, draw_seed, int(first_step) + k, labels=True, sampler=sampler)
             optimizer.zero_grad()
-            loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, labels=labels, lbl_smooth=params.lbl_smooth, loss=kind)
+            loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, labels=labels, lbl_smooth=params.lbl_smooth, loss=kind,
+                                                 logq=logq)
         loss.backward()
         if hasattr(optimizer, 'clip_and_step'):          # optim.ClipAdam: norm, clipping and update on the HIP kernels
             optimizer.clip_and_step(params.clip_grad)

@@ -1045,7 +1045,7 @@ class MGCN(nn.Module):
         labels = _native.label_rows(keys, index.keys, index.ptr, index.tails, n_ent, lbl_smooth=lbl_smooth)
         return self.loss_fn(_ScoreFn.apply(x, ent, self.conv2.bias), labels)
 
-    def forward_loss_candidates(self, src, rel, cand, data, index=None, labels=None, lbl_smooth=0.0, loss='bce'):
+    def forward_loss_candidates(self, src, rel, cand, data, index=None, labels=None, lbl_smooth=0.0, loss='bce', logq=None):
         """forward_loss with a per-query candidate list in place of the entity table (training on sampled negatives): the mean
         BCE of the scores of cand [B, K] int64 (the true tails plus sampled negatives, e.g. harness.sample_candidates) against
         targets that are hot at the known tails and cold elsewhere, smoothed with 1/N as forward_loss smooths. Exactly one of
@@ -1056,10 +1056,22 @@ class MGCN(nn.Module):
         upstream (encoder, query rows, trunk and their switches) is forward_loss's.
         loss: 'bce' (the above) or 'softmax': the softmax cross-entropy over each query's list (sampled softmax, include/mgcn_hip.h
         (16)): the target mass (1 - lbl_smooth) is shared by the list's known tails and lbl_smooth is spread over the list's live
-        positions, the mean runs over the B queries; a query whose list names no known tail adds nothing and counts in B."""
+        positions, the mean runs over the B queries; a query whose list names no known tail adds nothing and counts in B.
+        logq (None: the above, unchanged): f32 [N] on the device, sampling.NegativeSampler.logq = log(N Q(id)) of the
+        distribution the negatives were drawn from; softmax only. Every live position's logit becomes
+        z - logq[id], the positive's included, so that the sampled softmax stays an estimate of the full one: the scoring
+        kernels are handed bias - logq as their bias (one element-wise op of size N; d bias passes straight through it). A
+        logq of zeros leaves every bit as it is. The BCE takes weighted lists WITHOUT a correction (the word2vec convention):
+        logq with loss='bce' is refused."""
         self._refuse_training_ee16('MGCN.forward_loss_candidates')
         if loss not in ('bce', 'softmax'):
             raise _native.NativeError("forward_loss_candidates: loss must be 'bce' or 'softmax', got %r" % (loss,))
+        if logq is not None:
+            if loss != 'softmax':
+                raise _native.NativeError("forward_loss_candidates: logq corrects the softmax only; loss='bce' takes weighted lists as they are")
+            bias = self.conv2.bias
+            if logq.dtype != torch.float32 or tuple(logq.shape) != tuple(bias.shape) or logq.device != bias.device:
+                raise _native.NativeError('forward_loss_candidates: logq must be f32 %s on %s' % (tuple(bias.shape), bias.device))
         if (index is None) == (labels is None):
             raise _native.NativeError('forward_loss_candidates: give exactly one of index / labels')
         cand = self._candidate_block(cand, src.numel())
@@ -1073,7 +1085,8 @@ class MGCN(nn.Module):
         elif labels.dtype not in (torch.uint8, torch.bool) or tuple(labels.shape) != tuple(cand.shape):
             raise _native.NativeError('forward_loss_candidates: labels must be uint8 / bool %s' % (tuple(cand.shape),))
         if loss == 'softmax':
-            return _CandCEFn.apply(x, ent, self.conv2.bias, cand, labels, float(lbl_smooth))
+            bias = self.conv2.bias if logq is None else self.conv2.bias - logq
+            return _CandCEFn.apply(x, ent, bias, cand, labels, float(lbl_smooth))
         hot, cold = _native.smoothed_targets(lbl_smooth, n_ent)
         return _CandBCEFn.apply(x, ent, self.conv2.bias, cand, labels, hot, cold)
 
