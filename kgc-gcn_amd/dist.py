@@ -12,8 +12,11 @@ in the aggregation itself when every rank holds the whole graph (FB15k-237: 12 M
 """
 import torch
 import torch.distributed as dist
+import torch.nn.functional as F
 
 from . import _native
+from .autograd import _AggregateFn, _LayerTrainFn
+from .model import _drawn_dropout, counter_dropout, list_loss_stage, query_rows, refuse_list_step, table_bce_stage
 
 
 def shard_bounds(n, world):
@@ -475,106 +478,14 @@ class _Exchange(object):
         out = torch.cat([full[r * width:r * width + nb[r]] for r in range(self.world) if nb[r] > 0], dim=0)
         return (out.permute(1, 0, 2) if stacked else out).contiguous()
 
+    def gather_stats(self, stat):
+        """[world, B, 4]: every rank's [B, 4] row statistics of the list softmax in rank order (one all-gather)."""
+        return _gather(stat, self.group, self.world).view(self.world, stat.size(0), 4)
+
     def all_reduce(self, t):
         if self.world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
         return t
-
-
-def _mm(a, b):
-    return _native.matmul(a, b) if a.size(0) > 0 else a.new_zeros((0, b.size(1)))
-
-
-def _mm_tn(a, b):
-    return _native.matmul_tn(a, b) if a.size(0) > 0 else a.new_zeros((a.size(1), b.size(1)))
-
-
-class _ShardAggregateFn(torch.autograd.Function):
-    """In / out aggregates [n1 - n0, 2D] of this rank's destinations from its table shard; backward by mgcn_aggregate_bwd_shard
-    (gee complete, grel and gx partial: the ranks' sums add up). The incoming gradient goes through .contiguous(): a contiguous
-    one is passed through, every other layout is copied."""
-
-    @staticmethod
-    def forward(ctx, x, rels, ee_shard, csr, n0, n1):
-        out = torch.empty((n1 - n0, 2 * x.size(1)), dtype=torch.float32, device=x.device)
-        if n1 > n0:
-            _native.aggregate_fwd(csr, x, rels, ee_shard, True, None, out, node_range=(n0, n1), ee_sub=csr.shard_ee_sub(n0, n1),
-                                  out_row0=n0)
-        ctx.save_for_backward(x, rels, ee_shard)
-        ctx.csr, ctx.range = csr, (n0, n1)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, rels, ee = ctx.saved_tensors
-        gx, gee, grel = _native.aggregate_bwd_shard(ctx.csr, x, rels, ee, g.contiguous(), ctx.range, want_gx=ctx.needs_input_grad[0])
-        return gx, grel, gee, None, None, None
-
-
-class _ShardLayerTrainFn(torch.autograd.Function):
-    """model._LayerTrainFn on this rank's rows with GLOBAL batch statistics: the BN reductions run in the split stages of
-    csrc/train_layer.hip (4s) and every rank's per-block partials are all-gathered between them (forward: column sums, then
-    centred sums; backward: the g_pre / g_pre * xhat sums). Dropout keep-masks are the rank's own for its rows, or, with
-    `drop_keys` = (key_in, key_out, row0 = n0), the counter-based ones of csrc/dropout.hip: the bits of the GLOBAL rows, the same
-    on any partition, recomputed in the backward instead of saved. The incoming gradient goes through .contiguous(): a contiguous
-    one is passed through, every other layout is copied."""
-
-    @staticmethod
-    def forward(ctx, agg, a_loop, w_in, w_out, w_loop, bias, gamma, beta, running_mean, running_var, momentum, eps, p_drop, ex,
-                drop_keys=None):
-        d = w_in.size(0)
-        u_in, u_out = _mm(agg[:, :d], w_in.contiguous()), _mm(agg[:, d:], w_out.contiguous())
-        u_loop = _mm(a_loop.contiguous(), w_loop.contiguous())
-        m_in = m_out = None
-        ctx.inv_keep = 1.0
-        ctx.drop = None
-        if drop_keys is not None and p_drop > 0:
-            ctx.drop = (int(drop_keys[0]), int(drop_keys[1]), int(drop_keys[2]), float(p_drop))
-            _native.dropout_apply_pair(u_in, ctx.drop[0], u_out, ctx.drop[1], ctx.drop[2], ctx.drop[3], out_a=u_in, out_b=u_out)
-        elif p_drop >= 1.0:
-            m_in = torch.zeros(u_in.shape, dtype=torch.bool, device=u_in.device)
-            m_out, ctx.inv_keep = m_in, 0.0
-            u_in, u_out = torch.zeros_like(u_in), torch.zeros_like(u_out)
-        elif p_drop > 0:
-            keep = 1.0 - p_drop
-            ctx.inv_keep = 1.0 / keep
-            m_in = torch.empty_like(u_in).bernoulli_(keep).bool()
-            m_out = torch.empty_like(u_out).bernoulli_(keep).bool()
-            u_in, u_out = (u_in * m_in).mul_(ctx.inv_keep), (u_out * m_out).mul_(ctx.inv_keep)
-        z, part = _native.bn_train_stage_sum(u_in, u_out, u_loop, bias)
-        mean, part = _native.bn_train_stage_center(z, ex.gather_blocks(part), ex.total)
-        y, rstd = _native.bn_train_stage_finish(z, ex.gather_blocks(part), ex.total, mean, gamma, beta, running_mean, running_var,
-                                                momentum, eps)
-        ctx.save_for_backward(agg, a_loop, w_in, w_out, w_loop, gamma, z, y, mean, rstd, m_in, m_out)
-        ctx.has_bias, ctx.ex = bias is not None, ex
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        agg, a_loop, w_in, w_out, w_loop, gamma, z, y, mean, rstd, m_in, m_out = ctx.saved_tensors
-        d = w_in.size(0)
-        gy = gy.contiguous()
-        parts = ctx.ex.gather_blocks(_native.bn_train_bwd_stage_sums(z, y, gy, mean, rstd))
-        gz, gu, ggamma, gbeta = _native.bn_train_bwd_stage_apply(z, y, gy, mean, rstd, gamma, parts[0], parts[1], ctx.ex.total)
-        if ctx.drop is not None:
-            g_in, g_out = _native.dropout_apply_pair(gu, ctx.drop[0], gu, ctx.drop[1], ctx.drop[2], ctx.drop[3])
-        else:
-            g_in = (gu * m_in).mul_(ctx.inv_keep) if m_in is not None else gu
-            g_out = (gu * m_out).mul_(ctx.inv_keep) if m_out is not None else gu
-        need = ctx.needs_input_grad
-        g_agg = g_loop = g_win = g_wout = g_wloop = None
-        if need[0]:
-            g_agg = torch.cat([_mm(g_in, w_in.t().contiguous()), _mm(g_out, w_out.t().contiguous())], dim=1)
-        if need[1]:
-            g_loop = _mm(gu, w_loop.t().contiguous())
-        if need[2]:
-            g_win = _mm_tn(agg[:, :d], g_in)
-        if need[3]:
-            g_wout = _mm_tn(agg[:, d:], g_out)
-        if need[4]:
-            g_wloop = _mm_tn(a_loop.contiguous(), gu)
-        g_bias = gz.sum(0) if (ctx.has_bias and need[5]) else None
-        return g_agg, g_loop, g_win, g_wout, g_wloop, g_bias, ggamma, gbeta, None, None, None, None, None, None, None
 
 
 class _GatherRowsFn(torch.autograd.Function):
@@ -629,87 +540,8 @@ class _RankZeroGradFn(torch.autograd.Function):
         return (g if ctx.ex.rank == 0 else torch.zeros_like(g)), None
 
 
-class _ScoreBCEShardFn(torch.autograd.Function):
-    """model._ScoreBCEFn on this rank's entity rows: the mean runs over B x the GLOBAL entity count, so the ranks' losses and
-    gradients add up to the whole table's. The incoming scalar gradient is handled as in model._ScoreBCEFn."""
-
-    @staticmethod
-    def forward(ctx, x, ent, bias, mask, hot, cold, num_entities):
-        loss, g = _native.score_bce_fwd(x, ent, bias, mask, hot, cold, num_entities=num_entities)
-        ctx.save_for_backward(x, ent, g)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gl):
-        from .model import _ScoreBCEFn
-        return _ScoreBCEFn.backward(ctx, gl) + (None,)
-
-
-class _CandBCEShardFn(torch.autograd.Function):
-    """model._CandBCEFn on this rank's entity rows [row0, row0 + ent.size(0)) (include/mgcn_hip.h (14), the ent_row0 / n_local
-    form): list positions whose id another rank owns are dead here, they write g = 0, add no loss term and still count in the
-    divisor B K, so the ranks' losses and d x add up to the one-rank step's; d ent and d bias are the rank's rows, complete.
-    The incoming scalar gradient is handled as in model._CandBCEFn."""
-
-    @staticmethod
-    def forward(ctx, x, ent, bias, cand, label, hot, cold, row0):
-        loss, g = _native.cand_bce_fwd(x, ent, bias, cand, label, hot, cold, ent_row0=row0)
-        perm, ctx.n_live = _native.cand_plan(cand, ent.size(0), ent_row0=row0, count=False)
-        ctx.row0 = int(row0)
-        ctx.save_for_backward(x, ent, cand, g, perm)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gl):
-        x, ent, cand, g, perm = ctx.saved_tensors
-        g = g * gl                                           # (as model._CandBCEFn: gl = 1 changes no bit of g)
-        gx = _native.cand_bce_bwd_x(g, cand, ent, ent_row0=ctx.row0) if ctx.needs_input_grad[0] else None
-        want = tuple(n for i, n in ((1, 'ent'), (2, 'bias')) if ctx.needs_input_grad[i])
-        d_ent, d_bias = (None, None)
-        if want:
-            d_ent, d_bias = _native.cand_bce_bwd_ent(g, cand, x, perm, ctx.n_live, ent.size(0), ent_row0=ctx.row0, want=want)
-        return (gx, d_ent, d_bias, None, None, None, None, None)
-
-
-class _CandCEShardFn(torch.autograd.Function):
-    """model._CandCEFn on this rank's entity rows [row0, row0 + ent.size(0)) (include/mgcn_hip.h (16)): the rank's logits and
-    row statistics, ONE all-gather of the [B, 4] statistics, their merge over the ranks in rank order (the same kernel that
-    merged the chunks), and the finish with the global statistics. The rank's loss is the sum of its own positions' terms, so
-    the ranks' losses and d x add up to the one-rank step's; d ent and d bias are the rank's rows, complete. A rank without
-    rows contributes the empty statistic and joins the all-gather. With one rank there is no collective and no second merge:
-    model._CandCEFn's launches. The incoming scalar gradient is handled as in model._CandBCEFn."""
-
-    @staticmethod
-    def forward(ctx, x, ent, bias, cand, label, eps, row0, ex):
-        B, n = x.size(0), ent.size(0)
-        if n:
-            z, stat = _native.cand_ce_logits(x, ent, bias, cand, label, ent_row0=row0)
-            stat = _native.cand_ce_merge(stat)
-        else:
-            z = torch.full(tuple(cand.shape), float('-inf'), dtype=torch.float32, device=x.device)
-            stat = _native.cand_ce_empty_stat(B, x.device)
-        if ex.world > 1:
-            stat = _native.cand_ce_merge(_gather(stat, ex.group, ex.world).view(ex.world, B, 4), part_dim=0)
-        loss, g, _ = _native.cand_ce_finish(z, cand, label, stat, eps, n, ent_row0=row0)
-        perm, ctx.n_live = _native.cand_plan(cand, n, ent_row0=row0, count=False)
-        ctx.row0 = int(row0)
-        ctx.save_for_backward(x, ent, cand, g, perm)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gl):
-        return _CandBCEShardFn.backward(ctx, gl)
-
-
-def _dropout(x, p, generator):
-    """F.dropout with the keep-mask drawn from `generator` (model._drawn_dropout: the one both trunk paths use)."""
-    from .model import _drawn_dropout
-    return _drawn_dropout(x, p, generator)
-
-
 def _trunk(conv2, src_emb, rel_emb, generator):
     """ConvE.trunk with its two dropouts drawn from `generator` (None: torch's default generator, as ConvE.trunk)."""
-    import torch.nn.functional as F
     if generator is None or not conv2.training:
         return conv2.trunk(src_emb, rel_emb)
     if conv2._hip_trunk_train(src_emb, rel_emb):      # the HIP training trunk draws the same two masks from `generator`
@@ -718,7 +550,7 @@ def _trunk(conv2, src_emb, rel_emb, generator):
     o = p.gcn_out_dim
     stack = torch.cat([src_emb.view(-1, 1, o), rel_emb.view(-1, 1, o)], dim=1)
     stack = stack.transpose(2, 1).reshape(-1, 1, 2 * p.k_w, p.k_h)
-    x = _dropout(F.relu(conv2.bn1(conv2.conv_e(conv2.bn0(stack)))), conv2.feature_drop.p, generator)
+    x = _drawn_dropout(F.relu(conv2.bn1(conv2.conv_e(conv2.bn0(stack)))), conv2.feature_drop.p, generator)
     return conv2._tail(conv2.fc(x.view(-1, conv2.flat_sz)), generator, True)      # (the HIP tail with MGCN_QUERY_TRAIN=hip)
 
 
@@ -896,27 +728,15 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
     MGCN.encode does; every rank must hold the same (dropout_seed, dropout_step). With one rank the step then equals
     forward_loss + backward + clip_grad_norm_ + step bit for bit AT ANY DROPOUT.
     Returns the global loss (0-dim tensor, detached)."""
-    import torch.nn.functional as F
     ex, ent, xt = _sharded_trunk(model, graph, src, rel, optimizer, group, generator, 'train_step_sharded')
-    n0, n1, W = ex.n0, ex.n1, ex.world
-    bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]
-    N = ex.total
     keys = index.query_keys(src, rel)
-    if _native.score_bce_supported(xt, ent) and n1 > n0:
-        hot, cold = _native.smoothed_targets(lbl_smooth, N)
-        mask = _native.filter_mask(keys, index.keys, index.ptr, index.tails, n1 - n0, ent_row0=n0)
-        loss = _ScoreBCEShardFn.apply(xt, ent, bias, mask, hot, cold, N)
-    elif n1 == n0:      # a rank without entity rows scores nothing, but takes part in the backward's collectives
-        loss = (xt * 0.0).sum()
-    else:               # batch sizes the fused launch does not take: the scores of the rank's entities, then the BCE
-        from .model import _ScoreFn
-        labels = _native.label_rows(keys, index.keys, index.ptr, index.tails, n1 - n0, lbl_smooth=lbl_smooth, num_entities=N,
-                                    ent_row0=n0)
-        scores = _ScoreFn.apply(xt, ent, bias)
-        # one rank: forward_loss's own form (BCELoss's mean); several: the rank's sum over the global count, the ranks' parts add up
-        loss = model.loss_fn(scores, labels) if W == 1 else \
-            F.binary_cross_entropy(scores, labels, reduction='sum') * (1.0 / (xt.size(0) * N))
+    loss = table_bce_stage(model, xt, ent, _own_bias(model, ex), keys, index, lbl_smooth, ex.total, ex.n0, ex.world)
     return _sharded_finish(model, ex, loss, optimizer, clip, group)
+
+
+def _own_bias(model, ex):
+    """The scorer's bias of this rank's entity rows (one rank: the parameter itself, not a view of all of it)."""
+    return model.conv2.bias if ex.world == 1 else model.conv2.bias[ex.n0:ex.n1]
 
 
 def _sharded_trunk(model, graph, src, rel, optimizer, group, generator, what):
@@ -924,10 +744,7 @@ def _sharded_trunk(model, graph, src, rel, optimizer, group, generator, what):
     layer: aggregate, train epilogue, dropout, row gather) and the ConvE trunk of the whole batch, its output behind
     _AllReduceGradFn at W > 1 (every rank's scorer returns a partial d x). Returns (exchange, ent = this rank's rows [n1 - n0, O]
     of the last layer's output, xt = the trunk's output [B, O])."""
-    import torch.nn.functional as F
-    if _native.is_ee16(model.edge_embeddings):
-        raise _native.NativeError('%s: this model holds its per-edge tables in bf16 (params.edge_table_dtype), '
-                                  'which is inference-only' % what)
+    model._refuse_training_ee16(what, training=True)
     csr, ex = _sharded_setup(model, graph, group, what)
     n0, n1, W = ex.n0, ex.n1, ex.world
     model.train()
@@ -945,18 +762,17 @@ def _sharded_trunk(model, graph, src, rel, optimizer, group, generator, what):
         last = li == len(layers) - 1
         bn = layer.ent_bn
         rels = torch.cat([rel_e, layer.loop_rel], dim=0)
-        agg = _ShardAggregateFn.apply(x, rels, table, csr, n0, n1)
+        agg = _AggregateFn.apply(x, rels, table, csr, (n0, n1))
         x_own = x if (n0, n1) == (0, x.size(0)) else x[n0:n1]
         a_loop = (x_own * rels[-1]) * layer.loop_edge
-        y = _ShardLayerTrainFn.apply(agg, a_loop, layer.in_weight, layer.out_weight, layer.loop_weight, layer.bias, bn.weight,
-                                     bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, layer.drop.p, ex,
-                                     None if drop_ctx is None else
-                                     tuple(_native.dropout_key(drop_ctx[0], drop_ctx[1], _native.dropout_layer_site(li, w)) for w in (0, 1)) + (n0,))
+        keys = None if drop_ctx is None else \
+            tuple(_native.dropout_key(drop_ctx[0], drop_ctx[1], _native.dropout_layer_site(li, w)) for w in (0, 1)) + (n0,)
+        y = _LayerTrainFn.apply(agg, a_loop, layer.in_weight, layer.out_weight, layer.loop_weight, layer.bias, bn.weight,
+                                bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, layer.drop.p, keys, ex)
         with torch.no_grad():
             bn.num_batches_tracked += 1
         rel_e = torch.matmul(_RankZeroGradFn.apply(rels, ex) if (last and W > 1) else rels, layer.rels_weight)[:-1]
         if drop_ctx is not None:
-            from .model import counter_dropout
             y = counter_dropout(y, model.params.gcn_drop, drop_ctx[0], drop_ctx[1], _native.dropout_layer_site(li, 2), row0=n0)
         else:
             y = F.dropout(y, p=model.params.gcn_drop, training=True)
@@ -967,7 +783,6 @@ def _sharded_trunk(model, graph, src, rel, optimizer, group, generator, what):
     elif W > 1 and generator is None and (model.conv2.feature_drop.p > 0 or model.conv2.hidden_drop.p > 0):
         generator = torch.Generator(device=ent.device)
         generator.manual_seed(_agreed_seed(group, ent.device))
-    from .model import query_rows
     xt = _trunk(model.conv2, query_rows(model, x, src), query_rows(model, rel_e, rel), generator)
     if W > 1:
         xt = _AllReduceGradFn.apply(xt, ex)
@@ -1034,46 +849,18 @@ def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer
     params.dropout = 'counter'). A rank without entity rows scores nothing and joins every collective.
     loss = 'softmax': the softmax cross-entropy over each list instead (forward_loss_candidates(loss='softmax')):
     a row's maximum, sum and counts span the ranks, so the step makes one more collective, an all-gather of the [B, 4] row
-    statistics (_CandCEShardFn); lbl_smooth is spread over the list; the ranks' losses add up as above.
+    statistics (_CandCEFn with the exchange); lbl_smooth is spread over the list; the ranks' losses add up as above.
     logq (None: the above, unchanged): f32 [N] over the WHOLE table, sampling.NegativeSampler.logq on the device, softmax only
     (forward_loss_candidates(logq=...)): the rank hands its scoring stage bias[n0:n1] - logq[n0:n1].
     Returns the global loss (0-dim tensor, detached)."""
     what = 'train_step_sharded_candidates'
-    if loss not in ('bce', 'softmax'):
-        raise _native.NativeError("%s: loss must be 'bce' or 'softmax', got %r" % (what, loss))
-    if logq is not None:
-        if loss != 'softmax':
-            raise _native.NativeError("%s: logq corrects the softmax only; loss='bce' takes weighted lists as they are" % what)
-        n = model.entity_embedding.size(0)
-        if logq.dtype != torch.float32 or tuple(logq.shape) != (n,) or logq.device != model.conv2.bias.device:
-            raise _native.NativeError('%s: logq must be f32 [%d] on %s' % (what, n, model.conv2.bias.device))
-    if _native.is_ee16(model.edge_embeddings):      # (before the list is looked at: the refusal _sharded_trunk repeats)
-        raise _native.NativeError('%s: this model holds its per-edge tables in bf16 (params.edge_table_dtype), '
-                                  'which is inference-only' % what)
-    cand = model._candidate_block(cand, src.numel())
-    if labels is not None and (labels.dtype not in (torch.uint8, torch.bool) or tuple(labels.shape) != tuple(cand.shape)):
-        raise _native.NativeError('%s: labels must be uint8 / bool %s' % (what, tuple(cand.shape)))
+    model._refuse_training_ee16(what, training=True)      # (before the list is looked at: the refusal _sharded_trunk repeats)
+    cand = refuse_list_step(what, model, src.numel(), cand, labels, loss, logq)
     if labels is None and index is None:
         raise _native.NativeError('%s: give index or labels' % what)
     ex, ent, xt = _sharded_trunk(model, graph, src, rel, optimizer, group, generator, what)
-    n0, n1, W = ex.n0, ex.n1, ex.world
-    if loss == 'softmax':       # (a rank without entity rows passes the empty statistic on: it joins the all-gather)
-        bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]
-        if logq is not None:
-            bias = bias - (logq if W == 1 else logq[n0:n1])
-        xt = xt if xt.stride(-1) == 1 else xt.contiguous()
-        if labels is None:
-            labels = _native.cand_labels(index.query_keys(src, rel), index.keys, index.ptr, index.tails, cand, n1 - n0, ent_row0=n0)
-        loss = _CandCEShardFn.apply(xt, ent, bias, cand, labels, float(lbl_smooth), n0, ex)
-    elif n1 == n0:      # a rank without entity rows scores nothing, but takes part in the backward's collectives
-        loss = (xt * 0.0).sum()
-    else:
-        bias = model.conv2.bias if W == 1 else model.conv2.bias[n0:n1]
-        xt = xt if xt.stride(-1) == 1 else xt.contiguous()
-        if labels is None:
-            labels = _native.cand_labels(index.query_keys(src, rel), index.keys, index.ptr, index.tails, cand, n1 - n0, ent_row0=n0)
-        hot, cold = _native.smoothed_targets(lbl_smooth, ex.total)
-        loss = _CandBCEShardFn.apply(xt, ent, bias, cand, labels, hot, cold, n0)
+    keys = index.query_keys(src, rel) if labels is None else None
+    loss = list_loss_stage(xt, ent, _own_bias(model, ex), cand, labels, index, keys, lbl_smooth, loss, logq, ex.total, ex.n0, ex)
     return _sharded_finish(model, ex, loss, optimizer, clip, group)
 
 

@@ -27,17 +27,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native
+from .autograd import (_AggregateFn, _CandBCEFn, _CandCEFn, _CounterDropoutFn, _LayerTrainFn, _QueryRowsFn, _ScoreBCEFn, _ScoreFn,
+                       _TrunkTailFn, _TrunkTrainFn)
 from .graph import csr_for_tensors
 from .utils import get_param
 
 
 def _capturing(t):
     return t.is_cuda and torch.cuda.is_current_stream_capturing()
-
-
-def _key_arg(k):
-    """A dropout key as the autograd functions keep it: a plain int, or the device form as it is."""
-    return k if isinstance(k, _native.DeviceKey) else int(k)
 
 
 def _site_key(drop_ctx, site):
@@ -51,162 +48,6 @@ def _site_key(drop_ctx, site):
 
 def _word_of(drop_ctx):
     return drop_ctx[2] if len(drop_ctx) > 2 else None
-
-
-class _AggregateFn(torch.autograd.Function):
-    """A[:, :D] / A[:, D:2D] = in-/out-half aggregates; gradients by the HIP backward kernels.
-    The incoming gradient goes through .contiguous(): a contiguous one is passed through, every other layout is copied."""
-
-    @staticmethod
-    def forward(ctx, x, rel, ee_slot, csr):
-        out = torch.empty((x.size(0), 2 * x.size(1)), dtype=torch.float32, device=x.device)
-        _native.aggregate_fwd(csr, x, rel, ee_slot, True, None, out)
-        ctx.save_for_backward(x, rel, ee_slot)
-        ctx.csr = csr
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, rel, ee = ctx.saved_tensors
-        gx, gee, grel = _native.aggregate_bwd(ctx.csr, x, rel, ee, g.contiguous(), want_gx=ctx.needs_input_grad[0],
-                                              want_gee=ctx.needs_input_grad[2], want_grel=ctx.needs_input_grad[1])
-        return gx, grel, gee, None
-
-
-class _LayerTrainFn(torch.autograd.Function):
-    """Training-mode dense step + epilogue of one layer (model.py:103-106, 116 under .train()) on the HIP kernels:
-    y = tanh(BN_batch((drop(A_in W_in) + drop(A_out W_out) + A_loop W_loop) / 3 (+ bias))). Products on the f32 MFMA
-    kernels (forward A W, backward g W^T and the split-K A^T g), batch statistics / normalisation / tanh and their
-    backward on the two-stage reduction kernels of csrc/train_layer.hip; the running statistics are updated in place.
-    Dropout masks come from torch's generator (Bernoulli keep-masks scaled by 1 / keep, as F.dropout), or, with `drop_keys` =
-    (key_in, key_out, row0), from the counter-based definition of csrc/dropout.hip: one pair launch in place on the
-    two products, no mask saved, and one pair launch in the backward that forms both gradients from gu.
-    The incoming gradient is taken in any layout (_native._bn_grad): a contiguous one is passed through, every other one is copied."""
-
-    @staticmethod
-    def forward(ctx, agg, a_loop, w_in, w_out, w_loop, bias, gamma, beta, running_mean, running_var, momentum, eps, p_drop,
-                drop_keys=None):
-        d = w_in.size(0)
-        u_in, u_out = _native.matmul(agg[:, :d], w_in.contiguous()), _native.matmul(agg[:, d:], w_out.contiguous())
-        u_loop = _native.matmul(a_loop.contiguous(), w_loop.contiguous())
-        # dropout keep-masks are saved as bool (1 byte per element, not a scaled f32 copy) and scaled by 1 / keep at use
-        m_in = m_out = None
-        ctx.inv_keep = 1.0
-        ctx.drop = None
-        if drop_keys is not None and p_drop > 0:      # counter-based: the bits are recomputed in the backward, nothing is saved
-            ctx.drop = (_key_arg(drop_keys[0]), _key_arg(drop_keys[1]), int(drop_keys[2]), float(p_drop))
-            _native.dropout_apply_pair(u_in, ctx.drop[0], u_out, ctx.drop[1], ctx.drop[2], ctx.drop[3], out_a=u_in, out_b=u_out)
-        elif p_drop >= 1.0:                       # F.dropout(p=1) is all zeros (1 / keep would be 0 / 0)
-            m_in = torch.zeros(u_in.shape, dtype=torch.bool, device=u_in.device)
-            m_out, ctx.inv_keep = m_in, 0.0
-            u_in, u_out = torch.zeros_like(u_in), torch.zeros_like(u_out)
-        elif p_drop > 0:
-            keep = 1.0 - p_drop
-            ctx.inv_keep = 1.0 / keep
-            m_in = torch.empty_like(u_in).bernoulli_(keep).bool()
-            m_out = torch.empty_like(u_out).bernoulli_(keep).bool()
-            u_in, u_out = (u_in * m_in).mul_(ctx.inv_keep), (u_out * m_out).mul_(ctx.inv_keep)   # as F.dropout: x * mask * (1 / keep)
-        y, z, mean, rstd = _native.bn_tanh_train_fwd(u_in, u_out, u_loop, bias, gamma, beta, running_mean, running_var,
-                                                     momentum, eps)
-        ctx.save_for_backward(agg, a_loop, w_in, w_out, w_loop, gamma, z, y, mean, rstd, m_in, m_out)
-        ctx.has_bias = bias is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        agg, a_loop, w_in, w_out, w_loop, gamma, z, y, mean, rstd, m_in, m_out = ctx.saved_tensors
-        d = w_in.size(0)
-        gz, gu, ggamma, gbeta = _native.bn_tanh_train_bwd(z, y, gy, mean, rstd, gamma)
-        if ctx.drop is not None:
-            g_in, g_out = _native.dropout_apply_pair(gu, ctx.drop[0], gu, ctx.drop[1], ctx.drop[2], ctx.drop[3])
-        else:
-            g_in = (gu * m_in).mul_(ctx.inv_keep) if m_in is not None else gu
-            g_out = (gu * m_out).mul_(ctx.inv_keep) if m_out is not None else gu
-        need = ctx.needs_input_grad
-        g_agg = g_loop = g_win = g_wout = g_wloop = None
-        if need[0]:
-            g_agg = torch.cat([_native.matmul(g_in, w_in.t().contiguous()), _native.matmul(g_out, w_out.t().contiguous())], dim=1)
-        if need[1]:
-            g_loop = _native.matmul(gu, w_loop.t().contiguous())
-        if need[2]:
-            g_win = _native.matmul_tn(agg[:, :d], g_in)
-        if need[3]:
-            g_wout = _native.matmul_tn(agg[:, d:], g_out)
-        if need[4]:
-            g_wloop = _native.matmul_tn(a_loop.contiguous(), gu)
-        g_bias = gz.sum(0) if (ctx.has_bias and need[5]) else None
-        return g_agg, g_loop, g_win, g_wout, g_wloop, g_bias, ggamma, gbeta, None, None, None, None, None, None
-
-
-class _TrunkTrainFn(torch.autograd.Function):
-    """Training-mode ConvE trunk from the gathered rows to the fc output (model.py:164-171 under .train()) on the kernels of
-    csrc/conve_train.hip: z = fc(feature_drop(relu(bn1(conv_e(bn0(image(s, r))))))) with batch statistics, and its backward.
-    Saves the workspace that holds the pre-BN convolution output c, the bool keep-mask (1 byte per element, scaled by
-    1 / keep at use) and the batch statistics; the running statistics of bn0 / bn1 are updated in place.
-    The incoming gradient is passed through when its last stride is 1 and its rows are at least O apart (contiguous, row windows,
-    column windows at any offset); transposed and expanded ones (row stride 0) are copied."""
-
-    @staticmethod
-    def forward(ctx, s, r, conv_w, conv_b, fc_w, fc_b, g0, b0, g1, b1, bn0_stats, bn1_stats, keep, inv_keep, geom):
-        z, saved, ws = _native.conve_train_fwd(geom, s, r, conv_w, conv_b, fc_w, fc_b, (g0, b0) + bn0_stats, (g1, b1) + bn1_stats,
-                                               keep, inv_keep)
-        ctx.save_for_backward(s, r, conv_w, fc_w, g0, b0, g1, b1, keep, saved, ws)
-        ctx.geom, ctx.inv_keep, ctx.has_conv_bias, ctx.has_fc_bias = geom, inv_keep, conv_b is not None, fc_b is not None
-        return z
-
-    @staticmethod
-    def backward(ctx, gz):
-        s, r, conv_w, fc_w, g0, b0, g1, b1, keep, saved, ws = ctx.saved_tensors
-        names = ('s', 'r', 'conv_w', 'conv_b', 'fc_w', 'fc_b', 'g0', 'b0', 'g1', 'b1')
-        want = {n for i, n in enumerate(names) if ctx.needs_input_grad[i]}
-        want -= set() if ctx.has_conv_bias else {'conv_b'}
-        want -= set() if ctx.has_fc_bias else {'fc_b'}
-        # rows at least O apart, the rule of _QueryRowsFn / _TrunkTailFn: a row-expanded gradient (strides (0, 1), what a
-        # y.sum(0) downstream hands over) has a unit last stride and a leading dimension of 0, which the kernels refuse
-        gz = gz if (gz.stride(1) == 1 and gz.stride(0) >= gz.size(1)) else gz.contiguous()
-        g = _native.conve_train_bwd(ctx.geom, s, r, conv_w, fc_w, g0, b0, g1, b1, keep, ctx.inv_keep, saved, ws, gz, want)
-        return tuple(g.get(n) for n in names) + (None,) * 5
-
-
-class _QueryRowsFn(torch.autograd.Function):
-    """table[idx] (model.py:35-36). The forward stays torch.index_select (a copy); the backward is the fixed-order row sum of
-    csrc/query_train.hip, bit for bit the sequential loop d table[idx[b]] += g[b] in ascending b, instead of index_add_'s float
-    atomics. The incoming gradient is passed through when its last stride is 1 and its rows are at least dim apart (contiguous,
-    row windows, column windows at any offset); transposed and expanded ones are copied."""
-
-    @staticmethod
-    def forward(ctx, table, idx):
-        ctx.save_for_backward(idx)
-        ctx.num_rows = table.size(0)
-        return torch.index_select(table, 0, idx)
-
-    @staticmethod
-    def backward(ctx, g):
-        (idx,) = ctx.saved_tensors
-        g = g if (g.stride(1) == 1 and g.stride(0) >= g.size(1)) else g.contiguous()
-        return _native.query_rows_bwd(idx, g, ctx.num_rows), None
-
-
-class _TrunkTailFn(torch.autograd.Function):
-    """The trunk's tail x = relu(bn2(z keep inv_keep)) with batch statistics (model.py:173-175 under .train()) on the kernels of
-    csrc/query_train.hip, one launch forward and one backward. Saves z, the bool keep-mask, the batch statistics and the output
-    (the backward reads the relu mask from it); bn2's running statistics are updated in place.
-    The incoming gradient is passed through when its last stride is 1 and its rows are at least O apart (contiguous, row windows,
-    column windows at any offset); transposed and expanded ones are copied."""
-
-    @staticmethod
-    def forward(ctx, z, gamma, beta, running_mean, running_var, momentum, eps, keep, inv_keep):
-        x, saved = _native.conve_tail_fwd(z, keep, inv_keep, gamma, beta, running_mean, running_var, momentum, eps)
-        ctx.save_for_backward(z, gamma, keep, saved, x)
-        ctx.inv_keep = inv_keep
-        return x
-
-    @staticmethod
-    def backward(ctx, gx):
-        z, gamma, keep, saved, x = ctx.saved_tensors
-        gx = gx if (gx.stride(1) == 1 and gx.stride(0) >= gx.size(1)) else gx.contiguous()
-        want = {n for i, n in enumerate(('z', 'gamma', 'beta')) if ctx.needs_input_grad[i]}
-        return _native.conve_tail_bwd(z, keep, ctx.inv_keep, x, saved, gamma, gx, want) + (None,) * 6
 
 
 def _query_train_wanted(params):
@@ -228,7 +69,7 @@ def query_rows(model, table, idx):
 
 
 def _drawn_dropout(x, p, generator):
-    """F.dropout with the keep-mask drawn by bernoulli_ from `generator` (None: the default generator); dist._dropout is this."""
+    """F.dropout with the keep-mask drawn by bernoulli_ from `generator` (None: the default generator)."""
     if p <= 0:
         return x
     if p >= 1:
@@ -252,24 +93,6 @@ def edge_table_dtype(params):
     return torch.bfloat16 if want == 'bf16' else torch.float32
 
 
-class _CounterDropoutFn(torch.autograd.Function):
-    """Dropout of a matrix [rows, cols] whose keep bits are the counter-based ones of csrc/dropout.hip: a pure
-    function of (key, row0 + row, col). Forward and backward are the same launch; nothing is saved but the scalars.
-    The incoming gradient is passed through where _native.dropout_supported takes it (last stride 1, rows at least cols apart:
-    contiguous, row and column windows; a misaligned one takes the kernel's scalar path); transposed and expanded ones are copied."""
-
-    @staticmethod
-    def forward(ctx, x, key, row0, p):
-        ctx.args = (_key_arg(key), int(row0), float(p))
-        x = x if _native.dropout_supported(x) else x.contiguous()
-        return _native.dropout_apply(x, *ctx.args)
-
-    @staticmethod
-    def backward(ctx, g):
-        g = g if _native.dropout_supported(g) else g.contiguous()
-        return _native.dropout_apply(g, *ctx.args), None, None, None
-
-
 def counter_dropout(x, p, seed, step, site, row0=0, step_key_dev=None):
     """x [rows, cols] through the counter-based dropout of site `site` at (seed, step); p <= 0 launches nothing. `step_key_dev`
     (a one-word int64 device tensor, see _site_key): the device-key form, which reads the step from that word when it runs."""
@@ -291,103 +114,63 @@ def candidate_counts(scores, cand, obj, target):
     return torch.stack([(live & (scores > t)).sum(1), (eq & (cand < o)).sum(1), eq.sum(1)], dim=1).to(torch.int64)
 
 
-class _ScoreFn(torch.autograd.Function):
-    """sigmoid(x @ ent^T + bias): forward and both backward products on the HIP f32 MFMA tile kernel.
-    The incoming gradient is read by torch's elementwise gs * s * (1 - s) in any layout; the kernels see that product's contiguous
-    result only."""
-
-    @staticmethod
-    def forward(ctx, x, ent, bias):
-        s = _native.score_fwd(x, ent, bias)
-        ctx.save_for_backward(x, ent, s)
-        return s
-
-    @staticmethod
-    def backward(ctx, gs):
-        x, ent, s = ctx.saved_tensors
-        gz = (gs * s * (1.0 - s)).contiguous()
-        gzt = gz.t().contiguous() if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) else None
-        gx = None
-        if ctx.needs_input_grad[0]:
-            # gx = gz [B, N] @ ent [N, O]: the reduction runs over the N entities, so it goes to the split-K transposed kernel
-            # (K = N rows over <= 256 workgroups, partial products folded in order) — not to mgcn_matmul_f32's small-matrix
-            # kernel, whose one lane would walk all N terms in one sequential chain
-            gx = _native.matmul_tn(gzt, ent.contiguous()) if _native.matmul_tn_supported(gz.size(0), ent.size(1)) \
-                else _native.matmul(gz, ent.contiguous())
-        return (gx, _native.matmul(gzt, x.contiguous()) if ctx.needs_input_grad[1] else None,
-                gz.sum(0) if ctx.needs_input_grad[2] else None)
+def table_bce_stage(model, x, ent, bias, keys, index, lbl_smooth, num_entities, row0=0, world=1):
+    """The full-table BCE of MGCN.forward_loss and dist.train_step_sharded from the trunk output x [B, O]: `ent` / `bias` are
+    this rank's entity rows [row0, row0 + ent.size(0)) of `num_entities`, `keys` the queries' keys in `index`. One fused launch
+    (_ScoreBCEFn) where it takes the batch, else label_rows + _ScoreFn and the BCE in torch: BCELoss's mean with one rank, with
+    several the rank's sum over the global count, so that the ranks' parts add up. A rank without rows scores nothing and still
+    takes part in the backward's collectives."""
+    n = ent.size(0)
+    if n == 0:
+        return (x * 0.0).sum()
+    if x.is_cuda and _native.score_bce_supported(x, ent):
+        hot, cold = _native.smoothed_targets(lbl_smooth, num_entities)
+        mask = _native.filter_mask(keys, index.keys, index.ptr, index.tails, n, ent_row0=row0)
+        return _ScoreBCEFn.apply(x, ent, bias, mask, hot, cold, num_entities)
+    labels = _native.label_rows(keys, index.keys, index.ptr, index.tails, n, lbl_smooth=lbl_smooth, num_entities=num_entities,
+                                ent_row0=row0)
+    scores = _ScoreFn.apply(x, ent, bias)
+    if world == 1:
+        return model.loss_fn(scores, labels)
+    return F.binary_cross_entropy(scores, labels, reduction='sum') * (1.0 / (x.size(0) * num_entities))
 
 
-class _ScoreBCEFn(torch.autograd.Function):
-    """mean BCE(sigmoid(x @ ent^T + bias), targets) in ONE launch: the scores and the [B, N] targets are
-    never materialised; the launch leaves d loss / d logits [N, B], the backward is two products on the HIP MFMA kernels
-    (G x on the tile kernel, G^T ent on the split-K transposed kernel) and a row sum.
-    The incoming gradient is a scalar (a Python-scalar loss weight arrives as a 0-dim tensor, in any 0-dim view): it multiplies the
-    three results by broadcasting and reaches no kernel."""
-
-    @staticmethod
-    def forward(ctx, x, ent, bias, mask, hot, cold):
-        loss, g = _native.score_bce_fwd(x, ent, bias, mask, hot, cold)
-        ctx.save_for_backward(x, ent, g)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gl):
-        x, ent, g = ctx.saved_tensors
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = (_native.matmul_tn(g, ent.contiguous()) if _native.matmul_tn_supported(g.size(1), ent.size(1))
-                  else _native.matmul(g.t().contiguous(), ent.contiguous())) * gl
-        return (gx,
-                _native.matmul(g, x) * gl if ctx.needs_input_grad[1] else None,
-                g.sum(1) * gl if ctx.needs_input_grad[2] else None, None, None, None)
+def refuse_list_step(what, model, num_queries, cand, labels, loss, logq):
+    """The refusals that MGCN.forward_loss_candidates and dist.train_step_sharded_candidates share, raised before any launch or
+    collective of the step; returns the candidate block."""
+    if loss not in ('bce', 'softmax'):
+        raise _native.NativeError("%s: loss must be 'bce' or 'softmax', got %r" % (what, loss))
+    if logq is not None:
+        if loss != 'softmax':
+            raise _native.NativeError("%s: logq corrects the softmax only; loss='bce' takes weighted lists as they are" % what)
+        bias = model.conv2.bias
+        if logq.dtype != torch.float32 or tuple(logq.shape) != tuple(bias.shape) or logq.device != bias.device:
+            raise _native.NativeError('%s: logq must be f32 %s on %s' % (what, tuple(bias.shape), bias.device))
+    cand = model._candidate_block(cand, num_queries)
+    if labels is not None and (labels.dtype not in (torch.uint8, torch.bool) or tuple(labels.shape) != tuple(cand.shape)):
+        raise _native.NativeError('%s: labels must be uint8 / bool %s' % (what, tuple(cand.shape)))
+    return cand
 
 
-class _CandBCEFn(torch.autograd.Function):
-    """mean BCE over per-query candidate lists (include/mgcn_hip.h (14)): one launch leaves the loss partials and d loss / d logit
-    [B, K]; the backward is two fixed-order sums on the kernels of csrc/query_train.hip, d x over the gathered entity rows and
-    d ent / d bias over the runs of a sorted plan into a zeroed block. Nothing of size [B, N] exists; no float atomics.
-    The incoming gradient is a scalar in any 0-dim view: it is folded into g [B, K] by broadcasting (g * gl, a fresh contiguous
-    tensor) and reaches no kernel itself."""
-
-    @staticmethod
-    def forward(ctx, x, ent, bias, cand, label, hot, cold):
-        loss, g = _native.cand_bce_fwd(x, ent, bias, cand, label, hot, cold)
-        # (no host read of the live count: the whole plan is handed over, its dead tail is skipped entry by entry)
-        perm, ctx.n_live = _native.cand_plan(cand, ent.size(0), count=False)
-        ctx.save_for_backward(x, ent, cand, g, perm)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gl):
-        x, ent, cand, g, perm = ctx.saved_tensors
-        # d x gl, d ent gl, d bias gl with gl folded into g [B, K] first: the sums are linear in g, and the [N, dim] block is
-        # written once instead of being scaled in a second pass (gl = 1, the usual case, changes no bit of g)
-        g = g * gl
-        gx = _native.cand_bce_bwd_x(g, cand, ent) if ctx.needs_input_grad[0] else None
-        want = tuple(n for i, n in ((1, 'ent'), (2, 'bias')) if ctx.needs_input_grad[i])
-        d_ent, d_bias = (None, None)
-        if want:
-            d_ent, d_bias = _native.cand_bce_bwd_ent(g, cand, x, perm, ctx.n_live, ent.size(0), want=want)
-        return (gx, d_ent, d_bias, None, None, None, None)
-
-
-class _CandCEFn(torch.autograd.Function):
-    """softmax cross-entropy over per-query candidate lists (include/mgcn_hip.h (16)): logits and per-chunk statistics, their
-    merge per row, then d loss / d logit [B, K] and the loss partials; the backward is _CandBCEFn's, on that g. `eps` smooths
-    over the list. Nothing of size [B, N] exists; no float atomics. The incoming scalar gradient is handled as in _CandBCEFn."""
-
-    @staticmethod
-    def forward(ctx, x, ent, bias, cand, label, eps):
-        z, stat = _native.cand_ce_logits(x, ent, bias, cand, label)
-        loss, g, _ = _native.cand_ce_finish(z, cand, label, _native.cand_ce_merge(stat), eps, ent.size(0))
-        perm, ctx.n_live = _native.cand_plan(cand, ent.size(0), count=False)
-        ctx.save_for_backward(x, ent, cand, g, perm)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gl):
-        return _CandBCEFn.backward(ctx, gl)[:6]
+def list_loss_stage(x, ent, bias, cand, labels, index, keys, lbl_smooth, loss, logq, num_entities, row0=0, ex=None):
+    """The scoring stage of MGCN.forward_loss_candidates and dist.train_step_sharded_candidates from the trunk output x [B, O]:
+    `ent` / `bias` are this rank's entity rows [row0, row0 + ent.size(0)) of `num_entities`, cand [B, K] the lists, `labels`
+    their [B, K] block or None (looked up for the rank's rows in `index` under the queries' `keys`), `logq` the whole table's or
+    None, `ex` the sharded step's exchange. BCE smooths with the global count; the softmax is handed bias - logq of the rank's
+    rows. A rank without rows scores nothing under BCE and still takes part in the backward's collectives; under the softmax it
+    passes the empty statistic on (_CandCEFn), so it joins the all-gather."""
+    n = ent.size(0)
+    if loss == 'bce' and n == 0:
+        return (x * 0.0).sum()
+    if logq is not None:
+        bias = bias - logq[row0:row0 + n]
+    x = x if x.stride(-1) == 1 else x.contiguous()
+    if labels is None:
+        labels = _native.cand_labels(keys, index.keys, index.ptr, index.tails, cand, n, ent_row0=row0)
+    if loss == 'softmax':
+        return _CandCEFn.apply(x, ent, bias, cand, labels, float(lbl_smooth), row0, ex)
+    hot, cold = _native.smoothed_targets(lbl_smooth, num_entities)
+    return _CandBCEFn.apply(x, ent, bias, cand, labels, hot, cold, row0)
 
 
 class MGCNConv(nn.Module):
@@ -608,7 +391,7 @@ class ConvE(nn.Module):
     def _trunk_train(self, src_emb, rel_emb, generator, drop_ctx=None):
         src_emb = src_emb if src_emb.stride(1) == 1 else src_emb.contiguous()
         rel_emb = rel_emb if rel_emb.stride(1) == 1 else rel_emb.contiguous()
-        # the feature mask is drawn first, then the hidden one: dist._dropout's draws, on tensors of the activations' shapes
+        # the feature mask is drawn first, then the hidden one: dist._trunk's draws, on tensors of the activations' shapes
         p, keep, inv_keep = self.feature_drop.p, None, 1.0
         shape = (src_emb.size(0), self.flat_sz)
         if drop_ctx is not None and p > 0:
@@ -835,9 +618,10 @@ class MGCN(nn.Module):
         self._slot_csr = None
         self._enc_cache = None
 
-    def _refuse_training_ee16(self, what):
-        """bf16 per-edge tables are inference-only: raised before any launch of a training-mode call."""
-        if self.training and _native.is_ee16(self.edge_embeddings):
+    def _refuse_training_ee16(self, what, training=None):
+        """bf16 per-edge tables are inference-only: raised before any launch of a training-mode call (`training`: the call
+        trains whatever the mode, as the sharded steps do)."""
+        if (self.training if training is None else training) and _native.is_ee16(self.edge_embeddings):
             raise _native.NativeError('%s: this model holds its per-edge tables in bf16 (params.edge_table_dtype), which is '
                                       'inference-only; train the f32 model and load its checkpoint into this one' % what)
 
@@ -1035,15 +819,8 @@ class MGCN(nn.Module):
         self._refuse_training_ee16('MGCN.forward_loss')
         all_ent, all_rel = self.encode(data)
         x = self.conv2.trunk(query_rows(self, all_ent, src), query_rows(self, all_rel, rel))
-        n_ent = all_ent.size(0)
         keys = index.query_keys(src, rel)
-        ent = all_ent.contiguous()
-        if x.is_cuda and _native.score_bce_supported(x, ent):
-            hot, cold = _native.smoothed_targets(lbl_smooth, n_ent)
-            mask = _native.filter_mask(keys, index.keys, index.ptr, index.tails, n_ent)
-            return _ScoreBCEFn.apply(x, ent, self.conv2.bias, mask, hot, cold)
-        labels = _native.label_rows(keys, index.keys, index.ptr, index.tails, n_ent, lbl_smooth=lbl_smooth)
-        return self.loss_fn(_ScoreFn.apply(x, ent, self.conv2.bias), labels)
+        return table_bce_stage(self, x, all_ent.contiguous(), self.conv2.bias, keys, index, lbl_smooth, all_ent.size(0))
 
     def forward_loss_candidates(self, src, rel, cand, data, index=None, labels=None, lbl_smooth=0.0, loss='bce', logq=None):
         """forward_loss with a per-query candidate list in place of the entity table (training on sampled negatives): the mean
@@ -1064,31 +841,14 @@ class MGCN(nn.Module):
         logq of zeros leaves every bit as it is. The BCE takes weighted lists WITHOUT a correction (the word2vec convention):
         logq with loss='bce' is refused."""
         self._refuse_training_ee16('MGCN.forward_loss_candidates')
-        if loss not in ('bce', 'softmax'):
-            raise _native.NativeError("forward_loss_candidates: loss must be 'bce' or 'softmax', got %r" % (loss,))
-        if logq is not None:
-            if loss != 'softmax':
-                raise _native.NativeError("forward_loss_candidates: logq corrects the softmax only; loss='bce' takes weighted lists as they are")
-            bias = self.conv2.bias
-            if logq.dtype != torch.float32 or tuple(logq.shape) != tuple(bias.shape) or logq.device != bias.device:
-                raise _native.NativeError('forward_loss_candidates: logq must be f32 %s on %s' % (tuple(bias.shape), bias.device))
         if (index is None) == (labels is None):
             raise _native.NativeError('forward_loss_candidates: give exactly one of index / labels')
-        cand = self._candidate_block(cand, src.numel())
+        cand = refuse_list_step('forward_loss_candidates', self, src.numel(), cand, labels, loss, logq)
         all_ent, all_rel = self.encode(data)
         x = self.conv2.trunk(query_rows(self, all_ent, src), query_rows(self, all_rel, rel))
-        n_ent = all_ent.size(0)
-        ent = all_ent.contiguous()
-        x = x if x.stride(-1) == 1 else x.contiguous()
-        if labels is None:
-            labels = _native.cand_labels(index.query_keys(src, rel), index.keys, index.ptr, index.tails, cand, n_ent)
-        elif labels.dtype not in (torch.uint8, torch.bool) or tuple(labels.shape) != tuple(cand.shape):
-            raise _native.NativeError('forward_loss_candidates: labels must be uint8 / bool %s' % (tuple(cand.shape),))
-        if loss == 'softmax':
-            bias = self.conv2.bias if logq is None else self.conv2.bias - logq
-            return _CandCEFn.apply(x, ent, bias, cand, labels, float(lbl_smooth))
-        hot, cold = _native.smoothed_targets(lbl_smooth, n_ent)
-        return _CandBCEFn.apply(x, ent, self.conv2.bias, cand, labels, hot, cold)
+        keys = index.query_keys(src, rel) if labels is None else None
+        return list_loss_stage(x, all_ent.contiguous(), self.conv2.bias, cand, labels, index, keys, lbl_smooth, loss, logq,
+                               all_ent.size(0))
 
     # -- fused evaluation path (main.py:121-126 without materialising [B, N] scores) -------------
     @torch.no_grad()

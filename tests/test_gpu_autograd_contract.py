@@ -1,16 +1,17 @@
-"""The torch.autograd.Function classes of kgc-gcn_amd/model.py and kgc-gcn_amd/dist.py on a real MI355X, held to what autograd may
+"""The torch.autograd.Function classes of kgc-gcn_amd/autograd.py and kgc-gcn_amd/dist.py on a real MI355X, held to what autograd may
 hand them rather than to what loss.backward() of the production graph happens to: (1) every layout of the upstream gradient gives
 the bits of the contiguous one and leaves the handed tensor alone, (2) freezing inputs changes no bit of what is still computed,
 (3) a scalar loss weight scales exactly (powers of two), within the family's bar times |gl| (3.0), and the same as a tensor,
 (4) a random upstream gradient meets the float64 restatement of the Function's formula, (5) two backwards through one graph give
-the same bits and leave the saved tensors alone, (6) the shard forms at world 1 give the bits of the plain forms. Cases, layouts,
+the same bits and leave the saved tensors alone, (6) the shard forms (the rank's rows and a world-1 exchange made explicit) give the bits of
+the plain forms (every trailing argument at its default). Cases, layouts,
 restatements and bars: tests/autograd_ref.py (checked on the CPU by tests/test_autograd_ref_host.py). Every float64 check prints
 `RATIO family id worst / bar` (pytest -s) before it asserts.
 
 Which layouts reach a kernel uncopied (asserted in test_gradient_layouts where a wrapper call shows it, HANDED_THROUGH):
   _TrunkTrainFn, _QueryRowsFn, _TrunkTailFn, _CounterDropoutFn    (a) (b) (c) (e) as they are; (d) (f) (g) copied;
-  _AggregateFn, _ShardAggregateFn, _GatherRowsFn                  (a) (e) as they are; (b) (c) (d) (f) (g) copied;
-  _LayerTrainFn, _ShardLayerTrainFn                               the same, the copy being _native._bn_grad's / .contiguous();
+  _AggregateFn (plain, with node_range), _GatherRowsFn            (a) (e) as they are; (b) (c) (d) (f) (g) copied;
+  _LayerTrainFn (plain, with an exchange)                         the same, the copy being _native._bn_grad's / .contiguous();
   _ScoreFn                                                        none: torch's gs * s * (1 - s) reads any layout, the kernels its result;
   _AllReduceGradFn                                                every layout copied; _RankZeroGradFn: every layout handed on, no kernel;
   the loss Functions                                              a scalar, folded in by broadcasting.
@@ -159,7 +160,7 @@ def matrix_specs(pkg):
     shard = lambda k, t: csr.edge_table_shard(slot(k, t), 0, N) if k == 'ee' else t
     specs.append(Spec('aggregate', agg, lambda l, s: M._AggregateFn.apply(l['x'], l['rel'], l['ee'], csr), prepare=slot,
                       check64=_agg_check(pkg, False)))
-    specs.append(Spec('shard_aggregate', agg, lambda l, s: Dm._ShardAggregateFn.apply(l['x'], l['rel'], l['ee'], csr, 0, N), prepare=shard,
+    specs.append(Spec('shard_aggregate', agg, lambda l, s: M._AggregateFn.apply(l['x'], l['rel'], l['ee'], csr, (0, N)), prepare=shard,
                       check64=_agg_check(pkg, True)))
 
     lay = AR.layer_case()
@@ -172,7 +173,7 @@ def matrix_specs(pkg):
             with torch.random.fork_rng(devices=[0]):      # (the session's generators are left as they were)
                 torch.manual_seed(20260101)     # the torch-mask form draws from the device generator: the same masks every call
                 if sharded:
-                    return Dm._ShardLayerTrainFn.apply(*a, _exchange(pkg, AR.LAYER_N), drop_keys)
+                    return M._LayerTrainFn.apply(*a, drop_keys, _exchange(pkg, AR.LAYER_N))
                 return M._LayerTrainFn.apply(*a, drop_keys)
         return call
     st = dict(rm=e['rm'], rv=e['rv'])
@@ -231,20 +232,20 @@ def loss_specs(pkg):
         hot, cold = pkg._native.smoothed_targets(case.extra['smooth'], n)
         assert (hot, cold) == AR.smoothed(case.extra['smooth'], n)
         out[case.name] = (Spec(case.name, case, lambda l, s, mask=mask, hot=hot, cold=cold: M._ScoreBCEFn.apply(l['x'], l['ent'], l['bias'], mask, hot, cold)),
-                          Spec(case.name + '_shard', case, lambda l, s, mask=mask, hot=hot, cold=cold, n=n: Dm._ScoreBCEShardFn.apply(
+                          Spec(case.name + '_shard', case, lambda l, s, mask=mask, hot=hot, cold=cold, n=n: M._ScoreBCEFn.apply(
                               l['x'], l['ent'], l['bias'], mask, hot, cold, n)), AR.score_bce_reference)
     case = AR.cand_bce_case()
     e = case.extra
     cand, label = e['cand'].to(DEV), e['label'].to(DEV)
     out['cand_bce'] = (Spec('cand_bce', case, lambda l, s: M._CandBCEFn.apply(l['x'], l['ent'], l['bias'], cand, label, e['hot'], e['cold'])),
-                       Spec('cand_bce_shard', case, lambda l, s: Dm._CandBCEShardFn.apply(l['x'], l['ent'], l['bias'], cand, label, e['hot'], e['cold'], 0)),
+                       Spec('cand_bce_shard', case, lambda l, s: M._CandBCEFn.apply(l['x'], l['ent'], l['bias'], cand, label, e['hot'], e['cold'], 0)),
                        AR.cand_bce_reference)
     case2 = AR.cand_ce_case()
     e2 = case2.extra
     cand2, label2 = e2['cand'].to(DEV), e2['label'].to(DEV)
     ex = _exchange(pkg, e2['N'])
     out['cand_ce'] = (Spec('cand_ce', case2, lambda l, s: M._CandCEFn.apply(l['x'], l['ent'], l['bias'], cand2, label2, e2['eps'])),
-                      Spec('cand_ce_shard', case2, lambda l, s: Dm._CandCEShardFn.apply(l['x'], l['ent'], l['bias'], cand2, label2, e2['eps'], 0, ex)),
+                      Spec('cand_ce_shard', case2, lambda l, s: M._CandCEFn.apply(l['x'], l['ent'], l['bias'], cand2, label2, e2['eps'], 0, ex)),
                       AR.cand_ce_reference)
     return out
 

@@ -91,10 +91,10 @@ def test_world1_equals_one_gpu_step_at_counter_dropout(pkg, monkeypatch):
 
 # -- one process playing three ranks on the scoring stage ----------------------------------------------------------------
 def _score(pkg, x, ent, bias, cand, label, hot, cold, n0, n1):
-    """(loss, g, dx, d_ent, d_bias) of _CandBCEShardFn on rows [n0, n1)."""
+    """(loss, g, dx, d_ent, d_bias) of _CandBCEFn on rows [n0, n1)."""
     xs = x.clone().requires_grad_(True)
     es, bs = ent[n0:n1].clone().requires_grad_(True), bias[n0:n1].clone().requires_grad_(True)
-    loss = pkg.dist._CandBCEShardFn.apply(xs, es, bs, cand, label, hot, cold, n0)
+    loss = pkg.model._CandBCEFn.apply(xs, es, bs, cand, label, hot, cold, n0)
     g = loss.grad_fn.saved_tensors[3]
     loss.backward()
     return loss.detach(), g, xs.grad, es.grad, bs.grad

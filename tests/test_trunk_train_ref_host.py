@@ -1,5 +1,5 @@
 """tests/trunk_train_ref.py checked on the CPU (`-m "not gpu"`): the float64 reference against the torch modules of ConvE
-in float64 with the same masks, the masks' draw order against dist._dropout, the bars against their vacuity caps, what
+in float64 with the same masks, the masks' draw order against model._drawn_dropout (dist._trunk's draws), the bars against their vacuity caps, what
 the training-mode trunk's entry points (paragraph (9) of include/mgcn_hip.h) do without a GPU, and the limit cases: their
 launch arithmetic, the two conditions on their inputs (caps, relu margin) and four faults that must break a bar there."""
 import copy
