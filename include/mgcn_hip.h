@@ -294,7 +294,17 @@ int mgcn_dense_bn_tanh_fwd(int64_t num_nodes, int32_t dim_in, int32_t dim_out, c
  * generation 3: staging buffers (1..4), generation 4: slots per gather batch (2 / 4 / 8); bits 8-9 relation table in LDS
  * (1 = never); bits 10-11 force a generation (1 = generation 4, 2, 3; wp_dev must then come from mgcn_pack_weights_gen for
  * it); bits 12-13 generation 3: input columns per slot walk (0 or 1 = 128, 2 = 256), generation 4: phase groups of its
- * stagger (1 = none, 0 or 2 = two, 3 = four).
+ * stagger (1 = none, 0 or 2 = two, 3 = four); bit 14 generations 2 and 3: the legacy column cut (below).
+ * Column cut. Generations 2 and 3 (128-column walk) gather a mode's dim_in columns in chunks of at most 128, one slot walk per
+ * chunk, every chunk starting on a k-block (32 columns). Rows of the layer input lie 4 * dim_in bytes apart, so the 128-byte
+ * lines a chunk touches depend on where it starts. For 128 < dim_in <= 256 the boundary is the multiple of 32 columns (neither
+ * chunk above 128) that minimises the mean number of lines per row over the row offsets that stride produces (the multiples
+ * of gcd(4 * dim_in, 128)); ties go to the more balanced cut, then to the wider first chunk: dim_in = 200 is cut 96 | 104. Every
+ * other width keeps chunks of 128 with the last one short. Where a mode has more than one chunk, lanes past a chunk's width load
+ * that chunk's last float4 (and store zeros), so no lane touches a line its pass does not need; a single chunk (dim_in <= 128)
+ * keeps them on columns 0-3, which its pass fetches anyway. The legacy cut (`tune` bit 14; MGCN_FUSED_CUT=legacy in the Python
+ * binding) is 128 | rest with those lanes on columns 0-3 of the row. The k-blocks, their order and the packed weights do not
+ * depend on the cut: rows are bit-identical either way. mgcn_fused_cut reports the cut and its modelled lines.
  * status_dev (optional, one zero-initialised uint32 in device memory): generation 3 couples its roles through LDS counters
  * with BOUNDED spins; a spin that runs out (a wave parked for ~0.1 s by a debugger, a preemption, or a protocol error)
  * lets its wave go on, the rows of that tile are then garbage, and bit 0 of *status_dev is set: callers check the word at
@@ -311,6 +321,12 @@ int mgcn_dense_bn_tanh_fwd(int64_t num_nodes, int32_t dim_in, int32_t dim_out, c
 /* The kernel a launch of (2b) over num_rows destinations takes with `tune` bits 10-11 = 0: 2 (layer_fused2.hip) or 3
  * (layer_fused3.hip). Informational (profiles, benchmarks name the kernel they measured). */
 int mgcn_fused_kernel_generation(int32_t dim_in, int32_t dim_out, int64_t num_rows, int32_t with_row_bounds);
+/* The column cut of (2b) for dim_in input columns (legacy != 0: the legacy cut), no device work. Returns the number of chunks
+ * and writes each chunk's first column and width to col0_out / ncol_out [max_chunks] (either may be NULL) and the modelled mean
+ * number of 128-byte lines one input row costs per mode, idle lanes included, to *mean_lines_out (may be NULL); -1 for a width no
+ * fused kernel takes or more chunks than max_chunks. */
+int mgcn_fused_cut(int32_t dim_in, int32_t legacy, int32_t *col0_out, int32_t *ncol_out, int32_t max_chunks,
+                   double *mean_lines_out);
 int mgcn_layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, int32_t dim_out,
                          int32_t num_rel_rows, const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev,
                          const float *x_dev, int64_t ldx, const float *rel_dev, const float *loop_rel_dev,

@@ -76,6 +76,7 @@ _SIGNATURES = {
     'mgcn_score_bce_partials': (_i64, [_i32, _i64]),
     'mgcn_hub_partial_floats': (_i64, [_i64, _i32]),
     'mgcn_fused_kernel_generation': (ctypes.c_int, [_i32, _i32, _i64, _i32]),
+    'mgcn_fused_cut': (ctypes.c_int, [_i32, _i32, _ptr, _ptr, _i32, _ptr]),
     'mgcn_score_bce_fwd': (ctypes.c_int, [_i32, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _f32, _f32, _f32, _ptr,
                                           _i64, _ptr, _ptr]),
     'mgcn_label_rows': (ctypes.c_int, [_i32, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _f32, _f32, _ptr, _i64, _ptr]),
@@ -496,8 +497,23 @@ def dense_bn_tanh_fwd(a, w_cat, bias, bn_mean, bn_var, bn_gamma, bn_beta, eps, o
 
 # `tune` argument of mgcn_layer_fwd_fused (include/mgcn_hip.h): 0 = automatic. Read ONCE at import, for A/B tools only (see
 # INTEGRATION.md "Environment switches"): bits 0-3 row tiles per tile, 4-7 staging buffers / slots per batch, 8-9 relation
-# table in LDS, 10-11 a forced kernel generation (1 = 4, 2, 3), 12-13 columns per slot walk.
+# table in LDS, 10-11 a forced kernel generation (1 = 4, 2, 3), 12-13 columns per slot walk, 14 the legacy column cut.
 FUSED_TUNE = int(os.environ.get('MGCN_FUSED_TUNE', '0'), 0)
+# `tune` bit 14: the legacy column cut of the fused layer kernels (128-column chunks, idle lanes on the row's head) instead of
+# the one that follows the row stride (include/mgcn_hip.h (2b)); same rows either way. MGCN_FUSED_CUT=legacy, read ONCE at
+# import, sets it in every launch: for A/B runs.
+FUSED_CUT_LEGACY = 1 << 14
+FUSED_CUT = FUSED_CUT_LEGACY if os.environ.get('MGCN_FUSED_CUT', '') == 'legacy' else 0
+
+
+def fused_cut(dim_in, legacy=False):
+    """The column cut of a `dim_in`-wide fused layer (mgcn_fused_cut, no device work): ([(first column, columns), ...], modelled
+    mean 128-byte lines one input row costs per mode)."""
+    col0, ncol, lines = (_i32 * 8)(), (_i32 * 8)(), ctypes.c_double(0.0)
+    n = lib().mgcn_fused_cut(int(dim_in), int(bool(legacy)), col0, ncol, 8, ctypes.byref(lines))
+    if n < 0:
+        raise NativeError('fused_cut: no fused kernel takes %d input columns' % dim_in)
+    return [(col0[i], ncol[i]) for i in range(n)], lines.value
 
 
 def tune_generation(tune=None):
@@ -635,7 +651,7 @@ def layer_fwd_fused(csr, x, rel, loop_rel, ee, ee_in_slot_order, loop_edge, w_pa
         if not ee_in_slot_order or tuple(ee.shape) != (sum(rows), D) or not ee.is_contiguous() or \
                 ee_sub != csr.shard_ee_sub(n0, n1):
             raise NativeError('layer_fwd_fused: per-edge shard does not match destinations [%d, %d)' % (n0, n1))
-    tune = FUSED_TUNE if tune is None else int(tune)
+    tune = (FUSED_TUNE if tune is None else int(tune)) | FUSED_CUT
     if not rel.is_contiguous() or w_packed.numel() * 4 < lib().mgcn_packed_weights_bytes_gen(tune_generation(tune), D, O):
         raise NativeError('layer_fwd_fused: rel must be contiguous and w_packed sized by mgcn_packed_weights_bytes')
     for v in (bn_mean, bn_var, bn_gamma, bn_beta) + ((bias,) if bias is not None else ()):

@@ -47,6 +47,87 @@ struct LayerArgs {
   float *rel_out;         // [rel_rows - 1, O]
 };
 
+// ---------------------------------------------------------------------------------------------- the column cut
+// A gather pass ("chunk") covers at most 128 consecutive input columns: one float4 per lane of a 32-lane group. Generations 2
+// and 3 walk a mode's columns in the chunks of this table; a chunk starts on a k-block (32 columns), so every MFMA sees the
+// 32 columns it always saw, in the same order, whatever the cut: rows do not depend on it.
+//   col0 / ncol  first column and width of the chunk (ncol a multiple of 4, <= 128)
+//   kb0 / nkb    its first k-block within the mode (col0 / 32) and its k-blocks (ceil(ncol / 32))
+//   cidle        the column that lanes with 4 * lig >= ncol load (they store zeros): the chunk's last valid float4, so that no
+//                lane leaves the lines its pass fetches anyway — or 0, the row's head (the legacy walk)
+constexpr int FUSED_TUNE_LEGACY_CUT = 1 << 14;   // `tune` bit 14 (include/mgcn_hip.h): the legacy cut, for A/B runs
+constexpr int CUT_MAXCH = 8;   // D <= 1024
+struct CutTable {
+  int32_t col0[CUT_MAXCH], ncol[CUT_MAXCH], kb0[CUT_MAXCH], nkb[CUT_MAXCH], cidle[CUT_MAXCH];
+};
+struct FusedCut {
+  int nch;
+  CutTable t;
+};
+// The table as the kernels read it: one byte per chunk in a 64-bit kernel argument, kb0 | (nkb - 1) << 5, so that the roles'
+// control values come out of two scalar registers with shifts (a table in memory put a scalar load and its wait in front of every
+// k-block's weight prefetch: +1 us per launch, measured). col0 = 32 kb0, ncol = min(32 nkb, d - col0); the idle lanes' column is
+// the chunk's last float4 where `clamp` is set, else 0.
+inline uint64_t cut_pack(const CutTable &t, int nch) {
+  uint64_t w = 0;
+  for (int i = 0; i < nch; ++i) w |= uint64_t(t.kb0[i] | (t.nkb[i] - 1) << 5) << (8 * i);
+  return w;
+}
+__device__ __forceinline__ int cut_kb0(uint64_t w, int c) { return int(w >> (8 * c)) & 31; }
+__device__ __forceinline__ int cut_nkb(uint64_t w, int c) { return ((int(w >> (8 * c)) >> 5) & 7) + 1; }
+__device__ __forceinline__ int cut_ncol(uint64_t w, int c, int d) {
+  const int n = 32 * cut_nkb(w, c), left = d - 32 * cut_kb0(w, c);
+  return n < left ? n : left;
+}
+// The line model behind the cut: rows of d floats lie 4 d bytes apart, so a row starts at byte o of a 128-byte line for every o
+// that is a multiple of gcd(4 d, 128), each as often as the others. A pass over columns [c0, c0 + n) of such a row touches the
+// lines of bytes [o + 4 c0, o + 4 (c0 + n)), plus — when it has idle lanes (n < 128) — the line of the float4 they load, where
+// that is none of them. Returns the lines of all chunks summed over the 128 / gcd offsets; *noff = that number of offsets.
+inline int cut_lines(int d, const FusedCut &c, int *noff) {
+  int g = 128;
+  for (int r = (4 * d) % 128; r; ) { const int t = g % r; g = r; r = t; }
+  int total = 0;
+  for (int o = 0; o < 128; o += g) {
+    for (int i = 0; i < c.nch; ++i) {
+      const int b0 = o + 4 * c.t.col0[i], b1 = b0 + 4 * c.t.ncol[i] - 1;
+      total += (b1 >> 7) - (b0 >> 7) + 1;
+      const int il = (o + 4 * c.t.cidle[i]) >> 7;
+      if (c.t.ncol[i] < 128 && (il < (b0 >> 7) || il > (b1 >> 7))) ++total;
+    }
+  }
+  if (noff) *noff = 128 / g;
+  return total;
+}
+// The cut of a d-column mode. Legacy: chunks of 128 columns, the last one short, idle lanes on column 0. Otherwise the same
+// chunks with the idle lanes on their chunk's last float4, except for 128 < d <= 256 (two chunks, of which the 200-wide layer
+// is the case that matters): there the boundary is the multiple of 32 columns, with neither chunk above 128, that minimises
+// cut_lines; ties go to the more balanced cut, then to the wider first chunk. d = 200 (offsets 0, 32, 64, 96): 128 | 72 costs
+// 4.75 + 3 lines and 96 | 104 costs 3.75 + 4 — a tie that the balance decides for 96 | 104 (24 and 26 busy lanes instead of
+// 32 and 18); the legacy walk pays 8.75, its idle lanes of the second pass fetching the row's first line again.
+inline FusedCut fused_cut(int d, bool legacy) {
+  auto two = [&](int b) {       // chunks [0, b) and [b, d); b = d: one chunk
+    FusedCut c = {};
+    int col = 0;
+    while (col < d) {
+      const int n = (c.nch == 0 && b < d) ? b : (d - col < 128 ? d - col : 128);
+      c.t.col0[c.nch] = col; c.t.ncol[c.nch] = n; c.t.kb0[c.nch] = col / 32; c.t.nkb[c.nch] = (n + 31) / 32;
+      c.t.cidle[c.nch] = (legacy || b >= d) ? 0 : col + n - 4;
+      col += n;
+      ++c.nch;
+    }
+    return c;
+  };
+  FusedCut best = two(d < 128 ? d : 128);
+  if (legacy || d <= 128 || d > 256) return best;
+  int best_lines = cut_lines(d, best, nullptr), best_skew = 2 * 128 > d ? 2 * 128 - d : d - 2 * 128;
+  for (int b = 96; b >= 32 && d - b <= 128; b -= 32) {
+    const FusedCut c = two(b);
+    const int lines = cut_lines(d, c, nullptr), skew = 2 * b > d ? 2 * b - d : d - 2 * b;
+    if (lines < best_lines || (lines == best_lines && skew < best_skew)) { best = c; best_lines = lines; best_skew = skew; }
+  }
+  return best;
+}
+
 inline void fill_layer_args(LayerArgs &p, const mgcn::FusedLaunch &a) {
   p.rowptr = a.rowptr; p.rec = reinterpret_cast<const int4 *>(a.rec);
   p.x = a.x; p.rel = a.rel; p.loop_rel = a.loop_rel; p.ee = static_cast<const float *>(a.ee); p.loop_edge = a.loop_edge;

@@ -67,6 +67,26 @@ extern "C" int mgcn_fused_kernel_generation(int32_t dim_in, int32_t dim_out, int
   return (with_row_bounds && few_tiles && dim_out > 128) ? 3 : 2;
 }
 
+// The column cut generations 2 and 3 (128-column walk) take for dim_in input columns (fused_common.h: fused_cut), no device
+// work: the number of chunks, or -1 for a width no kernel takes or more chunks than max_chunks; col0_out / ncol_out [max_chunks]:
+// each chunk's first column and width; mean_lines_out: the modelled 128-byte lines one row of the layer input costs per mode.
+extern "C" int mgcn_fused_cut(int32_t dim_in, int32_t legacy, int32_t *col0_out, int32_t *ncol_out, int32_t max_chunks,
+                              double *mean_lines_out) {
+  if (dim_in <= 0 || dim_in % 4 != 0 || dim_in > 1024) return -1;
+  const FusedCut c = fused_cut(dim_in, legacy != 0);
+  if (c.nch > max_chunks && (col0_out || ncol_out)) return -1;
+  for (int i = 0; i < c.nch; ++i) {
+    if (col0_out) col0_out[i] = c.t.col0[i];
+    if (ncol_out) ncol_out[i] = c.t.ncol[i];
+  }
+  if (mean_lines_out) {
+    int noff = 1;
+    const int lines = cut_lines(dim_in, c, &noff);
+    *mean_lines_out = double(lines) / noff;
+  }
+  return c.nch;
+}
+
 namespace {
 // All four entry points. live_rowptr_dev / live_rec_dev: the live view the main walk takes (null: the canonical layout); the hub
 // pre-pass reads the canonical records either way. ee16: ee_dev is a bf16 table (include/mgcn_hip.h (2e)).

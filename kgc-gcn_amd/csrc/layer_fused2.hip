@@ -15,7 +15,7 @@
 //              6 * NRT MFMAs; the operands are swapped (W as the A operand) so that a lane ends up with four
 //              consecutive output columns of one row: the epilogue (/3, bias, BN eval, tanh: model.py:103-106)
 //              runs on the accumulators and stores 16 bytes per lane.
-// Stage = (mode, 128-column chunk of the input): the gather waves fill LDS image (s + 1) & 1 while the MFMA waves
+// Stage = (mode, chunk of at most 128 input columns: the column cut of fused_common.h): the gather waves fill LDS image (s + 1) & 1 while the MFMA waves
 // multiply image s & 1; one workgroup barrier per stage (all workgroups walk the weights in lockstep, which keeps the
 // packed weights L2-resident between the step's alternating layers: why this kernel, not layer_fused3.hip, takes the
 // shapes with D <= 256, O <= 208 — measured), the pipeline runs across modes and tiles.
@@ -31,7 +31,9 @@ namespace {
 constexpr int T2 = 1024;   // 8 MFMA waves + 8 gather waves: two of each per SIMD, 128 VGPRs per wave
 
 struct Args2 : LayerArgs {   // wp: [G][NT][3][64]
-  int32_t nch, nkb_last, kbm, G;   // 128-column chunks per mode, k-blocks of the last chunk, k-blocks per mode / tile
+  int32_t nch, kbm, G;   // chunks per mode (the column cut, fused_common.h), k-blocks per mode / tile
+  uint64_t cut;   // cut_pack: kb0 | (nkb - 1) << 5, one byte per chunk
+  int32_t clamp;  // idle lanes load their chunk's last float4 (else columns 0-3)
   float bn_eps;
 #ifdef MGCN_DIAG
   unsigned long long *stamps;   // [grid][2 roles][128]: s_memtime at stage starts / ends of wave 0 (multiply) and wave 4 (gather)
@@ -195,9 +197,9 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
           for (int chunk = 0; chunk < nch; ++chunk, ++stage) {
             if (wave == 8) MGCN_STAMP(1, 2 * stage);
             unsigned char *img = lds2 + (stage & 1) * BUF;
-            const int coff_ = chunk * 128 + lig * 4;
-            const bool col_ok = coff_ < p.d;
-            const int coff = col_ok ? coff_ : 0;   // lanes past the row width repeat columns 0-3 and store zeros
+            const int col0 = 32 * cut_kb0(p.cut, chunk), ncol = cut_ncol(p.cut, chunk, p.d);
+            const bool col_ok = lig * 4 < ncol;
+            const int coff = col_ok ? col0 + lig * 4 : (p.clamp ? col0 + ncol - 4 : 0);   // lanes past the chunk repeat one of its float4 (legacy cut: columns 0-3) and store zeros
             const float *xb = p.x + coff, *relb = (RELLDS ? rel_lds : p.rel) + coff;
             const typename EeElem<EE16>::type *eeb = reinterpret_cast<const typename EeElem<EE16>::type *>(p.ee) + coff;
             int4 myrec = firstrec;
@@ -287,9 +289,9 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
           for (int chunk = 0; chunk < nch; ++chunk, ++stage) {
             if (wave == 8) MGCN_STAMP(1, 2 * stage);
             unsigned char *img = lds2 + (stage & 1) * BUF;
-            const int coff_ = chunk * 128 + lig * 4;
-            const bool col_ok = coff_ < p.d;
-            const int coff = col_ok ? coff_ : 0;
+            const int col0 = 32 * cut_kb0(p.cut, chunk), ncol = cut_ncol(p.cut, chunk, p.d);
+            const bool col_ok = lig * 4 < ncol;
+            const int coff = col_ok ? col0 + lig * 4 : (p.clamp ? col0 + ncol - 4 : 0);
             const float4 lr = *reinterpret_cast<const float4 *>(p.loop_rel + coff);
             const float4 le = *reinterpret_cast<const float4 *>(p.loop_edge + coff);
             float4 xs[RPG];
@@ -413,7 +415,7 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
     bool barrier_done = false;
     int nkb_ = 0, nchunk = 0, nmode = 0;          // the k-block after the current one: (mode, chunk, ordinal)
     auto advance_next = [&]() {
-      const int n = (nchunk == nch - 1) ? p.nkb_last : 4;
+      const int n = cut_nkb(p.cut, nchunk);
       if (++nkb_ == n) {
         nkb_ = 0;
         if (++nchunk == nch) {
@@ -424,7 +426,7 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
     };
     auto gindex = [&]() {   // (packed weights are mode-major in the order in-half, out-half, self loop; stages run loop, in, out)
       const int mode_ = nmode == 0 ? 2 : nmode - 1;
-      return mode_ * p.kbm + 4 * nchunk + rotated(nkb_, nchunk);
+      return mode_ * p.kbm + cut_kb0(p.cut, nchunk) + rotated(nkb_, nchunk);
     };
     wload(wq0, wx0, gindex());
     advance_next();
@@ -439,7 +441,7 @@ __global__ __launch_bounds__(T2, 4) void layer_fused2_kernel(Args2 p) {
     auto kblock = [&](u32x4 (&wq)[QF][3], u32x4 (&wx)[XW][3], u32x4 (&nq)[QF][3], u32x4 (&nx)[XW][3]) {
       wload(nq, nx, gindex());           // the k-block after this one (wraps into the next tile: same weights)
       advance_next();
-      const int nkb_c = (chunk == nch - 1) ? p.nkb_last : 4;
+      const int nkb_c = cut_nkb(p.cut, chunk);
       if (kb == 0) {
         if (!barrier_done) stage_barrier();   // the stage's image is complete
         barrier_done = false;
@@ -549,14 +551,15 @@ int pick2(const Args2 &p, int dim_out, int nrt, int grid, int grid5, bool rel_ld
 }
 
 struct Shape2 {
-  int nch, nkb_last, kbm, G;
+  int nch, kbm, G;
+  CutTable cut;
 };
-Shape2 shape2(int d) {
+Shape2 shape2(int d, bool legacy_cut) {
   Shape2 s;
-  s.nch = (d + 127) / 128;
-  const int wlast = d - 128 * (s.nch - 1);
-  s.nkb_last = (wlast + 31) / 32;
-  s.kbm = 4 * (s.nch - 1) + s.nkb_last;   // = ceil(d / 32), pack_modes_kbm
+  const FusedCut c = fused_cut(d, legacy_cut);   // chunks on k-block boundaries: the k-blocks of a mode are 0 .. kbm - 1 in order
+  s.nch = c.nch;
+  s.cut = c.t;
+  s.kbm = c.t.kb0[c.nch - 1] + c.t.nkb[c.nch - 1];   // = ceil(d / 32), pack_modes_kbm
   s.G = 3 * s.kbm;
   return s;
 }
@@ -597,10 +600,10 @@ int fused2_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_de
 
 int fused2_launch(const FusedLaunch &a) {
   const int32_t dim_in = a.dim_in, dim_out = a.dim_out;
-  const Shape2 s = shape2(dim_in);
+  const Shape2 s = shape2(dim_in, (a.tune & FUSED_TUNE_LEGACY_CUT) != 0);
   Args2 p = {};
   fill_layer_args(p, a);
-  p.nch = s.nch; p.nkb_last = s.nkb_last; p.kbm = s.kbm; p.G = s.G;
+  p.nch = s.nch; p.kbm = s.kbm; p.G = s.G; p.cut = cut_pack(s.cut, s.nch); p.clamp = s.cut.cidle[s.nch - 1] != 0;
   p.bn_eps = a.bn_eps;
 #ifdef MGCN_DIAG
   if (const char *ab = getenv("MGCN_FUSED_ABLATE")) p.ablate = atoi(ab);

@@ -13,7 +13,7 @@
 //   waves 0-7   MULTIPLY  v_mfma_f32_16x16x32_bf16 on the six significant products of the split operands (f32-faithful:
 //               see split3p in fused_common.h / DESIGN.md), weights pre-split and pre-packed, streamed from L2 one k-block ahead;
 //               epilogue tanh(acc * scale + shift) (model.py:103-106) on the accumulators.
-// Stage = (mode, pass of 128 * NCH columns). The gather role is the launch's critical path (its waves run ~15 cycles per
+// Stage = (mode, pass of at most 128 * NCH columns; NCH = 1: the chunks of the column cut, fused_common.h). The gather role is the launch's critical path (its waves run ~15 cycles per
 // instruction beside the MFMA waves' LDS traffic), the multiply role has slack: so the gather only STORES finished f32
 // rows into a staging buffer (one ds_write_b128 per lane and row), and the MFMA waves split each staged tile into the
 // three bf16 pieces (a branch-free pass, 2 rows per wave-instruction) before multiplying it. Buffers are exactly as
@@ -34,8 +34,10 @@ constexpr int SPIN_LIMIT = 1 << 22;   // bounded spins: a protocol error (or a w
                                       // never hangs a wave; it is REPORTED through Args3::status, the caller's status word
 
 struct Args3 : LayerArgs {   // wp: [G][NT][3][64], pack_kernel<ModeWeights>
-  int32_t npass, nkb_last, kbp, kbm, G;   // passes per mode, k-blocks of the last pass / of a full pass / per mode / per tile
-  int32_t ncc;            // 16-byte chunk columns of a stage image (8 bf16 each)
+  int32_t npass, kbm, G;   // passes per mode, k-blocks per mode / per tile
+  uint64_t cut;           // cut_pack, one byte per pass: the passes' columns and k-blocks (the column cut, fused_common.h; NCH = 2: passes of 256 columns)
+  int32_t clamp;          // idle lanes load their pass's last float4 (else columns 0-3)
+  int32_t ncc;            // 16-byte chunk columns of a stage image (8 bf16 each): the widest pass's
   int32_t rows_per_wg, nimg;
   uint32_t *status;        // optional: bit 0 is set when a bounded spin below ran out (the launch's rows are then invalid)
   const int32_t *bounds;   // [grid + 1] row offsets from node0 of the workgroups' runs (work-balanced), or null: equal runs
@@ -262,9 +264,9 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
             int coff[NCH];
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
-              const int c_ = pass * (128 * NCH) + j * 128 + lig * 4;
-              col_ok[j] = c_ < p.d;
-              coff[j] = col_ok[j] ? c_ : 0;   // lanes past the row width repeat columns 0-3 and store zeros (or nothing)
+              col_ok[j] = j * 128 + lig * 4 < cut_ncol(p.cut, pass, p.d);
+              // lanes past the pass repeat one of its float4 (legacy cut, 256-column passes: columns 0-3) and store zeros (or nothing)
+              coff[j] = col_ok[j] ? 32 * cut_kb0(p.cut, pass) + j * 128 + lig * 4 : (p.clamp ? 32 * cut_kb0(p.cut, pass) + cut_ncol(p.cut, pass, p.d) - 4 : 0);
             }
             const float *relbase = RELLDS ? rel_lds : p.rel;
             int4 myrec = firstrec;
@@ -360,9 +362,8 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
             float4 lr[NCH], le[NCH];
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
-              const int c_ = pass * (128 * NCH) + j * 128 + lig * 4;
-              col_ok[j] = c_ < p.d;
-              coff[j] = col_ok[j] ? c_ : 0;
+              col_ok[j] = j * 128 + lig * 4 < cut_ncol(p.cut, pass, p.d);
+              coff[j] = col_ok[j] ? 32 * cut_kb0(p.cut, pass) + j * 128 + lig * 4 : (p.clamp ? 32 * cut_kb0(p.cut, pass) + cut_ncol(p.cut, pass, p.d) - 4 : 0);
               lr[j] = *reinterpret_cast<const float4 *>(p.loop_rel + coff[j]);
               le[j] = *reinterpret_cast<const float4 *>(p.loop_edge + coff[j]);
             }
@@ -459,7 +460,7 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
     int kb = 0, pass = 0;
     int nkb_ = 0, npass_ = 0, nmode = 0;          // the k-block after the current one: (mode, pass, ordinal)
     auto advance_next = [&]() {
-      const int n = (npass_ == npass - 1) ? p.nkb_last : p.kbp;
+      const int n = cut_nkb(p.cut, npass_);
       if (++nkb_ == n) {
         nkb_ = 0;
         if (++npass_ == npass) {
@@ -470,7 +471,7 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
     };
     auto gindex = [&]() {   // (packed weights are mode-major in the order in-half, out-half, self loop; stages run loop, in, out)
       const int mode_ = nmode == 0 ? 2 : nmode - 1;
-      return mode_ * p.kbm + p.kbp * npass_ + nkb_;
+      return mode_ * p.kbm + cut_kb0(p.cut, npass_) + nkb_;
     };
     int gcur = gindex();
     wload(wn[0], gcur, ct_of(0));
@@ -531,7 +532,7 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
     auto kblock = [&](auto Kc) __attribute__((always_inline)) {
       constexpr int K = decltype(Kc)::value;   // position of the k-block in the loop body (names of its entries: (K E + e) % 3)
       wload(wn[(K * E + 1) % 3], gcur, ct_of(1));   // this k-block's second entry
-      const int nkb_c = (pass == npass - 1) ? p.nkb_last : p.kbp;
+      const int nkb_c = cut_nkb(p.cut, pass);
       if (kb == 0) {
         // the stage's tile: staged f32 rows -> the bf16 image. Wave w converts rows 8 i + w (NCH = 2) or 16 i + 2 w + (lane >> 5)
         // (NCH = 1: two rows per wave-instruction); a lane splits one float4 exactly into three bf16 pieces.
@@ -625,23 +626,28 @@ __global__ __launch_bounds__(T3, 4) void layer_fused3_kernel(Args3 p) {
 int pick_nt3(int o) { return o <= 208 ? 13 : 32; }   // column tiles of the multiply role (narrower outputs ride along zero-padded)
 
 struct Shape3 {
-  int nch, npass, nkb_last, kbp, kbm, G, ncc;
+  int nch, npass, kbm, G, ncc;
+  CutTable cut;
 };
-Shape3 shape3(int d, int nch = 0) {   // nch: float4 per lane and slot walk (0 = by width)
-  Shape3 s;
+Shape3 shape3(int d, int nch, bool legacy_cut) {   // nch: float4 per lane and slot walk (0 = by width)
+  Shape3 s = {};
   // 128-column passes by default (one float4 per lane, four slots per batch): round 4's A/B on the product build has the 200-wide
   // layer at 96 / 107 us (warm / cold) against 108 / 118 with one 256-column walk (two float4, two slots per batch) on the WN18RR
   // shape and 187 against 193 on FB15k-237; the 256-column walk stays reachable through `tune` bits 12-13 = 2
   s.nch = nch ? nch : 1;
-  const int wpass = 128 * s.nch;
-  s.npass = (d + wpass - 1) / wpass;
-  const int wlast = d - wpass * (s.npass - 1);
-  s.nkb_last = (wlast + 31) / 32;
-  s.kbp = 4 * s.nch;
-  s.kbm = s.kbp * (s.npass - 1) + s.nkb_last;   // = ceil(d / 32) whatever nch, pack_modes_kbm
+  if (s.nch == 1) {   // the 128-column walk takes the column cut of generation 2 (fused_common.h): a rank's range fetches like the whole graph's launch
+    const FusedCut c = fused_cut(d, legacy_cut);
+    s.npass = c.nch;
+    s.cut = c.t;
+  } else {            // 256-column passes, the last one short; idle lanes on column 0
+    for (int col = 0; col < d; col += 256, ++s.npass) {
+      const int n = d - col < 256 ? d - col : 256;
+      s.cut.col0[s.npass] = col; s.cut.ncol[s.npass] = n; s.cut.kb0[s.npass] = col / 32; s.cut.nkb[s.npass] = (n + 31) / 32;
+    }
+  }
+  s.kbm = s.cut.kb0[s.npass - 1] + s.cut.nkb[s.npass - 1];   // = ceil(d / 32) whatever the passes, pack_modes_kbm
   s.G = 3 * s.kbm;
-  const int w0 = d < wpass ? d : wpass;
-  s.ncc = (w0 + 7) / 8;
+  for (int i = 0; i < s.npass; ++i) s.ncc = s.ncc > (s.cut.ncol[i] + 7) / 8 ? s.ncc : (s.cut.ncol[i] + 7) / 8;
   return s;
 }
 
@@ -720,16 +726,16 @@ int fused3_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_de
 }
 
 // tune: 0 = automatic; bits 0-3 row tiles per tile (3 / 4 / 5), bits 4-7 staging buffers (1..4), bits 8-9 relation table in LDS
-// (1 = never, 2 = whenever it fits), bits 12-13 columns per slot walk (1 = 128, 2 = 256): for A/B runs (tools/), never
-// needed for correctness (the packed weights do not depend on it).
+// (1 = never, 2 = whenever it fits), bits 12-13 columns per slot walk (1 = 128, 2 = 256), bit 14 the legacy column cut of the
+// 128-column walk: for A/B runs (tools/), never needed for correctness (the packed weights do not depend on it).
 int fused3_launch(const FusedLaunch &a) {
   const int32_t dim_in = a.dim_in, dim_out = a.dim_out, tune = a.tune;
   const int t_nch = (tune >> 12) & 3;
   if (t_nch > 2) return mgcn::fail(MGCN_EINVAL, "layer_fwd_fused: bad tune %d", tune);
-  const Shape3 s = shape3(dim_in, t_nch);
+  const Shape3 s = shape3(dim_in, t_nch, (tune & FUSED_TUNE_LEGACY_CUT) != 0);
   Args3 p = {};
   fill_layer_args(p, a);
-  p.npass = s.npass; p.nkb_last = s.nkb_last; p.kbp = s.kbp; p.kbm = s.kbm; p.G = s.G; p.ncc = s.ncc;
+  p.npass = s.npass; p.kbm = s.kbm; p.G = s.G; p.ncc = s.ncc; p.cut = cut_pack(s.cut, s.npass); p.clamp = s.cut.cidle[s.npass - 1] != 0;
   p.bn_eps = a.bn_eps;
   p.status = a.status;
   const int cus = cu_count();
