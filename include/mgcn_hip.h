@@ -1084,6 +1084,47 @@ int mgcn_cand_draw_alias_host(int64_t batch, int64_t n_cand, int64_t num_entitie
                               const int64_t *table_host, uint64_t key, uint64_t row0, int64_t *cand_host, int64_t ldc,
                               uint8_t *label_host, int64_t ldl);
 
+/* ---------------------------------------------------------------------------------------------
+ * (18) The list backward with long runs split across waves, in a fixed order (csrc/query_train.hip) — additive,
+ * MGCN_ABI_VERSION stays 4. mgcn_cand_bce_bwd_ent of (14) walks a run of plan entries that name one entity with one wave however
+ * long it is; on weighted lists a hub entity is named thousands of times. mgcn_cand_bce_bwd_ent_split takes that call's
+ * arguments, with the same meaning, checks and optionality (d_ent_dev NULL: bias only), plus
+ *   keys_dev [batch * n_cand] int64: the ascending sort keys row * (batch * n_cand) + position the plan perm was sorted by (dead
+ *     entries: row = n_local), i.e. keys_dev[i] is the key of perm_dev[i]; run_split = S in [16, 65536]; a workspace of at least
+ *     mgcn_cand_bwd_ent_split_workspace bytes, 16-byte aligned, which the call may overwrite completely and reads nothing from
+ *     that it has not written itself.
+ * THE ORDER (the contract). A run is a maximal stretch of plan entries e_0 .. e_{L-1} with one live row o, as in (14). Piece p
+ * holds e_{pS} .. e_{min((p+1)S, L)-1}: the cuts are counted from the run's OWN first entry, not from the plan's. A piece's
+ * partial is (14)'s loop over its entries: the sequential f32 sum from +0 of the rounded products g[pos] * x[b(pos), c] (for
+ * d_bias: of g[pos]) in plan order. d_ent[o, c] and d_bias[o] are the sequential f32 sum from +0 of the pieces' partials in piece
+ * order. Hence a run with L <= S has the bits mgcn_cand_bce_bwd_ent gives it (0 + a = a, and a sum from +0 is never -0), and a
+ * row's result depends only on the positions that name it and on S: not on the other ids of the list, on ent_row0 / n_local,
+ * on the grid or on scheduling, so a shard's rows equal the same rows of the one-rank call bit for bit. Rows that no live position
+ * names are LEFT AS THEY ARE. The dependent chain of a row is S + ceil(L / S) additions instead of L.
+ * THE LAUNCHES, all enqueued by the one call (no host read, no allocation, no atomics of any kind, plain vector stores; it may
+ * be captured): (a) one thread per plan entry i finds its run's first entry s, the lowest index with keys_dev[s] >=
+ * row_i * (batch * n_cand), by galloping backwards from i and bisecting inside [0, i], and marks i as a piece head iff
+ * (i - s) % S == 0; (b) one wave per plan entry, a head walks its at most S entries and writes either the row (the run's only
+ * piece) or a workspace slot of dim + 1 floats; (c) one wave per window of S plan entries adds the slots of the run of several
+ * pieces that begins in that window, if there is one (two cannot: they would be more than S entries apart).
+ * SLOTS: head i of a run of several pieces writes slot 2 * (i / S) + (1 if it is the run's first head else 0). Two heads of one
+ * run are S apart, so they lie in different windows i / S; two runs with a head in one window are adjacent in the plan, the
+ * earlier one's head there is not its first and the later one's is. So no two heads share a slot and 2 * ceil(batch * n_cand / S)
+ * slots suffice: the workspace is these slots, one int64 per window (written by one thread each) and one byte per plan entry.
+ * keys_dev is only ever COMPARED: the row, the query and every address of g / x / d_ent / d_bias come from cand through the
+ * liveness test as in (14), a slot index from the entry's own index i < n_live. Keys that are not the plan's can give wrong sums
+ * in the rows the lists name and nothing else.
+ * MGCN_EINVAL on top of (14)'s cases, nothing launched and nothing written: a null keys_dev, run_split outside [16, 65536], a
+ * null or misaligned workspace or one smaller than mgcn_cand_bwd_ent_split_workspace says, (n_local + 1) * batch * n_cand
+ * not below 2^63. mgcn_cand_bwd_ent_split_workspace returns 0 for sizes or a run_split the call refuses.
+ * NOT MEASURED: the three kernels' own times (DESIGN §4.16 times the stage).
+ */
+size_t mgcn_cand_bwd_ent_split_workspace(int32_t batch, int64_t n_cand, int32_t dim, int32_t run_split);
+int mgcn_cand_bce_bwd_ent_split(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim, const float *g_dev,
+                                int64_t ldg, const int64_t *cand_dev, int64_t ldc, const int64_t *perm_dev, int64_t n_live,
+                                const float *x_dev, int64_t ldx, float *d_ent_dev, int64_t lde, float *d_bias_dev,
+                                const int64_t *keys_dev, int32_t run_split, void *ws_dev, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

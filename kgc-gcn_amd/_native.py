@@ -93,6 +93,9 @@ _SIGNATURES = {
     'mgcn_cand_bce_bwd_x': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr]),
     'mgcn_cand_bce_bwd_ent': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64,
                                              _ptr, _ptr]),
+    'mgcn_cand_bwd_ent_split_workspace': (ctypes.c_size_t, [_i32, _i64, _i32, _i32]),
+    'mgcn_cand_bce_bwd_ent_split': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64,
+                                                   _ptr, _ptr, _i32, _ptr, ctypes.c_size_t, _ptr]),
     'mgcn_cand_ce_partials': (_i64, [_i32, _i64]),
     'mgcn_cand_ce_logits': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64,
                                            _ptr, _ptr]),
@@ -1154,13 +1157,15 @@ def cand_bce_bwd_x(g, cand, ent, ent_row0=0):
     return dx
 
 
-def cand_plan(cand, n_local, ent_row0=0, count=True):
+def cand_plan(cand, n_local, ent_row0=0, count=True, keys=False):
     """(perm [B K] int64, n_live): the flat positions b K + j of the live entries of cand [B, K] (ids in
     [ent_row0, ent_row0 + n_local)) ordered by (shard row, flat position), then the dead ones by flat position: the plan
     mgcn_cand_bce_bwd_ent takes. One torch.sort of the UNIQUE keys row * (B K) + pos (dead entries: row = n_local), so the plan is a
     function of cand alone whatever the sort does with ties. Integer work in torch, on any device. Counting the live entries
     reads one integer back from the device; count=False skips that and returns n_live = B K, which mgcn_cand_bce_bwd_ent takes
-    as well: the dead entries sort last, and the kernel re-checks every entry and skips a dead one."""
+    as well: the dead entries sort last, and the kernel re-checks every entry and skips a dead one.
+    keys=True: (perm, n_live, keys) with the sorted keys themselves, keys[i] the key of perm[i]: what
+    cand_bce_bwd_ent(run_split=...) finds a run's first entry by. The plan is the same either way."""
     if cand.dim() != 2 or cand.dtype != torch.int64:
         raise NativeError('cand_plan: cand must be int64 [B, K], got %s %s' % (cand.dtype, tuple(cand.shape)))
     n_local, row0, total = int(n_local), int(ent_row0), cand.numel()
@@ -1174,19 +1179,41 @@ def cand_plan(cand, n_local, ent_row0=0, count=True):
         live = live & (flat < row0 + n_local)
     row = torch.where(live, flat - row0, torch.full_like(flat, n_local))     # (a wrapped difference of a dead id is never used)
     key = row * total + torch.arange(total, dtype=torch.int64, device=cand.device)
-    perm = torch.sort(key).indices
-    return perm, int(live.sum()) if count else total
+    sorted_keys, perm = torch.sort(key)
+    n_live = int(live.sum()) if count else total
+    return (perm, n_live, sorted_keys) if keys else (perm, n_live)
 
 
-def cand_bce_bwd_ent(g, cand, x, perm, n_live, n_local, ent_row0=0, d_ent=None, d_bias=None, want=('ent', 'bias')):
+RUN_SPLIT_MIN, RUN_SPLIT_MAX = 16, 65536
+
+
+def check_run_split(what, run_split):
+    """run_split is None (the one-wave-per-run backward) or an int in [16, 65536]; anything else is refused."""
+    if run_split is None:
+        return None
+    if isinstance(run_split, bool) or not isinstance(run_split, int) or not RUN_SPLIT_MIN <= run_split <= RUN_SPLIT_MAX:
+        raise NativeError('%s: run_split must be None or an int in [%d, %d], got %r' % (what, RUN_SPLIT_MIN, RUN_SPLIT_MAX, run_split))
+    return run_split       # (16.0 and True are refused like 15: the value is a count that also keys a captured graph)
+
+
+def cand_bce_bwd_ent(g, cand, x, perm, n_live, n_local, ent_row0=0, d_ent=None, d_bias=None, want=('ent', 'bias'), run_split=None,
+                     keys=None):
     """(14) (d_ent [n_local, dim], d_bias [n_local]): the rows that live list positions name receive their fixed-order sums of
     g[pos] x[b(pos)] and of g[pos] (plan order, see mgcn_cand_bce_bwd_ent); every other row is LEFT AS IT IS. d_ent / d_bias:
-    blocks to write into (d_ent may be a column window); None allocates zeros for what `want` names."""
+    blocks to write into (d_ent may be a column window); None allocates zeros for what `want` names.
+    run_split = S (None: the above, unchanged), an int in [16, 65536], with keys = the sorted keys of cand_plan(keys=True): (18),
+    a run of more than S plan entries is cut into pieces of S counted from its own first entry, the pieces are summed by
+    different waves and folded in piece order (mgcn_cand_bce_bwd_ent_split). A run of at most S entries keeps its bits; a longer
+    one has another, equally fixed, summation order. The workspace (about 2 B K / S rows of dim + 1 floats, plus a byte per list
+    position) is allocated here per call."""
+    check_run_split('cand_bce_bwd_ent', run_split)
     B = g.size(0)
     K = _cand_block(cand, B, 'cand_bce_bwd_ent')
-    _same_device(g, cand, x, perm, d_ent, d_bias)
+    _same_device(g, cand, x, perm, d_ent, d_bias, keys)
     if x.dim() != 2 or x.size(0) != B or perm.dim() != 1 or perm.numel() != B * K or not 0 <= int(n_live) <= B * K:
         raise NativeError('cand_bce_bwd_ent: x must be (%d, dim), perm [%d] and 0 <= n_live <= %d' % (B, B * K, B * K))
+    if run_split is not None and (keys is None or keys.dim() != 1 or keys.numel() != B * K):
+        raise NativeError('cand_bce_bwd_ent: run_split needs keys [%d], the sorted keys of cand_plan(keys=True)' % (B * K))
     gp, ldg = _cand_rows(g, B, K, torch.float32, 'cand_bce_bwd_ent', 'g')
     n, O = int(n_local), x.size(1)
     if d_ent is None and 'ent' in want:
@@ -1197,6 +1224,20 @@ def cand_bce_bwd_ent(g, cand, x, perm, n_live, n_local, ent_row0=0, d_ent=None, 
         raise NativeError('cand_bce_bwd_ent: d_ent must be (%d, %d)' % (n, O))
     if d_bias is not None and (d_bias.numel() != n or not d_bias.is_contiguous()):
         raise NativeError('cand_bce_bwd_ent: d_bias must be contiguous [%d]' % n)
+    if run_split is not None:
+        if B and K and n and int(n_live):
+            need = int(lib().mgcn_cand_bwd_ent_split_workspace(B, K, O, run_split))
+            if need == 0:
+                raise NativeError('cand_bce_bwd_ent: no workspace for batch = %d, n_cand = %d, dim = %d, run_split = %d'
+                                  % (B, K, O, run_split))
+            ws = torch.empty(need, dtype=torch.uint8, device=g.device)
+            _check(lib().mgcn_cand_bce_bwd_ent_split(B, K, n, int(ent_row0), O, gp, ldg, _dev(cand, torch.int64, 'cand'), _ld(cand),
+                                                     _dev(perm, torch.int64, 'perm'), int(n_live), _dev(x, torch.float32, 'x'), _ld(x),
+                                                     _dev(d_ent, torch.float32, 'd_ent', True), _ld(d_ent) if d_ent is not None else 0,
+                                                     _dev(d_bias, torch.float32, 'd_bias', True), _dev(keys, torch.int64, 'keys'),
+                                                     run_split, _dev(ws, torch.uint8, 'workspace'), need, _stream(g)),
+                   'mgcn_cand_bce_bwd_ent_split')
+        return d_ent, d_bias
     if B and K and n and int(n_live):
         _check(lib().mgcn_cand_bce_bwd_ent(B, K, n, int(ent_row0), O, gp, ldg, _dev(cand, torch.int64, 'cand'), _ld(cand),
                                            _dev(perm, torch.int64, 'perm'), int(n_live), _dev(x, torch.float32, 'x'), _ld(x),

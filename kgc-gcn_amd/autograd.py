@@ -275,6 +275,15 @@ class _ScoreBCEFn(torch.autograd.Function):
                 g.sum(1) * gl if ctx.needs_input_grad[2] else None, None, None, None, None)
 
 
+def _save_plan(ctx, x, ent, cand, g, row0, run_split):
+    """What the list backward of _CandBCEFn / _CandCEFn needs, saved on ctx: the plan of the rank's rows, and with a run_split
+    its sorted keys too. No host read of the live count: the whole plan is handed over, its dead tail is skipped entry by entry."""
+    ctx.row0, ctx.run_split = int(row0), run_split
+    plan = _native.cand_plan(cand, ent.size(0), ent_row0=row0, count=False, keys=run_split is not None)
+    ctx.n_live = plan[1]
+    ctx.save_for_backward(x, ent, cand, g, plan[0], *plan[2:])
+
+
 class _CandBCEFn(torch.autograd.Function):
     """mean BCE over per-query candidate lists (include/mgcn_hip.h (14)): one launch leaves the loss partials and d loss / d logit
     [B, K]; the backward is two fixed-order sums on the kernels of csrc/query_train.hip, d x over the gathered entity rows and
@@ -283,20 +292,21 @@ class _CandBCEFn(torch.autograd.Function):
     another rank owns are dead here, they write g = 0, add no loss term and still count in the divisor B K, so the ranks' losses
     and d x add up to the one-rank step's; d ent and d bias are the rank's rows, complete.
     The incoming gradient is a scalar in any 0-dim view: it is folded into g [B, K] by broadcasting (g * gl, a fresh contiguous
-    tensor) and reaches no kernel itself."""
+    tensor) and reaches no kernel itself.
+    `run_split` (None: the above, unchanged): d ent / d bias cut runs longer than it into pieces summed by different waves
+    (include/mgcn_hip.h (18)); the forward then keeps the plan's sorted keys as well. Loss, g and d x do not see it."""
 
     @staticmethod
-    def forward(ctx, x, ent, bias, cand, label, hot, cold, row0=0):
+    def forward(ctx, x, ent, bias, cand, label, hot, cold, row0=0, run_split=None):
+        _native.check_run_split('_CandBCEFn', run_split)      # (before the first launch)
         loss, g = _native.cand_bce_fwd(x, ent, bias, cand, label, hot, cold, ent_row0=row0)
-        # (no host read of the live count: the whole plan is handed over, its dead tail is skipped entry by entry)
-        perm, ctx.n_live = _native.cand_plan(cand, ent.size(0), ent_row0=row0, count=False)
-        ctx.row0 = int(row0)
-        ctx.save_for_backward(x, ent, cand, g, perm)
+        _save_plan(ctx, x, ent, cand, g, row0, run_split)
         return loss
 
     @staticmethod
     def backward(ctx, gl):
-        x, ent, cand, g, perm = ctx.saved_tensors
+        x, ent, cand, g, perm = ctx.saved_tensors[:5]
+        keys = ctx.saved_tensors[5] if ctx.run_split is not None else None
         # d x gl, d ent gl, d bias gl with gl folded into g [B, K] first: the sums are linear in g, and the [N, dim] block is
         # written once instead of being scaled in a second pass (gl = 1, the usual case, changes no bit of g)
         g = g * gl
@@ -304,8 +314,9 @@ class _CandBCEFn(torch.autograd.Function):
         want = tuple(n for i, n in ((1, 'ent'), (2, 'bias')) if ctx.needs_input_grad[i])
         d_ent, d_bias = (None, None)
         if want:
-            d_ent, d_bias = _native.cand_bce_bwd_ent(g, cand, x, perm, ctx.n_live, ent.size(0), ent_row0=ctx.row0, want=want)
-        return (gx, d_ent, d_bias) + (None,) * 5
+            d_ent, d_bias = _native.cand_bce_bwd_ent(g, cand, x, perm, ctx.n_live, ent.size(0), ent_row0=ctx.row0, want=want,
+                                                     run_split=ctx.run_split, keys=keys)
+        return (gx, d_ent, d_bias) + (None,) * 6
 
 
 class _CandCEFn(torch.autograd.Function):
@@ -317,10 +328,11 @@ class _CandCEFn(torch.autograd.Function):
     the chunks; the finish then takes the global statistics. The rank's loss is the sum of its own positions' terms, so the
     ranks' losses and d x add up to the one-rank step's; d ent and d bias are the rank's rows, complete. A rank without rows
     contributes the empty statistic and joins the all-gather. Without an exchange, or with one of a single rank, there is no
-    collective and no second merge. The incoming scalar gradient is handled as in _CandBCEFn."""
+    collective and no second merge. The incoming scalar gradient and `run_split` are handled as in _CandBCEFn."""
 
     @staticmethod
-    def forward(ctx, x, ent, bias, cand, label, eps, row0=0, ex=None):
+    def forward(ctx, x, ent, bias, cand, label, eps, row0=0, ex=None, run_split=None):
+        _native.check_run_split('_CandCEFn', run_split)       # (before the first launch and the collective)
         B, n = x.size(0), ent.size(0)
         if n:
             z, stat = _native.cand_ce_logits(x, ent, bias, cand, label, ent_row0=row0)
@@ -331,9 +343,7 @@ class _CandCEFn(torch.autograd.Function):
         if ex is not None and ex.world > 1:
             stat = _native.cand_ce_merge(ex.gather_stats(stat), part_dim=0)
         loss, g, _ = _native.cand_ce_finish(z, cand, label, stat, eps, n, ent_row0=row0)
-        perm, ctx.n_live = _native.cand_plan(cand, n, ent_row0=row0, count=False)
-        ctx.row0 = int(row0)
-        ctx.save_for_backward(x, ent, cand, g, perm)
+        _save_plan(ctx, x, ent, cand, g, row0, run_split)
         return loss
 
     @staticmethod

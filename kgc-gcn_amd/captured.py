@@ -303,7 +303,7 @@ class CapturedTrainStep(object):
 
 class CapturedCandidateStep(CapturedTrainStep):
     """step = CapturedCandidateStep(model, graph, index, optimizer, num_neg, draw_seed, draw_step=0, loss='bce', lbl_smooth=0.0,
-    clip=None, warmup=2); loss = step(src, rel).
+    clip=None, warmup=2, sampler=None, run_split=None); loss = step(src, rel).
 
     CapturedTrainStep for the sampled-negative step: one step of harness.train_sampled_negatives(draw_seed=...) --
     zero_grad, harness.draw_candidates(..., labels=True), MGCN.forward_loss_candidates(labels=..., loss=...), backward,
@@ -313,19 +313,21 @@ class CapturedCandidateStep(CapturedTrainStep):
     draw_seed and step count) and act on the next call without a new capture. Eager calls pass the list key by value. The
     captured draw (mgcn_cand_draw_dev) reads a second device word, dropout_step_key(draw_seed, draw_step), which the wrapper
     writes next to the dropout step word and the Adam pairs in the same pinned image: a replay still costs ONE host-to-device copy
-    of scalars. `num_neg` and `loss` are plain attributes held by value in the graph: changing one re-captures. `cand` is the
+    of scalars. `num_neg`, `loss` and `run_split` (forward_loss_candidates', None or an int in [16, 65536]) are plain attributes
+    held by value in the graph: changing one re-captures. `cand` is the
     [B, 1 + num_neg] block of the last call (after a replay: the graph's static tensor, overwritten by the next replay).
 
     Raises NativeError, before anything is captured, for what the parent refuses (but the scoring stage takes any batch >= 1),
-    for num_neg < 0, a loss other than 'bce' / 'softmax' and an index that is not on the model's device."""
+    for num_neg < 0, a loss other than 'bce' / 'softmax', a run_split that forward_loss_candidates refuses and an index that is not
+    on the model's device."""
 
     _WORDS = 2     # the dropout step word, then the draw word
 
     def __init__(self, model, graph, index, optimizer, num_neg, draw_seed, draw_step=0, loss='bce', lbl_smooth=0.0, clip=None, warmup=2,
-                 sampler=None):
+                 sampler=None, run_split=None):
         super().__init__(model, graph, index, optimizer, lbl_smooth=lbl_smooth, clip=clip, warmup=warmup)
         self.num_neg, self.draw_seed, self.draw_step, self.loss = num_neg, int(draw_seed), int(draw_step), loss
-        self.sampler = sampler
+        self.sampler, self.run_split = sampler, run_split
         self.cand = None
 
     def _body(self, src, rel):
@@ -338,7 +340,8 @@ class CapturedCandidateStep(CapturedTrainStep):
                                        self.draw_seed, self.draw_step, labels=True, step_key_dev=word, sampler=self.sampler)
         self.draw_step += 1
         logq = self.sampler.logq if self.sampler is not None and self.loss == 'softmax' else None
-        loss = m.forward_loss_candidates(src, rel, cand, self.graph, labels=labels, lbl_smooth=self.lbl_smooth, loss=self.loss, logq=logq)
+        loss = m.forward_loss_candidates(src, rel, cand, self.graph, labels=labels, lbl_smooth=self.lbl_smooth, loss=self.loss, logq=logq,
+                                         run_split=self.run_split)
         loss.backward()
         opt.clip_and_step(self.clip)
         self.cand = cand
@@ -354,6 +357,7 @@ class CapturedCandidateStep(CapturedTrainStep):
             raise _native.NativeError('CapturedCandidateStep: num_neg must be an int >= 0, got %r' % (self.num_neg,))
         if self.loss not in ('bce', 'softmax'):
             raise _native.NativeError("CapturedCandidateStep: loss must be 'bce' or 'softmax', got %r" % (self.loss,))
+        _native.check_run_split('CapturedCandidateStep', self.run_split)
         dev = self.model.entity_embedding.device
         if any(t.device != dev for t in (self.index.keys, self.index.ptr, self.index.tails)):
             raise _native.NativeError('CapturedCandidateStep: the index is not on the model\'s device (%s)' % (dev,))
@@ -369,7 +373,7 @@ class CapturedCandidateStep(CapturedTrainStep):
     def _key(self):
         ix = self.index       # (the parent's key holds the index tensors' addresses too: here the draw reads them as well)
         sm = self.sampler     # (its tensors are persistent: their addresses are what the graph holds)
-        return super()._key() + (self.num_neg, self.loss, ix.keys.data_ptr(), ix.ptr.data_ptr(), ix.tails.data_ptr()) + \
+        return super()._key() + (self.num_neg, self.loss, self.run_split, ix.keys.data_ptr(), ix.ptr.data_ptr(), ix.tails.data_ptr()) + \
             (() if sm is None else (sm.table.data_ptr(), sm.logq.data_ptr()))
 
     def _stage_words(self, slot):

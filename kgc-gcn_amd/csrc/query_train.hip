@@ -222,8 +222,241 @@ __global__ __launch_bounds__(TPB) void cand_bwd_ent_kernel(int64_t total, int64_
   }
 }
 
+// ------------------------------------------------------------------------------------------------ (d) split runs
+// cand_bwd_ent_kernel's sums with a long run cut into pieces of S plan entries counted from the run's OWN first entry, paragraph
+// (18) of include/mgcn_hip.h: a piece's partial is that kernel's loop over its entries, a row is the sequential fold from +0 of
+// its pieces' partials in piece order. Three launches: heads (which entries begin a piece), pieces (one wave per head; a run
+// of one piece is written straight to its row, with the bits of cand_bwd_ent_kernel), fold (one wave per run of several pieces).
+// The sorted keys are only ever COMPARED, to find a run's first entry without a scan; every address is formed from cand through
+// plan_row, so keys that do not belong to the plan can give wrong sums and nothing else.
+constexpr int SPLIT_MIN = 16, SPLIT_MAX = 65536;
+constexpr uint8_t HEAD_NONE = 0, HEAD_FIRST = 1, HEAD_NEXT = 2;
+constexpr int SPLIT_UNR = 8;                          // entries whose x rows are in flight per lane (four columns each)
+constexpr int FOLD_UNR = 4;                           // pieces whose slot loads are in flight per lane
+
+// the workspace: piece slots of dim + 1 floats (the row's columns, then the bias term), two per window of S plan entries; per
+// window the first entry of the run of several pieces that begins in it, or -1; per plan entry its head mark
+struct SplitWs {
+  float *slot;
+  int64_t *first;
+  uint8_t *mark;
+};
+
+inline size_t up16(size_t n) { return (n + 15u) & ~size_t(15); }
+inline int64_t split_windows(int64_t total, int64_t S) { return (total + S - 1) / S; }
+inline size_t split_workspace(int64_t total, int dim, int64_t S) {
+  const size_t w = size_t(split_windows(total, S));
+  return up16(2 * w * (size_t(dim) + 1) * sizeof(float)) + up16(w * sizeof(int64_t)) + up16(size_t(total));
+}
+inline SplitWs split_carve(void *ws, int64_t total, int dim, int64_t S) {
+  const size_t w = size_t(split_windows(total, S));
+  char *p = static_cast<char *>(ws);
+  SplitWs out;
+  out.slot = reinterpret_cast<float *>(p);
+  p += up16(2 * w * (size_t(dim) + 1) * sizeof(float));
+  out.first = reinterpret_cast<int64_t *>(p);
+  p += up16(w * sizeof(int64_t));
+  out.mark = reinterpret_cast<uint8_t *>(p);
+  return out;
+}
+
+// (a) heads: one THREAD per plan entry i. The run of i's row begins at the lowest s in [0, i] with keys[s] >= row * total (the
+// keys are row * total + position, ascending): galloped backwards from i, then bisected; every index read lies in [0, i]. Entry
+// i begins a piece iff (i - s) % S == 0. The thread of a window's first entry i = (w + 1) S also writes first[w], the one
+// store to it: a run of more than S entries that begins in window w holds entry (w + 1) S, so that thread sees it or there is
+// none (two such runs cannot begin within S entries of each other).
+__global__ __launch_bounds__(TPB) void cand_split_heads_kernel(int64_t total, int64_t n_cand, int64_t n_local, int64_t row0, int S,
+                                                               const int64_t *__restrict__ cand, int64_t ldc,
+                                                               const int64_t *__restrict__ perm, const int64_t *__restrict__ keys,
+                                                               int64_t n_live, uint8_t *__restrict__ mark,
+                                                               int64_t *__restrict__ first) {
+  for (int64_t i = int64_t(blockIdx.x) * TPB + threadIdx.x; i < n_live; i += int64_t(gridDim.x) * TPB) {
+    int64_t b = 0, j = 0;
+    const int64_t row = plan_row(perm, i, total, n_cand, cand, ldc, row0, n_local, b, j);
+    const bool window = i > 0 && i % S == 0;
+    uint8_t m = HEAD_NONE;
+    int64_t begins = -1;
+    if (row >= 0) {
+      const int64_t target = row * total;             // (fits: the entry point checks (n_local + 1) total)
+      int64_t hi = i, lo = -1;
+      for (int64_t step = 1;; step <<= 1) {
+        const int64_t p = hi - step;
+        if (p < 0) break;
+        if (keys[p] < target) {
+          lo = p;
+          break;
+        }
+        hi = p;
+      }
+      while (hi - lo > 1) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < target)
+          lo = mid;
+        else
+          hi = mid;
+      }
+      const int64_t d = i - hi;
+      if (d % S == 0) m = d == 0 ? HEAD_FIRST : HEAD_NEXT;
+      if (window && d > 0 && d <= S && hi + S < n_live &&
+          plan_row(perm, hi + S, total, n_cand, cand, ldc, row0, n_local, b, j) == row)
+        begins = hi;
+    }
+    mark[i] = m;
+    if (window) first[i / S - 1] = begins;
+  }
+}
+
+// (b) pieces: one WAVE per plan entry, a head walks at most S entries of its run, every other wave exits. The walk takes 64
+// entries at a time, a lane looking up one entry's (row, query, g); the entries up to the first one of another row are then
+// added in plan order, lanes over columns, four column slabs per walk as in cand_bwd_ent_kernel. A first head whose run ends
+// within its piece writes the row; any other head writes slot 2 (i / S) + (first head ? 1 : 0).
+__global__ __launch_bounds__(TPB) void cand_split_piece_kernel(int64_t total, int64_t n_cand, int64_t n_local, int64_t row0, int dim,
+                                                               int S, const float *__restrict__ g, int64_t ldg,
+                                                               const int64_t *__restrict__ cand, int64_t ldc,
+                                                               const int64_t *__restrict__ perm, int64_t n_live,
+                                                               const float *__restrict__ x, int64_t ldx,
+                                                               const uint8_t *__restrict__ mark, float *__restrict__ slot,
+                                                               float *__restrict__ d_ent, int64_t lde, float *__restrict__ d_bias) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t i = int64_t(blockIdx.x) * (TPB / 64) + wave; i < n_live; i += int64_t(gridDim.x) * (TPB / 64)) {
+    const uint8_t m = mark[i];
+    if (m == HEAD_NONE) continue;                     // wave-uniform
+    int64_t b = 0, j = 0;
+    const int64_t row = plan_row(perm, i, total, n_cand, cand, ldc, row0, n_local, b, j);
+    if (row < 0) continue;
+    const int64_t lim = i + S < n_live ? i + S : n_live;
+    const int slabs = d_ent ? (dim + 255) / 256 : 1;
+    for (int sl = 0; sl < slabs; ++sl) {
+      const int c0 = sl * 256 + lane;
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, sb = 0.f;
+      int64_t walked = 0;
+      for (int64_t k0 = i; k0 < lim; k0 += 64) {
+        const int64_t k = k0 + lane;
+        int64_t kb = 0, kj = 0;
+        bool mine = false;
+        if (k < lim) mine = plan_row(perm, k, total, n_cand, cand, ldc, row0, n_local, kb, kj) == row;
+        const float g_l = mine ? g[kb * ldg + kj] : 0.f;
+        const int b_l = int(kb);                      // (batch < 2^31)
+        const unsigned long long others = ~__ballot(mine);
+        const int n = others ? __builtin_ctzll(others) : 64;
+        for (int q0 = 0; q0 < n; q0 += SPLIT_UNR) {
+          float gv[SPLIT_UNR], x0[SPLIT_UNR], x1[SPLIT_UNR], x2[SPLIT_UNR], x3[SPLIT_UNR];
+#pragma unroll
+          for (int u = 0; u < SPLIT_UNR; ++u) {
+            const int q = (q0 + u) & 63;
+            gv[u] = __shfl(g_l, q);
+            const float *xr = x + int64_t(__shfl(b_l, q)) * ldx;
+            const bool on = d_ent && q0 + u < n;      // (an entry past n is another run's or none: its query is not looked at)
+            x0[u] = on && c0 < dim ? xr[c0] : 0.f;
+            x1[u] = on && c0 + 64 < dim ? xr[c0 + 64] : 0.f;
+            x2[u] = on && c0 + 128 < dim ? xr[c0 + 128] : 0.f;
+            x3[u] = on && c0 + 192 < dim ? xr[c0 + 192] : 0.f;
+          }
+#pragma unroll
+          for (int u = 0; u < SPLIT_UNR; ++u)
+            if (q0 + u < n) {
+              if (d_ent) {
+                a0 = __fadd_rn(a0, __fmul_rn(gv[u], x0[u]));
+                a1 = __fadd_rn(a1, __fmul_rn(gv[u], x1[u]));
+                a2 = __fadd_rn(a2, __fmul_rn(gv[u], x2[u]));
+                a3 = __fadd_rn(a3, __fmul_rn(gv[u], x3[u]));
+              }
+              sb = __fadd_rn(sb, gv[u]);
+            }
+        }
+        walked += n;
+        if (n < 64) break;
+      }
+      const bool more = walked == S && i + S < n_live && plan_row(perm, i + S, total, n_cand, cand, ldc, row0, n_local, b, j) == row;
+      if (m == HEAD_FIRST && !more) {                 // the whole run: cand_bwd_ent_kernel's stores
+        if (d_ent) {
+          float *dr = d_ent + row * lde;
+          if (c0 < dim) dr[c0] = a0;
+          if (c0 + 64 < dim) dr[c0 + 64] = a1;
+          if (c0 + 128 < dim) dr[c0 + 128] = a2;
+          if (c0 + 192 < dim) dr[c0 + 192] = a3;
+        }
+        if (sl == 0 && d_bias && lane == 0) d_bias[row] = sb;
+      } else {
+        float *sr = slot + (2 * (i / S) + (m == HEAD_FIRST ? 1 : 0)) * (int64_t(dim) + 1);
+        if (d_ent) {
+          if (c0 < dim) sr[c0] = a0;
+          if (c0 + 64 < dim) sr[c0 + 64] = a1;
+          if (c0 + 128 < dim) sr[c0 + 128] = a2;
+          if (c0 + 192 < dim) sr[c0 + 192] = a3;
+        }
+        if (sl == 0 && lane == 0) sr[dim] = sb;
+      }
+    }
+  }
+}
+
+// (c) fold: one WAVE per window w with (w + 1) S < n_live. s = first[w] is followed only if it lies in the window and entries s
+// and s + S name one live row, each looked up through plan_row; the run's heads s, s + S, ... are then checked 64 at a time,
+// a lane per head, and the slots of the ones before the first head of another row are added in piece order from +0.
+__global__ __launch_bounds__(TPB) void cand_split_fold_kernel(int64_t total, int64_t n_cand, int64_t n_local, int64_t row0, int dim,
+                                                              int S, const int64_t *__restrict__ cand, int64_t ldc,
+                                                              const int64_t *__restrict__ perm, int64_t n_live, int64_t windows,
+                                                              const int64_t *__restrict__ first, const float *__restrict__ slot,
+                                                              float *__restrict__ d_ent, int64_t lde, float *__restrict__ d_bias) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t width = int64_t(dim) + 1;
+  for (int64_t w = int64_t(blockIdx.x) * (TPB / 64) + wave; w < windows; w += int64_t(gridDim.x) * (TPB / 64)) {
+    const int64_t s = first[w];
+    if (s < w * S || s >= (w + 1) * S || s + S >= n_live) continue;      // wave-uniform
+    int64_t b = 0, j = 0;
+    const int64_t row = plan_row(perm, s, total, n_cand, cand, ldc, row0, n_local, b, j);
+    if (row < 0 || plan_row(perm, s + S, total, n_cand, cand, ldc, row0, n_local, b, j) != row) continue;
+    int64_t pieces = 0;
+    for (int64_t p0 = 0;; p0 += 64) {
+      const int64_t h = s + (p0 + lane) * S;
+      const bool mine = h < n_live && plan_row(perm, h, total, n_cand, cand, ldc, row0, n_local, b, j) == row;
+      const unsigned long long others = ~__ballot(mine);
+      const int n = others ? __builtin_ctzll(others) : 64;
+      pieces += n;
+      if (n < 64) break;
+    }
+    // piece p's head is entry s + p S of window s / S + p: slot 2 (s / S + p) + (p == 0), below 2 ceil(total / S) as s + p S < n_live
+    const float *base = slot + 2 * (s / S) * width;
+    for (int64_t c0 = (d_ent ? 0 : dim) + lane; c0 < width; c0 += 256) {
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+      for (int64_t p0 = 0; p0 < pieces; p0 += FOLD_UNR) {
+        float v0[FOLD_UNR], v1[FOLD_UNR], v2[FOLD_UNR], v3[FOLD_UNR];
+#pragma unroll
+        for (int u = 0; u < FOLD_UNR; ++u) {
+          const int64_t p = p0 + u;
+          const float *sr = base + (2 * p + (p == 0 ? 1 : 0)) * width;
+          const bool on = p < pieces;
+          v0[u] = on ? sr[c0] : 0.f;
+          v1[u] = on && c0 + 64 < width ? sr[c0 + 64] : 0.f;
+          v2[u] = on && c0 + 128 < width ? sr[c0 + 128] : 0.f;
+          v3[u] = on && c0 + 192 < width ? sr[c0 + 192] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < FOLD_UNR; ++u)
+          if (p0 + u < pieces) {
+            a0 = __fadd_rn(a0, v0[u]);
+            a1 = __fadd_rn(a1, v1[u]);
+            a2 = __fadd_rn(a2, v2[u]);
+            a3 = __fadd_rn(a3, v3[u]);
+          }
+      }
+      const float acc[4] = {a0, a1, a2, a3};
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int64_t c = c0 + 64 * t;
+        if (c < dim) {
+          if (d_ent) d_ent[row * lde + c] = acc[t];
+        } else if (c == dim && d_bias) {
+          d_bias[row] = acc[t];
+        }
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ (b) trunk tail
-constexpr int CW = 16;                                // columns of a workgroup
+constexpr int CW = 16;                               // columns of a workgroup
 constexpr int RL = TPB / CW;                          // row lanes: thread (ty, tx) walks rows ty, ty + RL, ... of column tx
 
 // u = z keep inv_keep in the order of model._drawn_dropout: (x * mask) * (1 / keep)
@@ -459,5 +692,51 @@ extern "C" int mgcn_cand_bce_bwd_ent(int32_t batch, int64_t n_cand, int64_t n_lo
                         static_cast<hipStream_t>(stream)>>>(total, n_cand, n_local, ent_row0, dim, g_dev, ldg, cand_dev, ldc, perm_dev,
                                                             n_live, x_dev, ldx, d_ent_dev, lde, d_bias_dev);
   MGCN_CHECK_LAUNCH("cand_bwd_ent_kernel");
+  return MGCN_OK;
+}
+
+extern "C" size_t mgcn_cand_bwd_ent_split_workspace(int32_t batch, int64_t n_cand, int32_t dim, int32_t run_split) {
+  const int64_t lim = (int64_t(1) << 31) - 64;
+  if (batch < 0 || n_cand < 0 || batch >= lim || n_cand >= lim || dim < 1 || run_split < SPLIT_MIN || run_split > SPLIT_MAX) return 0;
+  return split_workspace(int64_t(batch) * n_cand, dim, run_split) + 16;     // (never 0 for sizes it takes: 0 is the refusal)
+}
+
+extern "C" int mgcn_cand_bce_bwd_ent_split(int32_t batch, int64_t n_cand, int64_t n_local, int64_t ent_row0, int32_t dim,
+                                           const float *g_dev, int64_t ldg, const int64_t *cand_dev, int64_t ldc,
+                                           const int64_t *perm_dev, int64_t n_live, const float *x_dev, int64_t ldx, float *d_ent_dev,
+                                           int64_t lde, float *d_bias_dev, const int64_t *keys_dev, int32_t run_split, void *ws_dev,
+                                           size_t ws_bytes, void *stream) {
+  const char *what = "cand_bce_bwd_ent_split";
+  if (int rc = check_cand_bwd(what, batch, n_cand, n_local, ent_row0, dim, g_dev, ldg, cand_dev, ldc)) return rc;
+  MGCN_REQUIRE(perm_dev && keys_dev && (!d_ent_dev || x_dev), "%s: null pointer", what);
+  MGCN_REQUIRE(!d_ent_dev || (ldx >= dim && lde >= dim), "%s: leading dimension too small", what);
+  const int64_t total = int64_t(batch) * n_cand;
+  MGCN_REQUIRE(n_live >= 0 && n_live <= total, "%s: n_live outside [0, batch * n_cand]", what);
+  MGCN_REQUIRE(run_split >= SPLIT_MIN && run_split <= SPLIT_MAX, "%s: run_split = %d outside [%d, %d]", what, run_split, SPLIT_MIN,
+               SPLIT_MAX);
+  MGCN_REQUIRE(total == 0 || n_local + 1 <= INT64_MAX / total, "%s: the keys row * (batch * n_cand) + position overflow int64", what);
+  const size_t need = mgcn_cand_bwd_ent_split_workspace(batch, n_cand, dim, run_split);
+  MGCN_REQUIRE(ws_dev && mgcn::aligned16(ws_dev), "%s: null pointer or misaligned workspace", what);
+  MGCN_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", what, ws_bytes, need);
+  if (batch == 0 || n_cand == 0 || n_local == 0 || n_live == 0 || (!d_ent_dev && !d_bias_dev)) return MGCN_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const SplitWs ws = split_carve(ws_dev, total, dim, run_split);
+  const int64_t cap = int64_t(1) << 22;
+  const int64_t tgroups = (n_live + TPB - 1) / TPB, wgroups = (n_live + TPB / 64 - 1) / (TPB / 64);
+  cand_split_heads_kernel<<<dim3(unsigned(tgroups < cap ? tgroups : cap)), dim3(TPB), 0, s>>>(
+      total, n_cand, n_local, ent_row0, run_split, cand_dev, ldc, perm_dev, keys_dev, n_live, ws.mark, ws.first);
+  MGCN_CHECK_LAUNCH("cand_split_heads_kernel");
+  cand_split_piece_kernel<<<dim3(unsigned(wgroups < cap ? wgroups : cap)), dim3(TPB), 0, s>>>(
+      total, n_cand, n_local, ent_row0, dim, run_split, g_dev, ldg, cand_dev, ldc, perm_dev, n_live, x_dev, ldx, ws.mark, ws.slot,
+      d_ent_dev, lde, d_bias_dev);
+  MGCN_CHECK_LAUNCH("cand_split_piece_kernel");
+  const int64_t windows = (n_live - 1) / run_split;   // the windows w whose successor's first entry (w + 1) S exists
+  if (windows > 0) {
+    const int64_t fgroups = (windows + TPB / 64 - 1) / (TPB / 64);
+    cand_split_fold_kernel<<<dim3(unsigned(fgroups < cap ? fgroups : cap)), dim3(TPB), 0, s>>>(
+        total, n_cand, n_local, ent_row0, dim, run_split, cand_dev, ldc, perm_dev, n_live, windows, ws.first, ws.slot, d_ent_dev, lde,
+        d_bias_dev);
+    MGCN_CHECK_LAUNCH("cand_split_fold_kernel");
+  }
   return MGCN_OK;
 }

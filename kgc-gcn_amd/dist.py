@@ -833,7 +833,7 @@ def train_epoch_sharded(model, queries, index, graph, optimizer, params, batch_s
 
 
 def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer, labels=None, lbl_smooth=0.0, clip=None, group=None,
-                                  generator=None, loss='bce', logq=None):
+                                  generator=None, loss='bce', logq=None, run_split=None):
     """train_step_sharded on per-query candidate lists (MGCN.forward_loss_candidates) in place of the
     rank's whole entity shard: everything up to and including the ConvE trunk is train_step_sharded's (same refusals, same
     dropout rules, same collectives), then rank r scores only the list positions whose id lies in its rows [n0, n1). No
@@ -852,20 +852,23 @@ def train_step_sharded_candidates(model, graph, src, rel, cand, index, optimizer
     statistics (_CandCEFn with the exchange); lbl_smooth is spread over the list; the ranks' losses add up as above.
     logq (None: the above, unchanged): f32 [N] over the WHOLE table, sampling.NegativeSampler.logq on the device, softmax only
     (forward_loss_candidates(logq=...)): the rank hands its scoring stage bias[n0:n1] - logq[n0:n1].
+    run_split (None: the above, unchanged): forward_loss_candidates(run_split=...), DESIGN §4.16, THE SAME VALUE ON EVERY RANK: a
+    run is cut from its own first entry, so a rank's rows keep the bits of the one-rank step with the same run_split.
     Returns the global loss (0-dim tensor, detached)."""
     what = 'train_step_sharded_candidates'
     model._refuse_training_ee16(what, training=True)      # (before the list is looked at: the refusal _sharded_trunk repeats)
-    cand = refuse_list_step(what, model, src.numel(), cand, labels, loss, logq)
+    cand = refuse_list_step(what, model, src.numel(), cand, labels, loss, logq, run_split)
     if labels is None and index is None:
         raise _native.NativeError('%s: give index or labels' % what)
     ex, ent, xt = _sharded_trunk(model, graph, src, rel, optimizer, group, generator, what)
     keys = index.query_keys(src, rel) if labels is None else None
-    loss = list_loss_stage(xt, ent, _own_bias(model, ex), cand, labels, index, keys, lbl_smooth, loss, logq, ex.total, ex.n0, ex)
+    loss = list_loss_stage(xt, ent, _own_bias(model, ex), cand, labels, index, keys, lbl_smooth, loss, logq, ex.total, ex.n0, ex,
+                           run_split=run_split)
     return _sharded_finish(model, ex, loss, optimizer, clip, group)
 
 
 def train_epoch_sharded_candidates(model, queries, index, graph, optimizer, params, batch_size, num_neg, draw_seed, first_step=0,
-                                   generator=None, group=None, loss='bce', sampler=None):
+                                   generator=None, group=None, loss='bce', sampler=None, run_split=None):
     """One epoch of train_step_sharded_candidates on counter-drawn lists, as harness.train_sampled_negatives(draw_seed=...): the
     shuffle of train_epoch_sharded (`generator` seeded identically on every rank, or a seed the group agrees on), the key check
     once, and per step i the lists and global labels of harness.draw_candidates(q, index, N, num_neg, draw_seed, first_step + i,
@@ -874,7 +877,7 @@ def train_epoch_sharded_candidates(model, queries, index, graph, optimizer, para
     the steps' global losses. loss: 'bce' or 'softmax', handed to every step.
     sampler (None: uniform negatives, unchanged): a sampling.NegativeSampler on the device, THE SAME TABLE ON EVERY RANK
     (broadcast_sampler gives it): the negatives follow its table, and the softmax steps take its logq; nothing is exchanged per
-    step."""
+    step. run_split (None: unchanged) is handed to every step."""
     from .harness import check_query_keys, draw_candidates
     kind = loss             # (`loss` below is a step's result)
     from .utils import RunningAverage
@@ -894,6 +897,7 @@ def train_epoch_sharded_candidates(model, queries, index, graph, optimizer, para
         cand, labels = draw_candidates(q, index, n_ent, num_neg, draw_seed, int(first_step) + k, labels=True, sampler=sampler)
         loss = train_step_sharded_candidates(model, graph, q[:, 0], q[:, 1], cand, index, optimizer, labels=labels,
                                              lbl_smooth=params.lbl_smooth, clip=params.clip_grad, group=group, loss=kind,
-                                             logq=sampler.logq if sampler is not None and kind == 'softmax' else None)
+                                             logq=sampler.logq if sampler is not None and kind == 'softmax' else None,
+                                             run_split=run_split)
         loss_avg.update(loss.item())
     return loss_avg()

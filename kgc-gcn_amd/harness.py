@@ -143,7 +143,7 @@ def check_query_keys(queries, index):
 
 
 def train_sampled_negatives(model, queries, index, graph, optimizer, params, batch_size, num_neg, generator=None, draw_seed=None,
-                            first_step=0, loss='bce', captured=None, sampler=None):
+                            first_step=0, loss='bce', captured=None, sampler=None, run_split=None):
     """One epoch like train_device_labels' eager loop, on sampled negatives: per step the candidate lists of
     sample_candidates (one known tail + num_neg uniform ids per query) and MGCN.forward_loss_candidates over them, so that no
     step touches a [B, N] block. `generator`: a CPU generator (or None: the default one) shuffles as train_device_labels does and
@@ -162,7 +162,8 @@ def train_sampled_negatives(model, queries, index, graph, optimizer, params, bat
     sampler (None: uniform negatives, unchanged): a sampling.NegativeSampler on params.device; needs draw_seed (the generator
     route stays uniform and refuses a sampler). The negatives follow its table; loss='softmax' subtracts its logq from every
     candidate's logit, loss='bce' takes the weighted lists without a correction (the word2vec convention). A
-    checkpoint stores sampler.state_dict() next to draw_seed and the step count."""
+    checkpoint stores sampler.state_dict() next to draw_seed and the step count.
+    run_split (None: unchanged): handed to every forward_loss_candidates, or set on the captured step."""
     kind = loss             # (`loss` below is a step's result)
     if sampler is not None and draw_seed is None:
         from . import _native
@@ -189,7 +190,7 @@ def train_sampled_negatives(model, queries, index, graph, optimizer, params, bat
     if captured is not None and captured is not False:
         step = _captured_cand_step(model, graph, index, optimizer, params) if captured is True else captured
         step.num_neg, step.loss, step.draw_seed, step.draw_step = int(num_neg), kind, int(draw_seed), int(first_step)
-        step.sampler = sampler
+        step.sampler, step.run_split = sampler, run_split
         starts = range(0, queries.size(0), batch_size)
         losses = torch.empty(len(starts), dtype=torch.float32, device=dev)
         for k, i in enumerate(starts):
@@ -203,12 +204,13 @@ def train_sampled_negatives(model, queries, index, graph, optimizer, params, bat
         if draw_seed is None:
             cand = sample_candidates(q, index, n_ent, num_neg, generator=generator, check=False)
             optimizer.zero_grad()
-            loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, index=index, lbl_smooth=params.lbl_smooth, loss=kind)
+            loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, index=index, lbl_smooth=params.lbl_smooth, loss=kind,
+                                                 run_split=run_split)
         else:
             cand, labels = draw_candidates(q, index, n_ent, num_neg, draw_seed, int(first_step) + k, labels=True, sampler=sampler)
             optimizer.zero_grad()
             loss = model.forward_loss_candidates(q[:, 0], q[:, 1], cand, graph, labels=labels, lbl_smooth=params.lbl_smooth, loss=kind,
-                                                 logq=logq)
+                                                 logq=logq, run_split=run_split)
         loss.backward()
         if hasattr(optimizer, 'clip_and_step'):          # optim.ClipAdam: norm, clipping and update on the HIP kernels
             optimizer.clip_and_step(params.clip_grad)
