@@ -1125,6 +1125,62 @@ int mgcn_cand_bce_bwd_ent_split(int32_t batch, int64_t n_cand, int64_t n_local, 
                                 const float *x_dev, int64_t ldx, float *d_ent_dev, int64_t lde, float *d_bias_dev,
                                 const int64_t *keys_dev, int32_t run_split, void *ws_dev, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (19) Edge dropout and own-triple removal: this step's graph as a copy of the slot records (csrc/dropout.hip, the table in
+ * csrc/csr_build.cpp) — additive, MGCN_ABI_VERSION stays 4. Every aggregation kernel of (2), (3), (3s) and (4) takes
+ * a slot's norm from its record and nothing else, and a slot with norm +0.0f contributes nothing (1v). So a training step that
+ * drops edges needs no new layout: it needs rec' [2E], the records with the norms of the kept edge list, which the layers are
+ * handed in place of rec. rowptr, slot_dst, mirror, the type lists and the hub chunks stay as (1) built them.
+ * THE DEFINITION. E = num_edges_half. Directed edge d in [0, 2E) has the undirected id u = d mod E: an edge and its reverse live
+ * and die together. keep(u) is element (row u, column 0) of the mask of (12) under `key` and `threshold`, i.e. byte u of
+ * mgcn_dropout_mask_host with rows = E, cols = 1, row0 = 0 (callers use key(seed, step, site 0x3000) and T(p); at p = 0 that is
+ * T = 2^32 - 1, so a word of 0xffffffff still drops its edge). forced [E] uint8, optional: kept(u) = keep(u) && !forced[u].
+ * For node n and half h, deg_h[n] is the number of kept slots in the destination run of n in half 1 - h — the non-hub run of
+ * rowptr, or the hub's segment chunks[first].begin .. chunks[first + count - 1].end — which by mirror symmetry is the kept
+ * out-degree of n in half h, the by-SOURCE degree (Q2) of the kept list. Integer counts: no order, no atomics. T[d] is
+ * mgcn_edge_drop_table_host's table, the feeder's own expression d ? 1.0f / sqrt(float(d)) : 0.0f evaluated on the host; the
+ * device only looks values up. For slot p in half h with source s and destination n:
+ *   rec'[p] = {src, type, kept(eid_p mod E) ? T[deg_h[s]] * T[deg_h[n]] : +0.0f, eid},   one f32 multiply, as in the feeder,
+ * so a kept slot carries, bit for bit, the norm mgcn_csr_build_host folds for that edge when it is run on the kept edge list alone.
+ * An eid outside [0, 2E) or a src / destination outside [0, N) gives norm +0.0f and addresses nothing.
+ * The graph must be mirror-symmetric and carry the backward index (slot_dst): callers refuse other graphs (the Python seam raises).
+ *   table_dev [table_len] f32 with table_len > max_run, max_run = the longest destination run in either half (hub segments
+ *   included); a count at or above table_len (a max_run that was not the graph's) reads nothing and gives 0.
+ *   cinv_dev [2, N] f32: workspace, written by the call (T[deg_h[n]]); rec_out_dev [2E]: 16-byte aligned, not rec_dev.
+ * mgcn_edge_drop_records: two launches on `stream`, no host read, no allocation, no LDS, no atomics, plain vector stores; it may
+ * be captured. (a) eight lanes per (half, node) walk the run, count the kept slots (an integer sum across the lanes) and store
+ * T[count]; (b) one lane per slot writes its record with one 16-byte store. The bits do not depend on the grid. threshold = 0
+ * (p >= 1): every norm is +0.0f. mgcn_edge_drop_records_dev: the same kernels, instantiated on the key source as (12)'s _dev
+ * forms: `site` and the 8-byte aligned step word sm(sm(seed) ^ step) in device memory, read when the launch RUNS.
+ * mgcn_edge_drop_records_host: the CPU twin from the same inline functions (test infrastructure); it measures max_run itself.
+ * mgcn_edge_drop_table_host: T[0 .. len), len in [1, 2^31).
+ * mgcn_edge_flags_from_queries: forced[u] = 1 for every directed edge whose key src * 2R + type equals a query key qkey[b]
+ * (the keys of mgcn_filter_index_build), u its undirected id. ekeys_dev [2E] int64 ascending, eund_dev [2E] int32 the undirected
+ * id of each sorted entry (an id outside [0, E) is skipped). One wave per query bisects ekeys (mgcn_filter_mask's idiom) and its
+ * lanes walk the run of equal keys; racing stores write the same byte. The caller zero-fills forced first; bytes of edges that no
+ * query names are left as they are.
+ * MGCN_EINVAL, nothing launched and nothing written: a null pointer (forced may be NULL; hubinfo / chunks when num_chunks = 0),
+ * a negative size, N, 2E or num_chunks outside int32 slots, records not 16-byte aligned, rec_out_dev == rec_dev, table_len <=
+ * max_run, a null or misaligned step_key_dev.
+ * NOT MEASURED: the kernels' own times (DESIGN §4.17 times the calls and the step).
+ */
+int mgcn_edge_drop_table_host(int64_t len, float *table_host);
+int mgcn_edge_drop_records(int64_t num_nodes, int64_t num_edges_half, const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev,
+                           const int32_t *slot_dst_dev, const int32_t *hubinfo_dev, const int32_t *chunks_dev, int64_t num_chunks,
+                           const float *table_dev, int64_t table_len, int64_t max_run, const uint8_t *forced_dev, uint64_t key,
+                           uint32_t threshold, float *cinv_dev, mgcn_edge_rec *rec_out_dev, void *stream);
+int mgcn_edge_drop_records_dev(int64_t num_nodes, int64_t num_edges_half, const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev,
+                               const int32_t *slot_dst_dev, const int32_t *hubinfo_dev, const int32_t *chunks_dev, int64_t num_chunks,
+                               const float *table_dev, int64_t table_len, int64_t max_run, const uint8_t *forced_dev,
+                               const uint64_t *step_key_dev, uint64_t site, uint32_t threshold, float *cinv_dev,
+                               mgcn_edge_rec *rec_out_dev, void *stream);
+int mgcn_edge_drop_records_host(int64_t num_nodes, int64_t num_edges_half, const int32_t *rowptr_host, const mgcn_edge_rec *rec_host,
+                                const int32_t *slot_dst_host, const int32_t *hubinfo_host, const int32_t *chunks_host, int64_t num_chunks,
+                                const float *table_host, int64_t table_len, const uint8_t *forced_host, uint64_t key,
+                                uint32_t threshold, float *cinv_host, mgcn_edge_rec *rec_out_host);
+int mgcn_edge_flags_from_queries(int32_t batch, const int64_t *qkey_dev, int64_t num_edges_half, const int64_t *ekeys_dev,
+                                 const int32_t *eund_dev, uint8_t *forced_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,11 @@ _SIGNATURES = {
     'mgcn_cand_draw_alias_dev': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64,
                                                 _ptr]),
     'mgcn_cand_draw_alias_host': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64]),
+    'mgcn_edge_drop_table_host': (ctypes.c_int, [_i64, _ptr]),
+    'mgcn_edge_drop_records': (ctypes.c_int, [_i64, _i64] + [_ptr] * 5 + [_i64, _ptr, _i64, _i64, _ptr, _u64, _u32, _ptr, _ptr, _ptr]),
+    'mgcn_edge_drop_records_dev': (ctypes.c_int, [_i64, _i64] + [_ptr] * 5 + [_i64, _ptr, _i64, _i64, _ptr, _ptr, _u64, _u32, _ptr, _ptr, _ptr]),
+    'mgcn_edge_drop_records_host': (ctypes.c_int, [_i64, _i64] + [_ptr] * 5 + [_i64, _ptr, _i64, _ptr, _u64, _u32, _ptr, _ptr]),
+    'mgcn_edge_flags_from_queries': (ctypes.c_int, [_i32, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
     'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
     'mgcn_ingest_close': (None, [_ptr]),
     'mgcn_ingest_count': (_i64, [_ptr, _i32]),
@@ -1830,6 +1835,110 @@ def dropout_mask_host(rows, cols, key, row0, p):
         return out
     _check(lib().mgcn_dropout_mask_host(int(rows), int(cols), out.data_ptr(), int(cols),
                                         int(key) & _M64, int(row0) & _M64, dropout_scale(p)[0]), 'mgcn_dropout_mask_host')
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# (19) edge dropout and own-triple removal: this step's slot records (csrc/dropout.hip)
+EDGE_DROP_SITE = 0x3000
+
+
+def edge_drop_threshold(p):
+    """The threshold of the edge site: T(p) of the dropout sites for p < 1 (p <= 0 included: T(0) = 2^32 - 1), 0 for p >= 1."""
+    return 0 if p >= 1 else dropout_threshold(max(float(p), 0.0))
+
+
+def edge_drop_table_host(length):
+    """(19) T[d] = deg^-1/2 as the feeder forms it, d = 0 .. length - 1: a host f32 tensor."""
+    out = torch.empty(int(length), dtype=torch.float32)
+    _check(lib().mgcn_edge_drop_table_host(int(length), out.data_ptr()), 'mgcn_edge_drop_table_host')
+    return out
+
+
+def max_run_host(rowptr, hubinfo, chunks, num_chunks):
+    """The longest destination run of a layout (host tensors of csr_build_host), hub segments included."""
+    longest = int((rowptr[:, 1:] - rowptr[:, :-1]).max()) if rowptr.size(1) > 1 else 0
+    if num_chunks:
+        first, cnt = hubinfo[:, :, 0].reshape(-1).long(), hubinfo[:, :, 1].reshape(-1).long()
+        hub = cnt > 0
+        if bool(hub.any()):
+            seg = chunks[(first + cnt - 1)[hub], 1] - chunks[first[hub], 0]
+            longest = max(longest, int(seg.max()))
+    return longest
+
+
+def _refuse_edge_drop_graph(csr, what):
+    if not csr.has_backward:
+        raise NativeError('%s: graph was prepared without the backward indices' % what)
+    if not csr.mirrored:
+        raise NativeError('%s: the edge list is not mirror-symmetric (edge e + E is not the reverse of edge e), so an edge and its '
+                          'reverse cannot be dropped together and the degrees of the kept graph do not follow from the destination runs'
+                          % what)
+
+
+def edge_drop_records(csr, state, key, p, forced=None, out=None):
+    """(19) rec' [2E, 4] int32 of `csr` under `key` (an int, or a DeviceKey: the _dev entry point) and drop probability `p`, with
+    the undirected edges marked in `forced` [E] uint8 (None: none) removed as well. `state` is csr.edge_drop_state(). p <= 0
+    without `forced`: nothing is launched and csr.rec itself is returned. `out`: the tensor to write (None: a fresh one)."""
+    what = 'edge_drop_records'
+    _refuse_edge_drop_graph(csr, what)
+    if p <= 0 and forced is None:
+        return csr.rec
+    N, E = csr.num_nodes, csr.num_edges_half
+    if out is None:
+        out = torch.empty_like(csr.rec)
+    if out.dtype != torch.int32 or tuple(out.shape) != tuple(csr.rec.shape) or not out.is_contiguous() or out.data_ptr() == csr.rec.data_ptr():
+        raise NativeError('%s: out must be a contiguous int32 %s that is not csr.rec' % (what, tuple(csr.rec.shape)))
+    if forced is not None and (forced.dtype != torch.uint8 or forced.numel() != E or not forced.is_contiguous()):
+        raise NativeError('%s: forced must be a contiguous uint8 [%d]' % (what, E))
+    _same_device(csr.rec, state.table, state.cinv, forced, out)
+    hubs = csr.num_chunks > 0
+    head = (N, E, _dev(csr.rowptr, torch.int32, 'rowptr'), _dev(csr.rec, torch.int32, 'rec'), _dev(csr.slot_dst, torch.int32, 'slot_dst'),
+            _dev(csr.hubinfo, torch.int32, 'hubinfo') if hubs else None, _dev(csr.chunks, torch.int32, 'chunks') if hubs else None,
+            csr.num_chunks, _dev(state.table, torch.float32, 'table'), state.table.numel(), state.max_run,
+            _dev(forced, torch.uint8, 'forced', True))
+    tail = (edge_drop_threshold(p), _dev(state.cinv, torch.float32, 'cinv'), _dev(out, torch.int32, 'rec_out'), _stream(out))
+    if isinstance(key, DeviceKey):
+        _same_device(out, key.word)
+        _check(lib().mgcn_edge_drop_records_dev(*(head + (key.word.data_ptr(), key.site) + tail)), 'mgcn_edge_drop_records_dev')
+    else:
+        _check(lib().mgcn_edge_drop_records(*(head + (int(key) & _M64,) + tail)), 'mgcn_edge_drop_records')
+    return out
+
+
+def edge_drop_records_host(host, table, key, p, forced=None):
+    """(19) on the CPU from the same inline functions: `host` is csr_build_host's dict (with the backward index), `table` a host
+    f32 tensor, `forced` a host uint8 [E] or None. Returns (rec' [2E, 4] int32, cinv [2, N] f32). Test infrastructure."""
+    rowptr, rec = host['rowptr'], host['rec']
+    N, E = rowptr.size(1) - 1, rec.size(0) // 2
+    out, cinv = torch.empty_like(rec), torch.empty((2, max(N, 1)), dtype=torch.float32)
+    nch = int(host['num_chunks'])
+    if forced is not None and (forced.dtype != torch.uint8 or forced.numel() != E or forced.is_cuda or not forced.is_contiguous()):
+        raise NativeError('edge_drop_records_host: forced must be a contiguous host uint8 [%d]' % E)
+    _check(lib().mgcn_edge_drop_records_host(
+        N, E, rowptr.data_ptr(), rec.data_ptr(), host['slot_dst'].data_ptr(), host['hubinfo'].data_ptr() if nch else None,
+        host['chunks'].data_ptr() if nch else None, nch, table.data_ptr(), table.numel(), None if forced is None else forced.data_ptr(),
+        int(key) & _M64, edge_drop_threshold(p), cinv.data_ptr(), out.data_ptr()), 'mgcn_edge_drop_records_host')
+    return out, cinv[:, :N]
+
+
+def edge_flags_from_queries(qkey, state, num_edges_half, out=None):
+    """(19) forced [E] uint8: 1 for every undirected edge one of whose directions (src, type) is a query of `qkey` [B] int64
+    (src * 2R + type, FilterIndex.query_keys), 0 elsewhere. `out` (None: state.forced) is zero-filled first."""
+    out = state.forced if out is None else out
+    E = int(num_edges_half)
+    if out.dtype != torch.uint8 or out.numel() != E or not out.is_contiguous():
+        raise NativeError('edge_flags_from_queries: out must be a contiguous uint8 [%d]' % E)
+    if state.ekeys.numel() != 2 * E or state.eund.numel() != 2 * E:
+        raise NativeError('edge_flags_from_queries: ekeys / eund must hold %d entries' % (2 * E))
+    qkey = qkey.reshape(-1).contiguous()
+    _same_device(qkey, state.ekeys, state.eund, out)
+    out.zero_()
+    if qkey.numel() == 0 or E == 0:
+        return out
+    _check(lib().mgcn_edge_flags_from_queries(qkey.numel(), _dev(qkey, torch.int64, 'qkey'), E, _dev(state.ekeys, torch.int64, 'ekeys'),
+                                              _dev(state.eund, torch.int32, 'eund'), _dev(out, torch.uint8, 'forced'), _stream(out)),
+           'mgcn_edge_flags_from_queries')
     return out
 
 

@@ -11,6 +11,9 @@ device that the host computes in the eager step, so the trajectory is the eager 
 reproducible (the HIP trunk and query path). A scheduler's lr, load_dropout_state, a changed seed and model.load_state_dict (an
 in-place copy) take effect on the next replay without a new capture.
 
+With params.edge_drop / params.edge_drop_queries on the step's record rewrite is captured too: the zero fill and the
+flags kernel follow the batch, mgcn_edge_drop_records_dev reads the same step word, and both switches are part of the capture key.
+
 CapturedCandidateStep, at the end of the module, is the same wrapper around the sampled-negative step: its lists are
 drawn inside the graph by mgcn_cand_draw_dev from a second device word that travels in the same copy.
 
@@ -35,10 +38,10 @@ import numpy as np
 import torch
 
 from . import _native
-from .model import _counter_dropout_wanted
+from .model import _counter_dropout_wanted, edge_drop_switches
 
-_ENV_SWITCHES = ('MGCN_QUERY_TRAIN', 'MGCN_TRUNK_TRAIN', 'MGCN_DROPOUT', 'MGCN_TRAIN_TORCH', 'MGCN_TRUNK')
-_PARAM_SWITCHES = ('query_path_train', 'conve_trunk_train', 'dropout', 'conve_trunk')
+_ENV_SWITCHES = ('MGCN_QUERY_TRAIN', 'MGCN_TRUNK_TRAIN', 'MGCN_DROPOUT', 'MGCN_TRAIN_TORCH', 'MGCN_TRUNK', 'MGCN_EDGE_DROP', 'MGCN_EDGE_DROP_QUERIES')
+_PARAM_SWITCHES = ('query_path_train', 'conve_trunk_train', 'dropout', 'conve_trunk', 'edge_drop', 'edge_drop_queries')
 _RING = 8      # pinned staging slots: the host may run this many replays ahead of the device before it waits for a copy
 
 
@@ -217,6 +220,13 @@ class CapturedTrainStep(object):
             _native.dropout_apply(x, k0, 0, 0.5)
             _native.dropout_apply_pair(x, k0, x, k1, 0, 0.5)
             _native.dropout_mask(2, x.size(1), k0, 0, 0.5, out=torch.zeros((2, 8), dtype=torch.uint8, device=dev)[:, :x.size(1)])
+        p_edge, by_queries = edge_drop_switches(self.model.params)
+        if p_edge > 0 or by_queries:      # this step's records: the _dev rewrite and the flags, into scratch tensors
+            csr = self.model._layout_for(self.graph)[0]
+            state = csr.edge_drop_state()
+            flags = _native.edge_flags_from_queries(torch.zeros(1, dtype=torch.int64, device=dev), state, csr.num_edges_half,
+                                                    out=torch.zeros_like(state.forced))
+            _native.edge_drop_records(csr, state, _native.DeviceKey(st.word, _native.EDGE_DROP_SITE), p_edge, flags)
         t = [torch.ones(4, device=dev) for _ in range(4)]
         for wd in (0.0, 0.01):
             _native.adam_step([t[0]], [t[1]], [t[2]], [t[3]], None, 0.0, 1.0, 0.9, 0.999, 1e-8, wd, hyper_dev=st.hyper[0])

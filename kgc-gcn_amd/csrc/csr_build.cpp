@@ -15,6 +15,12 @@ char *error_buffer() {
 }
 }  // namespace mgcn
 
+namespace {
+// deg^-1/2 with inf -> 0 (model.py:76-77), the ONE expression behind every f32 norm: the feeder's cinv below and the table that the
+// per-step record rewrite looks up (mgcn_edge_drop_table_host, include/mgcn_hip.h (19))
+inline float inv_sqrt_degree(int64_t deg) { return deg ? 1.0f / std::sqrt(static_cast<float>(deg)) : 0.0f; }
+}  // namespace
+
 extern "C" int mgcn_abi_version(void) { return MGCN_ABI_VERSION; }
 extern "C" const char *mgcn_last_error(void) { return mgcn::error_buffer(); }
 
@@ -97,7 +103,7 @@ extern "C" int mgcn_csr_build_host(int64_t num_nodes, int64_t num_edges_half, in
     // degree by SOURCE within the half (model.py:74-75), deg^-1/2 with inf -> 0 (model.py:76-77)
     std::vector<int32_t> deg(N, 0);
     for (int64_t e = lo; e < lo + E; ++e) deg[src[e]]++;
-    for (int64_t n = 0; n < N; ++n) cinv[n] = deg[n] ? 1.0f / std::sqrt(static_cast<float>(deg[n])) : 0.0f;
+    for (int64_t n = 0; n < N; ++n) cinv[n] = inv_sqrt_degree(deg[n]);
     for (int64_t e = lo; e < lo + E; ++e) {
       const int64_t slot = cursor[h * N + dst[e]]++;
       mgcn_edge_rec r;
@@ -135,6 +141,14 @@ extern "C" int mgcn_csr_build_host(int64_t num_nodes, int64_t num_edges_half, in
     std::memcpy(tcur.data(), typeptr_host, sizeof(int32_t) * (num_rel_rows + 1));
     for (int64_t s = 0; s < E2; ++s) typeslots_host[tcur[rec_host[s].type]++] = static_cast<int32_t>(s);
   }
+  return MGCN_OK;
+}
+
+// T[d] = the feeder's deg^-1/2 for d = 0 .. len - 1 (include/mgcn_hip.h (19)): the device looks these up and never forms one itself
+extern "C" int mgcn_edge_drop_table_host(int64_t len, float *table_host) {
+  MGCN_REQUIRE(len >= 1 && len < (int64_t(1) << 31) && table_host, "mgcn_edge_drop_table_host: len = %lld outside [1, 2^31) or a null pointer",
+               (long long)len);
+  for (int64_t d = 0; d < len; ++d) table_host[d] = inv_sqrt_degree(d);
   return MGCN_OK;
 }
 

@@ -7,6 +7,9 @@
 // The same Philox function also draws the candidate lists of sampled-negative training (include/mgcn_hip.h (15)):
 // mgcn_cand_draw, its device-key form and its host twin, at the end of the anonymous namespace, and their weighted forms
 // (include/mgcn_hip.h (17)), which read one alias-table word per negative.
+// And its keep bits decide which edges a training step's graph keeps (include/mgcn_hip.h (19)): mgcn_edge_drop_records,
+// its device-key form and host twin rewrite the slot records' norms for the kept edge list, mgcn_edge_flags_from_queries marks the
+// edges that answer the batch's own queries; after the draw kernels in the anonymous namespace.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -447,7 +450,223 @@ int draw_launch(const char *what, int64_t batch, const DrawArgs &a, const uint64
   return MGCN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Edge dropout and own-triple removal (include/mgcn_hip.h (19)): this step's graph is a copy of the slot records with
+// new norms. An undirected edge u = eid mod E is kept iff element (row u, column 0) of the site's mask is a keep bit and forced[u]
+// is not set; a node's degree is the number of kept slots of its destination run in the other half (by mirror symmetry its kept
+// out-degree in this one); the norm of a kept slot is T[deg(src)] * T[deg(dst)] with the host-built table T[d] = 1 / sqrt(float(d)).
+// Integers and table look-ups only up to the one f32 multiply, so the copy has the feeder's bits for the kept edge list.
+struct EdgeDropArgs {
+  int64_t num_nodes, num_edges_half;
+  const int32_t *rowptr;           // [2, N + 1]
+  const mgcn_edge_rec *rec;        // [2E]
+  const int32_t *slot_dst;         // [2E], bit 31 = half
+  const int32_t *hubinfo, *chunks; // null: no destination is a hub
+  int64_t num_chunks;
+  const float *table;              // T[0 .. table_len)
+  int64_t table_len;
+  const uint8_t *forced;           // [E] or null
+  uint64_t key;                    // the site's key, or the site id in the _dev entry point
+  uint32_t threshold;
+  float *cinv;                     // [2, N] workspace: T[deg_h[n]]
+  mgcn_edge_rec *rec_out;          // [2E]
+};
+
+// kept(eid mod E); an edge id outside [0, 2E) is no edge and is never kept (nothing is addressed through it)
+__host__ __device__ inline bool edge_kept(const EdgeDropArgs &a, int32_t eid) {
+  const int64_t E = a.num_edges_half;
+  if (uint64_t(int64_t(eid)) >= uint64_t(2 * E)) return false;
+  const int64_t u = eid >= E ? eid - E : eid;
+  uint32_t w[4];
+  dropout_words(a.key, uint64_t(u), 0u, w);
+  return w[0] < a.threshold && !(a.forced && a.forced[u]);
+}
+
+// the destination run [b, e) of node n in half h: the non-hub run of rowptr, or the hub's segment (its chunks are contiguous);
+// whatever the arrays hold, the run stays inside [0, 2E)
+__host__ __device__ inline void edge_run(const EdgeDropArgs &a, int h, int64_t n, int64_t &b, int64_t &e) {
+  const int64_t N = a.num_nodes, E2 = 2 * a.num_edges_half;
+  b = a.rowptr[h * (N + 1) + n], e = a.rowptr[h * (N + 1) + n + 1];
+  if (a.hubinfo) {
+    const int64_t first = a.hubinfo[(h * N + n) * 2], cnt = a.hubinfo[(h * N + n) * 2 + 1];
+    if (cnt > 0 && first >= 0 && first + cnt <= a.num_chunks) b = a.chunks[first * 4], e = a.chunks[(first + cnt - 1) * 4 + 1];
+  }
+  if (b < 0) b = 0;
+  if (e > E2) e = E2;
+  if (e < b) e = b;
+}
+
+__host__ __device__ inline float edge_table(const EdgeDropArgs &a, int64_t deg) { return deg < a.table_len ? a.table[deg] : 0.f; }
+
+// the new record of slot p: src, type and eid as they are, the norm of the kept graph or +0.0f
+__host__ __device__ inline mgcn_edge_rec edge_record(const EdgeDropArgs &a, int64_t p) {
+  mgcn_edge_rec r = a.rec[p];
+  const int32_t sd = a.slot_dst[p];
+  const int64_t N = a.num_nodes, n = sd & 0x7fffffff, s = r.src, h = (uint32_t(sd) >> 31) & 1u;
+  float norm = 0.f;
+  if (edge_kept(a, r.eid) && uint64_t(s) < uint64_t(N) && n < N) norm = a.cinv[h * N + s] * a.cinv[h * N + n];
+  r.norm = norm;
+  return r;
+}
+
+constexpr int EDGE_GS = 8;      // lanes per (half, node) in the degree launch
+
+// launch 1: EDGE_GS lanes per (half h, node n) count the kept slots of n's run in half 1 - h and lane 0 stores T[count]
+template <bool KD>
+__global__ __launch_bounds__(TPB) void edge_degree_kernel(EdgeDropArgs a, const uint64_t *__restrict__ step_key) {
+  a.key = site_key<KD>(a.key, step_key);
+  const int64_t N = a.num_nodes, units = 2 * N, groups = int64_t(gridDim.x) * (TPB / EDGE_GS);
+  const int lane = threadIdx.x % EDGE_GS;
+  // every lane of a wave runs the same number of turns, so the shuffles below always meet whole groups
+  const int64_t turns = (units + groups - 1) / groups;
+  int64_t i = int64_t(blockIdx.x) * (TPB / EDGE_GS) + threadIdx.x / EDGE_GS;
+  for (int64_t t = 0; t < turns; ++t, i += groups) {
+    int count = 0;
+    if (i < units) {
+      const int h = i >= N ? 1 : 0;
+      int64_t b, e;
+      edge_run(a, 1 - h, i - h * N, b, e);
+      for (int64_t p = b + lane; p < e; p += EDGE_GS) count += edge_kept(a, a.rec[p].eid) ? 1 : 0;
+    }
+#pragma unroll
+    for (int m = EDGE_GS / 2; m >= 1; m >>= 1) count += __shfl_xor(count, m, EDGE_GS);
+    if (i < units && lane == 0) a.cinv[i] = edge_table(a, count);
+  }
+}
+
+// launch 2: one lane per slot, one 16-byte store
+template <bool KD>
+__global__ __launch_bounds__(TPB) void edge_records_kernel(EdgeDropArgs a, const uint64_t *__restrict__ step_key) {
+  a.key = site_key<KD>(a.key, step_key);
+  const int64_t slots = 2 * a.num_edges_half, stride = int64_t(gridDim.x) * TPB;
+  for (int64_t p = int64_t(blockIdx.x) * TPB + threadIdx.x; p < slots; p += stride) {
+    const mgcn_edge_rec r = edge_record(a, p);
+    *reinterpret_cast<int4 *>(a.rec_out + p) = make_int4(r.src, r.type, __float_as_int(r.norm), r.eid);
+  }
+}
+
+// every check of mgcn_edge_drop_records / _dev / _host; max_run: the longest destination run (hub segments included)
+int check_edge_drop(const char *what, const EdgeDropArgs &a, int64_t max_run) {
+  const int64_t N = a.num_nodes, E = a.num_edges_half;
+  MGCN_REQUIRE(N >= 0 && E >= 0 && a.num_chunks >= 0 && max_run >= 0, "%s: negative size", what);
+  MGCN_REQUIRE(N < (int64_t(1) << 31) - 1 && 2 * E < (int64_t(1) << 31) - 1 && a.num_chunks < (int64_t(1) << 31) - 1,
+               "%s: sizes exceed int32 slots", what);
+  MGCN_REQUIRE(a.rowptr && a.table && (N == 0 || a.cinv) && (E == 0 || (a.rec && a.slot_dst && a.rec_out)), "%s: null pointer", what);
+  MGCN_REQUIRE(a.num_chunks == 0 || (a.hubinfo && a.chunks), "%s: null pointer (hubinfo / chunks of %lld chunks)", what, (long long)a.num_chunks);
+  MGCN_REQUIRE(E == 0 || (mgcn::aligned16(a.rec) && mgcn::aligned16(a.rec_out)), "%s: records not aligned to 16 bytes", what);
+  MGCN_REQUIRE(a.rec != a.rec_out, "%s: rec_out is rec (the canonical records stay as they are)", what);
+  MGCN_REQUIRE(a.table_len > max_run, "%s: the table holds %lld entries, the longest run has %lld slots", what, (long long)a.table_len,
+               (long long)max_run);
+  return MGCN_OK;
+}
+
+int edge_drop_launch(const char *what, EdgeDropArgs a, int64_t max_run, const uint64_t *step_key_dev, void *stream) {
+  if (int rc = check_edge_drop(what, a, max_run)) return rc;
+  if (!a.num_chunks) a.hubinfo = a.chunks = nullptr;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (a.num_nodes > 0) {
+    const dim3 grid(grid_for(2 * a.num_nodes * EDGE_GS)), block(TPB);
+    if (step_key_dev)
+      edge_degree_kernel<true><<<grid, block, 0, st>>>(a, step_key_dev);
+    else
+      edge_degree_kernel<false><<<grid, block, 0, st>>>(a, nullptr);
+    MGCN_CHECK_LAUNCH(what);
+  }
+  if (a.num_edges_half > 0) {
+    const dim3 grid(grid_for(2 * a.num_edges_half)), block(TPB);
+    if (step_key_dev)
+      edge_records_kernel<true><<<grid, block, 0, st>>>(a, step_key_dev);
+    else
+      edge_records_kernel<false><<<grid, block, 0, st>>>(a, nullptr);
+    MGCN_CHECK_LAUNCH(what);
+  }
+  return MGCN_OK;
+}
+
+// One wave per query: the lower bound of its key in the sorted directed-edge keys (mgcn_filter_mask's bisection), then the lanes
+// walk the run of equal keys and store byte 1 for each entry's undirected edge. Racing stores write the same value.
+__global__ __launch_bounds__(TPB) void edge_flags_kernel(int32_t batch, const int64_t *__restrict__ qkey, int64_t num_edges_half,
+                                                         const int64_t *__restrict__ ekeys, const int32_t *__restrict__ eund,
+                                                         uint8_t *__restrict__ forced) {
+  const int64_t b = int64_t(blockIdx.x) * (TPB / 64) + threadIdx.x / 64, E2 = 2 * num_edges_half;
+  if (b >= batch) return;
+  const int64_t q = qkey[b];
+  int64_t k0 = 0, k1 = E2;
+  while (k0 < k1) {
+    const int64_t mid = (k0 + k1) >> 1;
+    if (ekeys[mid] < q) k0 = mid + 1; else k1 = mid;
+  }
+  for (int64_t i = k0 + threadIdx.x % 64; i < E2 && ekeys[i] == q; i += 64) {
+    const int32_t u = eund[i];
+    if (uint64_t(int64_t(u)) < uint64_t(num_edges_half)) forced[u] = 1;
+  }
+}
+
 }  // namespace
+
+extern "C" int mgcn_edge_drop_records(int64_t num_nodes, int64_t num_edges_half, const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev,
+                                      const int32_t *slot_dst_dev, const int32_t *hubinfo_dev, const int32_t *chunks_dev, int64_t num_chunks,
+                                      const float *table_dev, int64_t table_len, int64_t max_run, const uint8_t *forced_dev, uint64_t key,
+                                      uint32_t threshold, float *cinv_dev, mgcn_edge_rec *rec_out_dev, void *stream) {
+  const EdgeDropArgs a = {num_nodes, num_edges_half, rowptr_dev, rec_dev,    slot_dst_dev, hubinfo_dev, chunks_dev, num_chunks,
+                          table_dev, table_len,      forced_dev, key,        threshold,    cinv_dev,    rec_out_dev};
+  return edge_drop_launch("mgcn_edge_drop_records", a, max_run, nullptr, stream);
+}
+
+extern "C" int mgcn_edge_drop_records_dev(int64_t num_nodes, int64_t num_edges_half, const int32_t *rowptr_dev, const mgcn_edge_rec *rec_dev,
+                                          const int32_t *slot_dst_dev, const int32_t *hubinfo_dev, const int32_t *chunks_dev,
+                                          int64_t num_chunks, const float *table_dev, int64_t table_len, int64_t max_run,
+                                          const uint8_t *forced_dev, const uint64_t *step_key_dev, uint64_t site, uint32_t threshold,
+                                          float *cinv_dev, mgcn_edge_rec *rec_out_dev, void *stream) {
+  const char *what = "mgcn_edge_drop_records_dev";
+  if (int rc = check_step_key(what, step_key_dev)) return rc;
+  const EdgeDropArgs a = {num_nodes, num_edges_half, rowptr_dev, rec_dev,    slot_dst_dev, hubinfo_dev, chunks_dev, num_chunks,
+                          table_dev, table_len,      forced_dev, site,       threshold,    cinv_dev,    rec_out_dev};
+  return edge_drop_launch(what, a, max_run, step_key_dev, stream);
+}
+
+// the CPU twin, from the same inline functions; it measures the longest run itself
+extern "C" int mgcn_edge_drop_records_host(int64_t num_nodes, int64_t num_edges_half, const int32_t *rowptr_host, const mgcn_edge_rec *rec_host,
+                                           const int32_t *slot_dst_host, const int32_t *hubinfo_host, const int32_t *chunks_host,
+                                           int64_t num_chunks, const float *table_host, int64_t table_len, const uint8_t *forced_host,
+                                           uint64_t key, uint32_t threshold, float *cinv_host, mgcn_edge_rec *rec_out_host) {
+  const char *what = "mgcn_edge_drop_records_host";
+  EdgeDropArgs a = {num_nodes,  num_edges_half, rowptr_host, rec_host, slot_dst_host, hubinfo_host, chunks_host, num_chunks,
+                    table_host, table_len,      forced_host, key,      threshold,     cinv_host,    rec_out_host};
+  if (int rc = check_edge_drop(what, a, 0)) return rc;
+  if (!a.num_chunks) a.hubinfo = a.chunks = nullptr;
+  const int64_t N = num_nodes;
+  int64_t max_run = 0;
+  for (int h = 0; h < 2; ++h)
+    for (int64_t n = 0; n < N; ++n) {
+      int64_t b, e;
+      edge_run(a, h, n, b, e);
+      if (e - b > max_run) max_run = e - b;
+    }
+  if (int rc = check_edge_drop(what, a, max_run)) return rc;
+  for (int h = 0; h < 2; ++h)
+    for (int64_t n = 0; n < N; ++n) {
+      int64_t b, e, count = 0;
+      edge_run(a, 1 - h, n, b, e);
+      for (int64_t p = b; p < e; ++p) count += edge_kept(a, rec_host[p].eid) ? 1 : 0;
+      cinv_host[h * N + n] = edge_table(a, count);
+    }
+  for (int64_t p = 0; p < 2 * num_edges_half; ++p) rec_out_host[p] = edge_record(a, p);
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_edge_flags_from_queries(int32_t batch, const int64_t *qkey_dev, int64_t num_edges_half, const int64_t *ekeys_dev,
+                                            const int32_t *eund_dev, uint8_t *forced_dev, void *stream) {
+  const char *what = "mgcn_edge_flags_from_queries";
+  MGCN_REQUIRE(batch >= 0 && num_edges_half >= 0, "%s: negative size", what);
+  MGCN_REQUIRE(2 * num_edges_half < (int64_t(1) << 31) - 1, "%s: sizes exceed int32 slots", what);
+  if (batch == 0 || num_edges_half == 0) return MGCN_OK;
+  MGCN_REQUIRE(qkey_dev && ekeys_dev && eund_dev && forced_dev, "%s: null pointer", what);
+  edge_flags_kernel<<<dim3(unsigned((int64_t(batch) + TPB / 64 - 1) / (TPB / 64))), dim3(TPB), 0, static_cast<hipStream_t>(stream)>>>(
+      batch, qkey_dev, num_edges_half, ekeys_dev, eund_dev, forced_dev);
+  MGCN_CHECK_LAUNCH(what);
+  return MGCN_OK;
+}
 
 extern "C" int mgcn_cand_draw(int64_t batch, int64_t n_cand, int64_t num_entities, const int64_t *qkey_dev, int64_t num_keys,
                               const int64_t *keys_dev, const int64_t *ptr_dev, const int32_t *tails_dev, int64_t n_tails, uint64_t key,

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from . import _native
 from .autograd import _AggregateFn, _LayerTrainFn
-from .model import _drawn_dropout, counter_dropout, list_loss_stage, query_rows, refuse_list_step, table_bce_stage
+from .model import _drawn_dropout, counter_dropout, list_loss_stage, query_rows, refuse_list_step, step_csr, table_bce_stage
 
 
 def shard_bounds(n, world):
@@ -758,11 +758,13 @@ def _sharded_trunk(model, graph, src, rel, optimizer, group, generator, what):
             raise _native.NativeError('%s: layer %s is outside the HIP training path' % (what, layer))
     x, rel_e = model.entity_embedding, model.relation_embedding
     drop_ctx = model._begin_dropout_step()       # (seed, step) with the counter-based dropout on, else None
+    # this step's graph: every rank rewrites the whole record array, which it holds; csr itself with the switches off
+    step = step_csr(model, csr, drop_ctx, (src, rel), what)
     for li, (layer, table) in enumerate(zip(layers, tables)):
         last = li == len(layers) - 1
         bn = layer.ent_bn
         rels = torch.cat([rel_e, layer.loop_rel], dim=0)
-        agg = _AggregateFn.apply(x, rels, table, csr, (n0, n1))
+        agg = _AggregateFn.apply(x, rels, table, step, (n0, n1))
         x_own = x if (n0, n1) == (0, x.size(0)) else x[n0:n1]
         a_loop = (x_own * rels[-1]) * layer.loop_edge
         keys = None if drop_ctx is None else \

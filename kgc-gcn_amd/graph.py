@@ -210,6 +210,46 @@ class GraphCSR(object):
         (i0, i1), (o0, o1), (h0, h1) = self._shard_bounds(n0, n1)
         return torch.cat([table_slot_order[i0:i1], table_slot_order[o0:o1], table_slot_order[h0:h1]], dim=0).contiguous()
 
+    # -- this step's graph (include/mgcn_hip.h (19)) --------------------------------
+    def edge_drop_state(self):
+        """The graph-static parts of the per-step record rewrite, built once and cached: `table` (T[d] = deg^-1/2 for every run
+        length, from the host), `max_run`, `ekeys` / `eund` (the directed edges' keys src * 2R + type, ascending, and each sorted
+        entry's undirected id: what mgcn_edge_flags_from_queries bisects), and the two per-step workspaces `cinv` [2, N] and
+        `forced` [E], which the rewrite consumes before it returns. The record copy itself is a fresh tensor per step: the
+        backward of a step reads the records its forward read. Refuses (NativeError) a graph that is not mirror-symmetric or was
+        built without the backward index."""
+        import types
+        _native._refuse_edge_drop_graph(self, 'GraphCSR.edge_drop_state')
+        dev = self.rec.device
+        st = self.__dict__.get('_edge_drop')
+        if st is None or st.table.device != dev:
+            E, N = self.num_edges_half, self.num_nodes
+            max_run = _native.max_run_host(self.rowptr.cpu(), self.hubinfo.cpu(), self.chunks.cpu(), self.num_chunks)
+            rec = self.rec.to(torch.int64)
+            keys = rec[:, 0] * (self.num_rel_rows - 1) + rec[:, 1]
+            ekeys, order = torch.sort(keys)
+            eund = (rec[:, 3].index_select(0, order) % max(E, 1)).to(torch.int32)
+            st = types.SimpleNamespace(table=_native.edge_drop_table_host(max_run + 1).to(dev), max_run=max_run, ekeys=ekeys.contiguous(),
+                                       eund=eund.contiguous(), cinv=torch.zeros((2, max(N, 1)), dtype=torch.float32, device=dev),
+                                       forced=torch.zeros(E, dtype=torch.uint8, device=dev))
+            self._edge_drop = st
+        return st
+
+    def with_records(self, rec):
+        """A shallow view of this graph that shares every array but `rec` (this step's records, (19)); it has no live view
+        (live_rowptr / live_rec are None: the live view leaves out the slots whose CANONICAL norm is zero). Caches that hold
+        device buffers (hub partial sums, shard indices) are shared with the graph, not copied."""
+        import copy
+        if rec.dtype != torch.int32 or tuple(rec.shape) != tuple(self.rec.shape) or rec.device != self.rec.device or not rec.is_contiguous():
+            raise _native.NativeError('GraphCSR.with_records: rec must be a contiguous int32 %s on %s' % (tuple(self.rec.shape), self.rec.device))
+        for name in ('_shard_cache', '_hub_partials'):
+            self.__dict__.setdefault(name, {})
+        view = copy.copy(self)
+        view.rec, view.live_rowptr, view.live_rec = rec, None, None
+        view.num_dead_slots = 0
+        view.__dict__.pop('_edge_drop', None)
+        return view
+
     def norms(self):
         """Per-slot degree norm (f32 view of the record's third word)."""
         return self.rec[:, 2].contiguous().view(torch.float32)

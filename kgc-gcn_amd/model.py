@@ -17,6 +17,9 @@ What runs where
     csrc/conve_train.hip; with params.query_path_train = 'hip' (or MGCN_QUERY_TRAIN=hip) the rest of the training step's query path
     runs on csrc/query_train.hip: the trunk's tail hidden_drop -> bn2 -> relu, forward and backward, and the backward of the two
     query-row gathers all_ent[src], all_rel[rel] (a fixed-order sum in place of index_add_'s float atomics).
+  * with params.edge_drop = p and / or params.edge_drop_queries = True (MGCN_EDGE_DROP, MGCN_EDGE_DROP_QUERIES; both need the
+    counter-based dropout) the layers of a training step aggregate over this step's graph: a copy of the slot records whose norms
+    are those of the kept edges, written on the device by csrc/dropout.hip (step_csr below).
 There is no CPU path: tensors that are not on a GPU make the native layer raise.
 """
 import os
@@ -82,6 +85,44 @@ def _counter_dropout_wanted(params):
     """The switch of the counter-based dropout: params.dropout == 'counter', overridden in both directions by the environment
     variable MGCN_DROPOUT ('counter' or 'torch')."""
     return (os.environ.get('MGCN_DROPOUT') or getattr(params, 'dropout', 'torch')) == 'counter'
+
+
+def edge_drop_switches(params):
+    """(p, by_queries) of the per-step graph: params.edge_drop (default 0.0; the environment variable
+    MGCN_EDGE_DROP overrides) is the share of undirected edges dropped each training step, params.edge_drop_queries (default
+    False; MGCN_EDGE_DROP_QUERIES = 1 / 0 overrides) removes the edges that answer the batch's own queries."""
+    env_p, env_q = os.environ.get('MGCN_EDGE_DROP'), os.environ.get('MGCN_EDGE_DROP_QUERIES')
+    p = float(env_p) if env_p else float(getattr(params, 'edge_drop', 0.0) or 0.0)
+    by_queries = (env_q == '1') if env_q else bool(getattr(params, 'edge_drop_queries', False))
+    return p, by_queries
+
+
+def step_csr(model, csr, drop_ctx, queries, what):
+    """The graph the layers of ONE training-mode encoder pass aggregate over: `csr` itself with both switches of
+    edge_drop_switches off (no launch, nothing changes), else a view of it (GraphCSR.with_records) whose records carry the norms
+    of this step's kept edges (include/mgcn_hip.h (19)): one rewrite per step serves every layer, forward and backward. `drop_ctx`
+    is _begin_dropout_step's (seed, step[, device word]): the keep bits are those of site _native.EDGE_DROP_SITE at that step,
+    so the switches need params.dropout = 'counter'. `queries` = (src, rel) of the batch or None: with edge_drop_queries on,
+    every edge (s, r, .) of a query (s, r) is removed with its reverse. Shared by MGCN.encode and the sharded steps, where every
+    rank rewrites the whole record array, which it holds anyway."""
+    p, by_queries = edge_drop_switches(model.params)
+    if not model.training or (p <= 0 and not by_queries):
+        return csr
+    if drop_ctx is None:
+        raise _native.NativeError("%s: params.edge_drop / params.edge_drop_queries need params.dropout = 'counter' (or "
+                                  'MGCN_DROPOUT=counter) on a GPU: the step\'s (seed, step) is the counter-based dropout\'s' % what)
+    by_queries = by_queries and queries is not None
+    if p <= 0 and not by_queries:
+        return csr
+    state = csr.edge_drop_state()
+    forced = None
+    if by_queries:
+        src, rel = queries
+        qkey = src.reshape(-1).to(torch.int64) * (csr.num_rel_rows - 1) + rel.reshape(-1).to(torch.int64)
+        forced = _native.edge_flags_from_queries(qkey, state, csr.num_edges_half)
+    rec = _native.edge_drop_records(csr, state, _site_key(drop_ctx, _native.EDGE_DROP_SITE), p, forced)
+    model._edge_drop_count = getattr(model, '_edge_drop_count', 0) + 1
+    return csr.with_records(rec)
 
 
 def edge_table_dtype(params):
@@ -721,8 +762,12 @@ class MGCN(nn.Module):
             self._use_reference_order()      # this graph gathers rows by edge id: the tables must be in reference order
         return csr, ent_identity, edge_identity
 
-    def encode(self, data):
+    def encode(self, data, queries=None):
         """model.py:25-34: (all_ent [N, O], all_rel [2R, O]) for the whole graph.
+
+        `queries` = (src, rel) of the batch the result will answer, or None: read only in training mode with
+        params.edge_drop_queries on (step_csr), where the layers then aggregate over a graph without the edges
+        (s, r, .) of those queries; with both edge switches off, and in eval mode, the call is what it was without the argument.
 
         Eval mode without autograd ("frozen") adds two things the reference does not have, both result-neutral:
         the whole layer stack is replayed from a captured hipGraph (the step is ~6 short launches, so host launch
@@ -732,7 +777,7 @@ class MGCN(nn.Module):
         csr, ent_identity, edge_identity = self._layout_for(data)
         frozen = not self.training and not torch.is_grad_enabled()
         if not frozen:
-            return self._encode_layers(data, csr, ent_identity, edge_identity, self._begin_dropout_step())
+            return self._encode_layers(data, csr, ent_identity, edge_identity, self._begin_dropout_step(), queries)
 
         tensors = self._encoder_tensors()
         use_cache = getattr(self.params, 'cache_encoder', True)
@@ -747,8 +792,16 @@ class MGCN(nn.Module):
             self._enc_cache = (stamp, out[0], out[1])
         return out
 
-    def _encode_layers(self, data, csr, ent_identity, edge_identity, drop_ctx=None):
+    def _encode_for(self, data, src, rel):
+        """encode(data) for a step that answers the queries (src, rel): they are handed over only where they are read, in
+        training mode with edge_drop_queries on; every other call is encode(data) as it was."""
+        if self.training and edge_drop_switches(self.params)[1]:
+            return self.encode(data, queries=(src, rel))
+        return self.encode(data)
+
+    def _encode_layers(self, data, csr, ent_identity, edge_identity, drop_ctx=None, queries=None):
         edge_type, edge_ids = data.edge_attr
+        csr = step_csr(self, csr, drop_ctx, queries, 'MGCN.encode')      # this step's graph: csr itself with the switches off
         x = self.entity_embedding if ent_identity else torch.index_select(self.entity_embedding, 0, data.entity)
         rel = self.relation_embedding
         layers = [self.conv1] + list(self.conv1_extra)
@@ -820,7 +873,7 @@ class MGCN(nn.Module):
         elsewhere, smoothed as data_loader.py:41-43. Falls back to the two-step form for batch sizes the fused launch
         does not take (B % 4 != 0)."""
         self._refuse_training_ee16('MGCN.forward_loss')
-        all_ent, all_rel = self.encode(data)
+        all_ent, all_rel = self._encode_for(data, src, rel)
         x = self.conv2.trunk(query_rows(self, all_ent, src), query_rows(self, all_rel, rel))
         keys = index.query_keys(src, rel)
         return table_bce_stage(self, x, all_ent.contiguous(), self.conv2.bias, keys, index, lbl_smooth, all_ent.size(0))
@@ -855,7 +908,7 @@ class MGCN(nn.Module):
         if (index is None) == (labels is None):
             raise _native.NativeError('forward_loss_candidates: give exactly one of index / labels')
         cand = refuse_list_step('forward_loss_candidates', self, src.numel(), cand, labels, loss, logq, run_split)
-        all_ent, all_rel = self.encode(data)
+        all_ent, all_rel = self._encode_for(data, src, rel)
         x = self.conv2.trunk(query_rows(self, all_ent, src), query_rows(self, all_rel, rel))
         keys = index.query_keys(src, rel) if labels is None else None
         return list_loss_stage(x, all_ent.contiguous(), self.conv2.bias, cand, labels, index, keys, lbl_smooth, loss, logq,
