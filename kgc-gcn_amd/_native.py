@@ -2,160 +2,25 @@
 
 There is deliberately NO fallback: if the library is missing or a tensor is not resident on a GPU the
 call raises. torch is used here for device memory and the current HIP stream only.
+
+The header is the one description of the C ABI: the restype / argtypes of every entry point and the constants the header
+defines are parsed from its text at import (_parse_abi, _abi_defines), the same text the compiler holds every definition
+under csrc/ to. Adding an entry point means declaring it in the header and writing its wrapper here, nothing else.
 """
 import ctypes
 import math
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MGCN_LIB') or os.path.join(_HERE, 'csrc', 'libmgcn_hip.so')   # MGCN_LIB: A/B builds
-ABI_VERSION = 4
+_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'mgcn_hip.h')   # the tree's header, also under MGCN_LIB
 
 _lib = None
 
-_i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-_u32, _u64 = ctypes.c_uint32, ctypes.c_uint64
-_ptr = ctypes.c_void_p
-
-_SIGNATURES = {
-    'mgcn_abi_version': (ctypes.c_int, []),
-    'mgcn_last_error': (ctypes.c_char_p, []),
-    'mgcn_csr_build_host': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
-                                           _ptr] + [_ptr] * 4),
-    'mgcn_aggregate_fwd': (ctypes.c_int, [_i64, _i64, _i32, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
-                                          _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr]),
-    'mgcn_aggregate_bwd': (ctypes.c_int, [_i64, _i64, _i32, _i32] + [_ptr] * 6 + [_i64, _ptr, _ptr] +
-                           [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_aggregate_bwd_workspace': (ctypes.c_size_t, [_i64, _i32, _i32, _i64]),
-    'mgcn_aggregate_bwd_shard': (ctypes.c_int, [_i64, _i64, _i32, _i32, _ptr, _ptr] + [_i64] * 8 + [_ptr] * 4 + [_i64, _ptr, _ptr,
-                                                _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_aggregate_bwd_shard_workspace': (ctypes.c_size_t, [_i64, _i32, _i32, _i64]),
-    'mgcn_bn_train_stage_sum': (ctypes.c_int, [_i64, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
-    'mgcn_bn_train_stage_center': (ctypes.c_int, [_i64, _i32, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr]),
-    'mgcn_bn_train_stage_finish': (ctypes.c_int, [_i64, _i32, _ptr, _ptr, _i64, _i64] + [_ptr] * 5 + [_f32, _f32, _ptr, _ptr, _ptr]),
-    'mgcn_bn_train_bwd_stage_sums': (ctypes.c_int, [_i64, _i32] + [_ptr] * 8),
-    'mgcn_bn_train_bwd_stage_apply': (ctypes.c_int, [_i64, _i32] + [_ptr] * 8 + [_i64, _i64] + [_ptr] * 5),
-    'mgcn_dense_bn_tanh_fwd': (ctypes.c_int, [_i64, _i32, _i32, _ptr, _i64] + [_ptr] * 6 + [_f32, _ptr, _i64, _ptr]),
-    'mgcn_layer_fwd_fused': (ctypes.c_int, [_i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
-                                            _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i64, _i64, _i64,
-                                            _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr,
-                                            _ptr]),
-    'mgcn_layer_fwd_fused_live': (ctypes.c_int, [_i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
-                                                 _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i64, _i64, _i64,
-                                                 _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr,
-                                                 _ptr]),
-    'mgcn_aggregate_fwd_ee16': (ctypes.c_int, [_i64, _i64, _i32, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
-                                               _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _i64, _i64, _i64, _ptr]),
-    'mgcn_layer_fwd_fused_ee16': (ctypes.c_int, [_i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
-                                                 _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i64, _i64, _i64,
-                                                 _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr,
-                                                 _ptr]),
-    'mgcn_layer_fwd_fused_live_ee16': (ctypes.c_int, [_i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32,
-                                                      _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i64, _i64, _i64,
-                                                      _i64, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr,
-                                                      _ptr]),
-    'mgcn_csr_live_view_host': (ctypes.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
-    'mgcn_pack_weights': (ctypes.c_int, [_i32, _i32, _ptr, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_packed_weights_bytes': (ctypes.c_size_t, [_i32, _i32]),
-    'mgcn_pack_weights_gen': (ctypes.c_int, [_i32, _i32, _i32, _ptr, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_packed_weights_bytes_gen': (ctypes.c_size_t, [_i32, _i32, _i32]),
-    'mgcn_matmul_f32': (ctypes.c_int, [_i64, _i32, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr]),
-    'mgcn_bn_tanh_train_workspace': (ctypes.c_size_t, [_i64, _i32]),
-    'mgcn_bn_tanh_train_fwd': (ctypes.c_int, [_i64, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _f32, _ptr,
-                                              _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_bn_tanh_train_bwd': (ctypes.c_int, [_i64, _i32] + [_ptr] * 11 + [ctypes.c_size_t, _ptr]),
-    'mgcn_matmul_tn_workspace': (ctypes.c_size_t, [_i64, _i32, _i32]),
-    'mgcn_matmul_tn_f32': (ctypes.c_int, [_i64, _i32, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_score_fwd': (ctypes.c_int, [_i32, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr]),
-    'mgcn_score_target': (ctypes.c_int, [_i32, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
-    'mgcn_score_rank': (ctypes.c_int, [_i32, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i64,
-                                       _ptr, _i64, _ptr, _ptr]),
-    'mgcn_filter_mask': (ctypes.c_int, [_i32, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr]),
-    'mgcn_score_bce_partials': (_i64, [_i32, _i64]),
-    'mgcn_hub_partial_floats': (_i64, [_i64, _i32]),
-    'mgcn_fused_kernel_generation': (ctypes.c_int, [_i32, _i32, _i64, _i32]),
-    'mgcn_fused_cut': (ctypes.c_int, [_i32, _i32, _ptr, _ptr, _i32, _ptr]),
-    'mgcn_score_bce_fwd': (ctypes.c_int, [_i32, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _f32, _f32, _f32, _ptr,
-                                          _i64, _ptr, _ptr]),
-    'mgcn_label_rows': (ctypes.c_int, [_i32, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _f32, _f32, _ptr, _i64, _ptr]),
-    'mgcn_score_topk_workspace': (ctypes.c_size_t, [_i32, _i64, _i32]),
-    'mgcn_score_topk': (ctypes.c_int, [_i32, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _i64,
-                                       _ptr, _i64, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_topk_merge': (ctypes.c_int, [_i32, _i32, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _ptr]),
-    'mgcn_score_candidates': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64,
-                                             _ptr, _i64, _ptr]),
-    'mgcn_cand_labels': (ctypes.c_int, [_i32, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr]),
-    'mgcn_cand_bce_partials': (_i64, [_i32, _i64]),
-    'mgcn_cand_bce_fwd': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _f32, _f32,
-                                         _f32, _ptr, _i64, _ptr, _ptr]),
-    'mgcn_cand_bce_bwd_x': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr]),
-    'mgcn_cand_bce_bwd_ent': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64,
-                                             _ptr, _ptr]),
-    'mgcn_cand_bwd_ent_split_workspace': (ctypes.c_size_t, [_i32, _i64, _i32, _i32]),
-    'mgcn_cand_bce_bwd_ent_split': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64,
-                                                   _ptr, _ptr, _i32, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_cand_ce_partials': (_i64, [_i32, _i64]),
-    'mgcn_cand_ce_logits': (ctypes.c_int, [_i32, _i64, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64,
-                                           _ptr, _ptr]),
-    'mgcn_cand_ce_merge': (ctypes.c_int, [_i32, _i64, _ptr, _i64, _i64, _ptr, _ptr]),
-    'mgcn_cand_ce_finish': (ctypes.c_int, [_i32, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _f32, _f32, _ptr, _i64,
-                                           _ptr, _ptr]),
-    'mgcn_conve_packed_bytes': (ctypes.c_size_t, [_i32] * 5),
-    'mgcn_conve_pack': (ctypes.c_int, [_i32] * 5 + [_ptr, _ptr, _ptr, _i64, _ptr] + ([_ptr] * 4 + [_f32]) * 3 +
-                        [_ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_conve_trunk_workspace': (ctypes.c_size_t, [_i32] * 6),
-    'mgcn_conve_trunk_fwd': (ctypes.c_int, [_i32] * 6 + [_ptr, _i64, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _ptr,
-                                            ctypes.c_size_t, _ptr]),
-    'mgcn_conve_train_workspace': (ctypes.c_size_t, [_i32] * 6),
-    'mgcn_conve_train_fwd': (ctypes.c_int, [_i32] * 6 + [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr] +
-                             [_ptr, _ptr, _ptr, _ptr, _f32, _f32] * 2 + [_ptr, _f32, _ptr, _i64, _ptr, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_conve_train_bwd': (ctypes.c_int, [_i32] * 6 + [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64] + [_ptr] * 5 + [_f32, _ptr, _ptr, _i64,
-                                                         _ptr, _i64, _ptr, _i64] + [_ptr] * 7 + [_i64, _ptr, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_adam_sq_norms_workspace': (ctypes.c_size_t, [_i64, _ptr]),
-    'mgcn_adam_sq_norms': (ctypes.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_adam_clip_coef': (ctypes.c_int, [_i64, _ptr, _f32, _ptr, _ptr]),
-    'mgcn_adam_step': (ctypes.c_int, [_i64] + [_ptr] * 6 + [_f32, _f32] + [ctypes.c_double] * 4 + [_ptr]),
-    'mgcn_adam_step_dev': (ctypes.c_int, [_i64] + [_ptr] * 7 + [ctypes.c_double] * 4 + [_ptr]),
-    'mgcn_query_rows_bwd_workspace': (ctypes.c_size_t, [_i32]),
-    'mgcn_query_rows_bwd': (ctypes.c_int, [_i32, _i64, _i32, _ptr, _ptr, _i64, _ptr, _i64, _ptr, ctypes.c_size_t, _ptr]),
-    'mgcn_conve_tail_fwd': (ctypes.c_int, [_i32, _i32, _ptr, _i64, _ptr, _i64, _f32, _ptr, _ptr, _ptr, _ptr, _f32, _f32, _ptr, _i64, _ptr,
-                                           _i64, _ptr]),
-    'mgcn_conve_tail_bwd': (ctypes.c_int, [_i32, _i32, _ptr, _i64, _ptr, _i64, _f32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64,
-                                           _ptr, _ptr, _ptr]),
-    'mgcn_dropout_apply': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _i64, _u64, _u64, _u32, _f32, _ptr]),
-    'mgcn_dropout_apply_pair': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _i64, _u64, _ptr, _i64, _ptr, _i64, _u64, _u64, _u32, _f32,
-                                               _ptr]),
-    'mgcn_dropout_mask': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _u64, _u64, _u32, _ptr]),
-    'mgcn_dropout_apply_dev': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _i64, _ptr, _u64, _u64, _u32, _f32, _ptr]),
-    'mgcn_dropout_apply_pair_dev': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _i64, _u64, _ptr, _i64, _ptr, _i64, _u64, _ptr, _u64, _u32,
-                                                   _f32, _ptr]),
-    'mgcn_dropout_mask_dev': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _ptr, _u64, _u64, _u32, _ptr]),
-    'mgcn_dropout_mask_host': (ctypes.c_int, [_i64, _i32, _ptr, _i64, _u64, _u64, _u32]),
-    'mgcn_cand_draw': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _u64, _u64, _ptr, _i64, _ptr, _i64, _ptr]),
-    'mgcn_cand_draw_dev': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64, _ptr]),
-    'mgcn_cand_draw_host': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _u64, _u64, _ptr, _i64, _ptr, _i64]),
-    'mgcn_alias_build_host': (ctypes.c_int, [_i64, _ptr, _ptr]),
-    'mgcn_cand_draw_alias': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64, _ptr]),
-    'mgcn_cand_draw_alias_dev': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64,
-                                                _ptr]),
-    'mgcn_cand_draw_alias_host': (ctypes.c_int, [_i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _u64, _u64, _ptr, _i64, _ptr, _i64]),
-    'mgcn_edge_drop_table_host': (ctypes.c_int, [_i64, _ptr]),
-    'mgcn_edge_drop_records': (ctypes.c_int, [_i64, _i64] + [_ptr] * 5 + [_i64, _ptr, _i64, _i64, _ptr, _u64, _u32, _ptr, _ptr, _ptr]),
-    'mgcn_edge_drop_records_dev': (ctypes.c_int, [_i64, _i64] + [_ptr] * 5 + [_i64, _ptr, _i64, _i64, _ptr, _ptr, _u64, _u32, _ptr, _ptr, _ptr]),
-    'mgcn_edge_drop_records_host': (ctypes.c_int, [_i64, _i64] + [_ptr] * 5 + [_i64, _ptr, _i64, _ptr, _u64, _u32, _ptr, _ptr]),
-    'mgcn_edge_flags_from_queries': (ctypes.c_int, [_i32, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
-    'mgcn_ingest_open': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_ptr)]),
-    'mgcn_ingest_close': (None, [_ptr]),
-    'mgcn_ingest_count': (_i64, [_ptr, _i32]),
-    'mgcn_ingest_triples': (ctypes.c_int, [_ptr, _i32, _ptr]),
-    'mgcn_ingest_names_bytes': (_i64, [_ptr, _i32]),
-    'mgcn_ingest_names': (ctypes.c_int, [_ptr, _i32, _ptr, _ptr]),
-    'mgcn_filter_index_build': (ctypes.c_int, [_i64, _ptr, _i64, _ptr, _ptr, _ptr, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
-}
-
-EXPORTS = tuple(sorted(_SIGNATURES))
+_i32, _i64, _ptr = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
 
 
 class NativeError(RuntimeError):
@@ -165,6 +30,64 @@ class NativeError(RuntimeError):
 class FusedUnsupported(NativeError):
     """mgcn_layer_fwd_fused returned MGCN_EUNSUPPORTED (misaligned operand, shape outside the kernel): callers take the
     aggregation + dense launches instead."""
+
+
+_C_SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint32_t': ctypes.c_uint32,
+              'uint64_t': ctypes.c_uint64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float, 'double': ctypes.c_double}
+
+
+def _strip_comments(text):
+    return re.sub(r'/\*[^*]*\*+(?:[^/*][^*]*\*+)*/|//[^\n]*', ' ', text)     # /* ... */ (the unrolled form of /\*.*?\*/) and // ...
+
+
+def _abi_defines(text):
+    """{macro: value} of the header's `#define MGCN_<NAME> <integer>` lines."""
+    return {k: int(v) for k, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(MGCN_\w+)[ \t]+(\d+)[ \t]*$', _strip_comments(text), re.M)}
+
+
+def _c_type(fn, text, is_param):
+    """ctypes type of one parameter (`const float *x_dev`) or return type (`const char *`) of declaration `fn`."""
+    # [const] type [stars, `*const` too] [name]: no arrays, no function pointers
+    m = re.fullmatch(r'\s*(const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)(\w*)\s*', text)
+    const, base, stars, name = m.groups() if m else (None, None, '', '')
+    if stars:                                                              # `const char *` is a string, every other pointer an address
+        return ctypes.c_char_p if const and (base, stars.strip()) == ('char', '*') else ctypes.c_void_p
+    if base == 'void' and not (is_param or const or name):
+        return None
+    if base in _C_SCALARS and (is_param or not name):
+        return _C_SCALARS[base]
+    raise NativeError('include/mgcn_hip.h: %s: no ctypes type for `%s`' % (fn, ' '.join(text.split())))
+
+
+def _parse_abi(text):
+    """{name: (restype, [argtypes])} of every `<return type> mgcn_<name>(<params>);` in the text of include/mgcn_hip.h. Strict: a type
+    outside the map above, an array or function-pointer parameter, or a declaration this pattern cannot read raises."""
+    text = re.sub(r'^[ \t]*#[^\n]*', ' ', _strip_comments(text), flags=re.M)
+    table = {}
+    for stmt in re.split(r'[;{}]', text):
+        m = re.fullmatch(r'\s*([\w\s*]+?)\s*\b(mgcn_\w+)\s*\(([^()]*)\)\s*', stmt)
+        if m:
+            ret, fn, params = m.groups()
+            params = [] if params.strip() == 'void' else params.split(',')
+            table[fn] = (_c_type(fn, ret, False), [_c_type(fn, p, True) for p in params])
+    skipped = set(re.findall(r'\b(mgcn_\w+)\s*\(', text)) - set(table)
+    if skipped:
+        raise NativeError('include/mgcn_hip.h: cannot parse the declaration of %s' % ', '.join(sorted(skipped)))
+    return table
+
+
+def _read_header():
+    if not os.path.exists(_HEADER_PATH):
+        raise NativeError('%s not found: the binding takes the C ABI from it' % _HEADER_PATH)
+    with open(_HEADER_PATH) as f:
+        return f.read()
+
+
+_HEADER = _read_header()
+_SIGNATURES = _parse_abi(_HEADER)
+_DEFINES = _abi_defines(_HEADER)
+EXPORTS = tuple(sorted(_SIGNATURES))
+ABI_VERSION = _DEFINES['MGCN_ABI_VERSION']
 
 
 def lib():
@@ -1465,7 +1388,7 @@ def conve_train_bwd(geom, s, r, conv_w, fc_w, bn0_weight, bn0_bias, bn1_weight, 
 
 # ------------------------------------------------------------------------------------------------
 # (11) the training step's query path: the row gathers' backward and the trunk's tail
-QUERY_MAX_BATCH = 4096
+QUERY_MAX_BATCH = _DEFINES['MGCN_QUERY_MAX_BATCH']
 
 
 def query_rows_supported(batch):
@@ -1611,8 +1534,8 @@ def label_rows(qkey, keys, ptr, tails, n_local, lbl_smooth=0.0, num_entities=Non
     return out
 
 
-ADAM_CHUNK = 8192     # MGCN_ADAM_CHUNK: elements per workgroup of the optimizer kernels (csrc/optim.hip)
-ADAM_BATCH = 64       # MGCN_ADAM_BATCH: tensors per launch
+ADAM_CHUNK = _DEFINES['MGCN_ADAM_CHUNK']     # elements per workgroup of the optimizer kernels (csrc/optim.hip)
+ADAM_BATCH = _DEFINES['MGCN_ADAM_BATCH']     # tensors per launch
 
 
 def _ptr_array(tensors):
