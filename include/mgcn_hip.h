@@ -277,7 +277,9 @@ int mgcn_dense_bn_tanh_fwd(int64_t num_nodes, int32_t dim_in, int32_t dim_out, c
  * slots [rowptr_in[node_begin], rowptr_in[node_end]) followed by those of the out-half slots of the same nodes — and
  * then the hub slots [chunks[chunk_begin].begin, chunks[chunk_end - 1].end) of the same nodes — and passes
  * ee_sub_in / ee_sub_out / ee_sub_hub such that the row of (absolute) slot s is s - ee_sub_{region}; with the whole
- * table all three are 0. x_dev is always the whole [N, D] layer input.
+ * table all three are 0. x_dev is always the whole [N, D] layer input. The kernels carry ee_sub_in / ee_sub_out as int32 (slot
+ * indices are below 2^31) and the row stride of x as uint32: an offset outside int32 is MGCN_EINVAL, ldx >= 2^31 is
+ * MGCN_EUNSUPPORTED (callers use (2) + (4), whose strides are 64-bit); every address is then formed in 64 bits.
  * Hubs as in (2): hubinfo_dev / chunks_dev / [chunk_begin, chunk_end) / partial_dev [mgcn_hub_partial_floats(chunk_end -
  * chunk_begin, dim_in)] with its counters zero (one pre-pass launch before the layer's launch).
  * rel_out_dev (optional, [num_rel_rows - 1, dim_out]) = rel_dev @ rels_weight_dev [dim_in, dim_out] (model.py:107, the
@@ -409,6 +411,8 @@ int mgcn_layer_fwd_fused_live_ee16(int64_t num_nodes, int64_t num_edges_half, in
  * z, y [N, O] contiguous; save_mean / save_rstd [O] are kept for the backward. Reductions over rows are two-stage with fixed
  * row blocks (bitwise reproducible). workspace: mgcn_bn_tanh_train_workspace(N, O) bytes.
  * Backward: given gy = dL/dy, returns gz = dL/dz [N, O], gu = gz / 3 (= dL/du_* before the dropout masks), ggamma, gbeta [O].
+ * Every entry point of (4t) and (4s) returns MGCN_EINVAL, nothing launched, for num_rows * dim_out above 2^37 elements (their
+ * launch grids are sized in 32 bits; addresses inside the kernels are 64-bit).
  */
 size_t mgcn_bn_tanh_train_workspace(int64_t num_rows, int32_t dim_out);
 int mgcn_bn_tanh_train_fwd(int64_t num_rows, int32_t dim_out, const float *u_in_dev, const float *u_out_dev,

@@ -109,6 +109,9 @@ int layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, i
                    bn_gamma_dev && bn_beta_dev && (out_dev || node_end == node_begin) && (rel_dev || num_rel_rows == 1) &&
                    (num_edges_half == 0 || rec_dev), "layer_fwd_fused: null pointer");
   MGCN_REQUIRE(ldx >= dim_in && ldo >= dim_out, "layer_fwd_fused: ldx/ldo too small");
+  // the kernels carry the two shard offsets as int32 (fused_common.h LayerArgs): a value outside int32 would be cut silently
+  MGCN_REQUIRE(ee_sub_in >= INT32_MIN && ee_sub_in <= INT32_MAX && ee_sub_out >= INT32_MIN && ee_sub_out <= INT32_MAX,
+               "layer_fwd_fused: table shard offsets (%lld, %lld) exceed int32", (long long)ee_sub_in, (long long)ee_sub_out);
   const bool aligned = mgcn::aligned16(x_dev) && mgcn::aligned16(rel_dev) && mgcn::aligned16(loop_rel_dev) &&
                        mgcn::aligned16(loop_edge_dev) && (!ee_dev || (ee16 ? mgcn::aligned8(ee_dev) : mgcn::aligned16(ee_dev))) &&
                        mgcn::aligned16(out_dev) && mgcn::aligned16(wp_dev) && ldx % 4 == 0 && ldo % 4 == 0;

@@ -175,6 +175,12 @@ __global__ __launch_bounds__(TPB) void matmul_tn_fold_kernel(const float *__rest
   c[(i / nc) * ldc + (i % nc)] = s;
 }
 
+// Every (4t) / (4s) launch sizes a grid by rows / RB or rows * O / TPB in 32 bits: a block of more than 2^37 elements
+// (512 GiB of f32) is refused before anything is formed from it.
+inline bool rows_fit(int64_t num_rows, int32_t dim_out) { return dim_out > 0 && num_rows <= (int64_t(1) << 37) / dim_out; }
+#define MGCN_REQUIRE_ROWS_FIT(who) \
+  MGCN_REQUIRE(rows_fit(num_rows, dim_out), who ": num_rows x dim_out = %lld x %d exceeds 2^37 elements", (long long)num_rows, dim_out)
+
 int tn_blocks(int64_t k) {
   int64_t nb = (k + 255) / 256;
   return int(nb < 1 ? 1 : (nb > 256 ? 256 : nb));
@@ -193,6 +199,7 @@ extern "C" int mgcn_bn_tanh_train_fwd(int64_t num_rows, int32_t dim_out, const f
                                       float eps, float *z_dev, float *y_dev, float *save_mean_dev, float *save_rstd_dev,
                                       float *workspace_dev, size_t workspace_bytes, void *stream) {
   MGCN_REQUIRE(num_rows > 0 && dim_out > 0, "bn_tanh_train_fwd: bad sizes");
+  MGCN_REQUIRE_ROWS_FIT("bn_tanh_train_fwd");
   MGCN_REQUIRE(u_in_dev && u_out_dev && u_loop_dev && gamma_dev && beta_dev && z_dev && y_dev && save_mean_dev && save_rstd_dev &&
                    workspace_dev, "bn_tanh_train_fwd: null pointer");
   MGCN_REQUIRE(ldu >= dim_out && (running_mean_dev != nullptr) == (running_var_dev != nullptr), "bn_tanh_train_fwd: bad arguments");
@@ -220,6 +227,7 @@ extern "C" int mgcn_bn_tanh_train_bwd(int64_t num_rows, int32_t dim_out, const f
                                       float *gu_dev, float *ggamma_dev, float *gbeta_dev, float *workspace_dev,
                                       size_t workspace_bytes, void *stream) {
   MGCN_REQUIRE(num_rows > 0 && dim_out > 0, "bn_tanh_train_bwd: bad sizes");
+  MGCN_REQUIRE_ROWS_FIT("bn_tanh_train_bwd");
   MGCN_REQUIRE(z_dev && y_dev && gy_dev && save_mean_dev && save_rstd_dev && gamma_dev && gz_dev && gu_dev && ggamma_dev && gbeta_dev &&
                    workspace_dev, "bn_tanh_train_bwd: null pointer");
   MGCN_REQUIRE(workspace_bytes >= mgcn_bn_tanh_train_workspace(num_rows, dim_out), "bn_tanh_train_bwd: workspace too small");
@@ -267,6 +275,7 @@ extern "C" int mgcn_bn_train_stage_sum(int64_t num_rows, int32_t dim_out, const 
                                        const float *u_loop_dev, int64_t ldu, const float *bias_dev, float *z_dev, float *part_dev,
                                        void *stream) {
   MGCN_REQUIRE(num_rows >= 0 && dim_out > 0 && ldu >= dim_out, "bn_train_stage_sum: bad sizes");
+  MGCN_REQUIRE_ROWS_FIT("bn_train_stage_sum");
   if (num_rows == 0) return MGCN_OK;
   MGCN_REQUIRE(u_in_dev && u_out_dev && u_loop_dev && z_dev && part_dev, "bn_train_stage_sum: null pointer");
   const int nblk = int((num_rows + RB - 1) / RB);
@@ -280,6 +289,7 @@ extern "C" int mgcn_bn_train_stage_center(int64_t num_rows, int32_t dim_out, con
                                           int64_t num_blocks, int64_t total_rows, float *mean_dev, float *part_dev, void *stream) {
   MGCN_REQUIRE(num_rows >= 0 && dim_out > 0 && total_rows >= num_rows && total_rows > 0 && num_blocks > 0 && num_blocks < (int64_t(1) << 31),
                "bn_train_stage_center: bad sizes");
+  MGCN_REQUIRE_ROWS_FIT("bn_train_stage_center");
   MGCN_REQUIRE(sum_parts_dev && mean_dev && (num_rows == 0 || (z_dev && part_dev)), "bn_train_stage_center: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned cg = unsigned((dim_out + TPB - 1) / TPB);
@@ -299,6 +309,7 @@ extern "C" int mgcn_bn_train_stage_finish(int64_t num_rows, int32_t dim_out, con
                                           float eps, float *rstd_dev, float *y_dev, void *stream) {
   MGCN_REQUIRE(num_rows >= 0 && dim_out > 0 && total_rows >= num_rows && total_rows > 0 && num_blocks > 0 && num_blocks < (int64_t(1) << 31),
                "bn_train_stage_finish: bad sizes");
+  MGCN_REQUIRE_ROWS_FIT("bn_train_stage_finish");
   MGCN_REQUIRE(sq_parts_dev && mean_dev && gamma_dev && beta_dev && rstd_dev && (num_rows == 0 || (z_dev && y_dev)),
                "bn_train_stage_finish: null pointer");
   MGCN_REQUIRE((running_mean_dev != nullptr) == (running_var_dev != nullptr), "bn_train_stage_finish: bad arguments");
@@ -318,6 +329,7 @@ extern "C" int mgcn_bn_train_bwd_stage_sums(int64_t num_rows, int32_t dim_out, c
                                             const float *gy_dev, const float *save_mean_dev, const float *save_rstd_dev,
                                             float *g_part_dev, float *gx_part_dev, void *stream) {
   MGCN_REQUIRE(num_rows >= 0 && dim_out > 0, "bn_train_bwd_stage_sums: bad sizes");
+  MGCN_REQUIRE_ROWS_FIT("bn_train_bwd_stage_sums");
   if (num_rows == 0) return MGCN_OK;
   MGCN_REQUIRE(z_dev && y_dev && gy_dev && save_mean_dev && save_rstd_dev && g_part_dev && gx_part_dev,
                "bn_train_bwd_stage_sums: null pointer");
@@ -335,6 +347,7 @@ extern "C" int mgcn_bn_train_bwd_stage_apply(int64_t num_rows, int32_t dim_out, 
                                              float *gbeta_dev, void *stream) {
   MGCN_REQUIRE(num_rows >= 0 && dim_out > 0 && total_rows >= num_rows && total_rows > 0 && num_blocks > 0 && num_blocks < (int64_t(1) << 31),
                "bn_train_bwd_stage_apply: bad sizes");
+  MGCN_REQUIRE_ROWS_FIT("bn_train_bwd_stage_apply");
   MGCN_REQUIRE(save_mean_dev && save_rstd_dev && gamma_dev && g_parts_dev && gx_parts_dev && ggamma_dev && gbeta_dev &&
                    (num_rows == 0 || (z_dev && y_dev && gy_dev && gz_dev && gu_dev)),
                "bn_train_bwd_stage_apply: null pointer");
