@@ -16,6 +16,11 @@ header). Consequently:
 Nothing from /root/reference is copied into the repo: outputs are arrays (inputs + expected
 outputs) and the Toy data files (fixture data the reference ships: data/Toy/*.txt).
 
+run_trajectory adds tests/golden/traj_syn_a_A.npz / traj_syn_a_B.npz: eight steps of the reference's training loop
+(main.py:58-71 with the optimizer and scheduler calls of main.py:217-219) on syn_a in float64, and the worst distance of
+the reference's float32 rounding twins from that run, which is what the bars of tests/test_gpu_trajectory.py rest on
+(DESIGN §4.18). Their names do not have the form syn_a.<x>.npz, which tests/conftest.py would merge into the case syn_a.
+
 Usage:  python tests/golden/gen/make_golden.py        (rewrites tests/golden/*.npz, data/*)
 """
 import glob
@@ -280,6 +285,182 @@ def run_case(root, name, params_over, scale_tables=1.0, full_model=True, seed=20
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# multi-step training trajectories (tests/test_gpu_trajectory.py, tests/test_traj_ref_host.py)
+# ------------------------------------------------------------------------------------------------
+TRAJ_SIZES = (16, 16, 16, 16, 5, 16, 16, 16)   # step 5: 341 train queries mod 16, an epoch's short last batch
+TRAJ_LR_STEP = 4                               # StepLR(step_size=1, gamma=0.5).step() once, after this step
+TRAJ_EVALS = (4, 8)                            # eval-mode scores of the first TRAJ_EVAL_Q valid_tail queries after these steps
+TRAJ_EVAL_Q = 16
+TRAJ_MARGIN = 16.0                             # bar = TRAJ_MARGIN x twin_gap
+TRAJ_TWIN_PERMS = 4                            # x the thread counts below: float32 rounding twins per trajectory
+TRAJ_TWIN_THREADS = (1, 8)
+TRAJ = {
+    # max_norm: the first candidate that meets the trajectory's condition on the float64 coefficients is recorded
+    'A': dict(lr=0.01, weight_decay=0.01, max_norm=(0.25, 0.2, 0.1), snaps=(1, 4, 5, 8), coef='all_active', gap_cap=1e-3),
+    'B': dict(lr=0.001, weight_decay=0.0, max_norm=(1.0, 1.2, 1.1, 1.3, 1.5), snaps=(4, 8), coef='both', gap_cap=5e-3),
+}
+# B only: a training-mode BatchNorm follows these three parameters, so their gradient is mathematically zero; without weight
+# decay Adam turns its rounding noise into steps of about +-lr, and they drag the four tensors after them. Not held to a bar in B.
+TRAJ_EXEMPT_B = ('conv2.bn0.bias', 'conv2.conv_e.bias', 'conv2.fc.bias', 'conv2.bn0.weight', 'conv2.bn1.running_mean',
+                 'conv2.bn1.running_var', 'conv2.bn2.running_mean')
+
+
+def _traj_once(dl, params, pdict, sd0, cfg, max_norm, dtype, perm_seed=None, threads=None):
+    """One run of the reference's training loop (main.py:58-71 with the optimizer and scheduler calls of main.py:217-219) over
+    the fixed batches. perm_seed: permute each batch's rows (the same mathematics, other rounding)."""
+    if threads is not None:
+        torch.set_num_threads(threads)
+    model = ref_model.MGCN(dl.num_entity, dl.num_relation, dl.num_edge, params)
+    model.load_state_dict(sd0)
+    model.conv1.drop.p = 0.0
+    if dtype == torch.float64:
+        model.double()
+    graph = dl.graph
+    iters = dl.get_data_loaders(pdict['batch_size'], 0, params)
+    ds, ev = iters['train'].dataset, iters['valid_tail'].dataset
+    ev_items = [ev[i] for i in range(TRAJ_EVAL_Q)]
+    ev_trip, ev_lab = torch.stack([it[0] for it in ev_items]), torch.stack([it[1] for it in ev_items])
+    optimizer = torch.optim.Adam(model.parameters(), lr=cfg['lr'], weight_decay=cfg['weight_decay'])
+    scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=1, gamma=0.5, last_epoch=-1)
+    g = None if perm_seed is None else torch.Generator().manual_seed(perm_seed)
+    out = dict(q=[], loss=[], norm=[], snaps={}, evals={}, ev_trip=ev_trip, ev_lab=ev_lab, group=optimizer.param_groups[0])
+    model.train()
+    lo = 0
+    for step, nb in enumerate(TRAJ_SIZES, 1):
+        items = [ds[i] for i in range(lo, lo + nb)]
+        lo += nb
+        trip = torch.stack([it[0] for it in items])
+        lab = torch.stack([it[1] for it in items]).to(dtype)     # smoothed by the dataset's own __getitem__, in float32
+        out['q'].append(trip[:, :2].clone())
+        if g is not None:
+            perm = torch.randperm(nb, generator=g)
+            trip, lab = trip[perm], lab[perm]
+        optimizer.zero_grad()
+        pred = model(trip[:, 0], trip[:, 1], graph)
+        loss = model.loss(pred, lab)
+        loss.backward()
+        norm = torch.nn.utils.clip_grad_norm_(parameters=model.parameters(), max_norm=max_norm)
+        optimizer.step()
+        out['loss'].append(float(loss))
+        out['norm'].append(float(norm))
+        if step in cfg['snaps']:
+            out['snaps'][step] = {k: v.clone() for k, v in model.state_dict().items()}
+        if step == TRAJ_LR_STEP:
+            scheduler.step()
+            out['lr_after'] = float(optimizer.param_groups[0]['lr'])
+        if step in TRAJ_EVALS:
+            model.eval()
+            with torch.no_grad():
+                out['evals'][step] = model(ev_trip[:, 0], ev_trip[:, 1], graph).clone()
+            model.train()
+    if threads is not None:
+        torch.set_num_threads(_DEFAULT_THREADS)
+    return out
+
+
+_DEFAULT_THREADS = torch.get_num_threads()
+
+
+def _coefs(norms, max_norm):
+    return [min(max_norm / (n + 1e-6), 1.0) for n in norms]
+
+
+def run_trajectory(root, tag, sd0):
+    """tests/golden/traj_syn_a_<tag>.npz: 8 steps of the reference's training loop on syn_a in float64 from the committed sd_*
+    state, and the worst distance of its float32 rounding twins from that run (`gap_*`; bar_* = TRAJ_MARGIN x gap_*)."""
+    os.chdir(root)
+    cfg = TRAJ[tag]
+    over = dict(gcn_in_dim=12, gcn_out_dim=24, k_w=3, k_h=8, num_filter=6, kernel_size=3, bias=True,
+                gcn_drop=0.0, hidden_drop=0.0, feat_drop=0.0, lbl_smooth=0.1, batch_size=16)
+    params, pdict = make_params(**over)
+    dl = ref_dl.DataLoader('syn_a', params)
+    assert len(dl.triplets['train']) % 16 == TRAJ_SIZES[4] == 5
+    sd0 = {k: v.clone() for k, v in sd0.items()}
+    ref = max_norm = None
+    for max_norm in cfg['max_norm']:
+        ref = _traj_once(dl, params, pdict, sd0, cfg, max_norm, torch.float64)
+        coefs = _coefs(ref['norm'], max_norm)
+        ok = all(c < 1 for c in coefs) if cfg['coef'] == 'all_active' else (any(c < 1 for c in coefs) and any(c == 1 for c in coefs))
+        if ok:
+            break
+        print('traj %s: max_norm %g does not give the pattern %r: float64 norms %s' % (
+            tag, max_norm, cfg['coef'], ' '.join('%.4f' % n for n in ref['norm'])))
+    else:
+        raise AssertionError('trajectory %s: no max_norm candidate gives the coefficient pattern %r' % (tag, cfg['coef']))
+    names = [k for k in ref['snaps'][cfg['snaps'][0]] if not k.endswith('num_batches_tracked')]
+    gap_sd = np.zeros((len(names), len(cfg['snaps'])))
+    gap_loss, gap_norm = np.zeros(len(TRAJ_SIZES)), np.zeros(len(TRAJ_SIZES))
+    gap_eval = np.zeros(len(TRAJ_EVALS))
+    n_twins = 0
+    for threads in TRAJ_TWIN_THREADS:
+        for perm in range(TRAJ_TWIN_PERMS):
+            tw = _traj_once(dl, params, pdict, sd0, cfg, max_norm, torch.float32, perm_seed=1000 * threads + perm, threads=threads)
+            n_twins += 1
+            for j, s in enumerate(cfg['snaps']):
+                for i, k in enumerate(names):
+                    gap_sd[i, j] = max(gap_sd[i, j], float((tw['snaps'][s][k].double() - ref['snaps'][s][k]).abs().max()))
+                for k in ref['snaps'][s]:
+                    if k.endswith('num_batches_tracked'):
+                        assert int(tw['snaps'][s][k]) == int(ref['snaps'][s][k]) == s
+            gap_loss = np.maximum(gap_loss, np.abs(np.array(tw['loss']) - np.array(ref['loss'])))
+            gap_norm = np.maximum(gap_norm, np.abs(np.array(tw['norm']) - np.array(ref['norm'])))
+            for j, s in enumerate(TRAJ_EVALS):
+                gap_eval[j] = max(gap_eval[j], float((tw['evals'][s].double() - ref['evals'][s]).abs().max()))
+    assert n_twins >= 8
+    exempt = TRAJ_EXEMPT_B if tag == 'B' else ()
+    held = np.array([k not in exempt for k in names])
+    assert set(exempt) <= set(names)
+    # float64 against float64 with permuted rows: the twins' distances are float32 rounding, not the permutation itself
+    again = _traj_once(dl, params, pdict, sd0, cfg, max_norm, torch.float64, perm_seed=99)
+    f64_gap = max(float((again['snaps'][s][k] - ref['snaps'][s][k]).abs().max()) for s in cfg['snaps'] for k in names if k not in exempt)
+    assert f64_gap < 1e-12, f64_gap
+    worst = gap_sd[held].max()
+    assert worst < cfg['gap_cap'] * cfg['lr'], 'trajectory %s: a held tensor\'s twin_gap %.3g is not below %g lr' % (tag, worst, cfg['gap_cap'])
+    assert gap_sd[held].min() > 0 and gap_loss.min() > 0 and gap_norm.min() > 0 and gap_eval.min() > 0
+
+    out = dict(lr=cfg['lr'], weight_decay=cfg['weight_decay'], max_norm=max_norm, lr_after=ref['lr_after'], lbl_smooth=pdict['lbl_smooth'],
+               beta1=ref['group']['betas'][0], beta2=ref['group']['betas'][1], eps=ref['group']['eps'], margin=TRAJ_MARGIN,
+               lr_step=TRAJ_LR_STEP, snaps=np.array(cfg['snaps']), eval_steps=np.array(TRAJ_EVALS), twins=n_twins,
+               loss=np.array(ref['loss']), norm=np.array(ref['norm']), coef=np.array(_coefs(ref['norm'], max_norm)),
+               names=np.array(names), exempt=np.array(exempt, dtype='U64'), gap_sd=gap_sd, gap_loss=gap_loss, gap_norm=gap_norm,
+               gap_eval=gap_eval, bar_sd=TRAJ_MARGIN * gap_sd, bar_loss=TRAJ_MARGIN * gap_loss, bar_norm=TRAJ_MARGIN * gap_norm,
+               bar_eval=TRAJ_MARGIN * gap_eval, eval_triple=ref['ev_trip'], eval_label=ref['ev_lab'].to(torch.uint8))
+    for i, q in enumerate(ref['q'], 1):
+        out['q_%d' % i] = q
+    for s in cfg['snaps']:
+        for k, v in ref['snaps'][s].items():
+            out['sd%d_%s' % (s, k)] = v.to(torch.int64) if k.endswith('num_batches_tracked') else v.double()
+    for j, s in enumerate(TRAJ_EVALS):
+        pred = ref['evals'][s]
+        det = rank_details(pred.clone(), ref['ev_lab'], ref['ev_trip'][:, 2])
+        assert int(det['ties'].sum()) == 0
+        b = torch.arange(pred.size(0))
+        masked = torch.where(ref['ev_lab'].bool(), torch.full_like(pred, -1e7), pred)
+        diff = (masked - det['target'][:, None]).abs()
+        diff[b, ref['ev_trip'][:, 2]] = float('inf')
+        decide = diff.min(1).values                     # the smallest score difference that decides the filtered rank
+        undecided = int((decide <= 2 * TRAJ_MARGIN * gap_eval[j]).sum())
+        print('  eval after step %d: score gap %.3g, deciding differences %s' % (s, gap_eval[j], ' '.join('%.2g' % d for d in sorted(decide.tolist()))))
+        # B's eval-mode scores read the exempt running statistics, on which the reference's own float32 twins differ by about lr:
+        # their spread leaves no rank decided there, so the condition is the generator's in A only and B records the count
+        assert undecided <= 1 or tag == 'B', 'trajectory %s, eval after step %d: %d of %d ranks are closer than twice the score bar' % (
+            tag, s, undecided, pred.size(0))
+        out['eval%d_undecided' % s] = undecided
+        out['eval%d_score' % s] = pred.double()
+        out['eval%d_rank' % s] = 1 + det['gt']
+        out['eval%d_decide' % s] = decide
+    arrays = npify(out)
+    assert sum(a.nbytes for a in arrays.values()) < PART_BYTES
+    np.savez_compressed(os.path.join(GOLDEN, 'traj_syn_a_%s.npz' % tag), **arrays)
+    print('traj %s max_norm=%g coef=%s' % (tag, max_norm, ' '.join('%.3f' % c for c in out['coef'])))
+    print('  worst held twin_gap / lr = %.3g, loss gap %.3g, norm gap %.3g, eval gap %s' % (
+        worst / cfg['lr'], gap_loss.max(), gap_norm.max(), gap_eval))
+    for i, k in enumerate(names):
+        print('  %-28s %s%s' % (k, ' '.join('%.3g' % (x / cfg['lr']) for x in gap_sd[i]), '  (exempt)' if k in exempt else ''))
+    return out
+
+
 PART_BYTES = 1000000      # raw array bytes per fixture file: every committed file stays under 1 MiB
 
 
@@ -332,13 +513,15 @@ def main():
         shutil.move(os.path.join(GOLDEN, 'Toy.npz'), os.path.join(GOLDEN, 'toy_small.npz'))
         run_case(root, 'Toy', dict(batch_size=4), full_model=False)
         shutil.move(os.path.join(GOLDEN, 'Toy.npz'), os.path.join(GOLDEN, 'toy_d100.npz'))
-        run_case(root, 'syn_a', dict(gcn_in_dim=12, gcn_out_dim=24, k_w=3, k_h=8, num_filter=6, kernel_size=3, bias=True),
-                 scale_tables=5.0)
+        syn_a = run_case(root, 'syn_a', dict(gcn_in_dim=12, gcn_out_dim=24, k_w=3, k_h=8, num_filter=6, kernel_size=3, bias=True),
+                         scale_tables=5.0)
         run_case(root, 'syn_b', dict(gcn_in_dim=20, gcn_out_dim=40, k_w=5, k_h=8, num_filter=8, kernel_size=3),
                  scale_tables=5.0)
         run_case(root, 'syn_c', dict(), full_model=False)
         for name in ('toy_small', 'toy_d100', 'syn_a', 'syn_b', 'syn_c'):
             split_into_parts(name)
+        for tag in sorted(TRAJ):
+            run_trajectory(root, tag, {k[3:]: v for k, v in syn_a.items() if k.startswith('sd_')})
 
         # untrained Toy, seed 2020, default dims, reference evaluate('test')
         os.chdir(root)
