@@ -324,8 +324,8 @@ class CapturedCandidateStep(CapturedTrainStep):
     captured draw (mgcn_cand_draw_dev) reads a second device word, dropout_step_key(draw_seed, draw_step), which the wrapper
     writes next to the dropout step word and the Adam pairs in the same pinned image: a replay still costs ONE host-to-device copy
     of scalars. `num_neg`, `loss` and `run_split` (forward_loss_candidates', None or an int in [16, 65536]) are plain attributes
-    held by value in the graph: changing one re-captures. `cand` is the
-    [B, 1 + num_neg] block of the last call (after a replay: the graph's static tensor, overwritten by the next replay).
+    held by value in the graph: changing one re-captures. `cand` and `labels` are the
+    [B, 1 + num_neg] int64 / uint8 blocks of the last call (after a replay: the graph's static tensors, overwritten by the next replay).
 
     Raises NativeError, before anything is captured, for what the parent refuses (but the scoring stage takes any batch >= 1),
     for num_neg < 0, a loss other than 'bce' / 'softmax', a run_split that forward_loss_candidates refuses and an index that is not
@@ -338,7 +338,7 @@ class CapturedCandidateStep(CapturedTrainStep):
         super().__init__(model, graph, index, optimizer, lbl_smooth=lbl_smooth, clip=clip, warmup=warmup)
         self.num_neg, self.draw_seed, self.draw_step, self.loss = num_neg, int(draw_seed), int(draw_step), loss
         self.sampler, self.run_split = sampler, run_split
-        self.cand = None
+        self.cand = self.labels = None
 
     def _body(self, src, rel):
         from .harness import draw_candidates
@@ -354,7 +354,7 @@ class CapturedCandidateStep(CapturedTrainStep):
                                          run_split=self.run_split)
         loss.backward()
         opt.clip_and_step(self.clip)
-        self.cand = cand
+        self.cand, self.labels = cand, labels
         return loss.detach()
 
     def _refuse(self, src):
@@ -406,11 +406,11 @@ class CapturedCandidateStep(CapturedTrainStep):
         finally:
             self.draw_step = saved
         if hit is not None:
-            hit.cand = self.cand                       # the graph's static list block
+            hit.cand, hit.labels = self.cand, self.labels      # the graph's static list and label blocks
         return hit
 
     def _replay(self, hit, src, rel):
         loss = super()._replay(hit, src, rel)          # (its _upload staged the word of draw_step)
         self.draw_step += 1
-        self.cand = hit.cand
+        self.cand, self.labels = hit.cand, hit.labels
         return loss
