@@ -253,15 +253,12 @@ int mgcn_dense_bn_tanh_fwd(int64_t num_nodes, int32_t dim_in, int32_t dim_out, c
  *       48-80, stages of 128 input columns (256 through `tune` only), a ring of f32 staging buffers coupled by LDS counters,
  *       13 or 32 column tiles.
  *       Generations 2 and 3 run the same arithmetic (k order, products, and for dim_out > 128 the weight packing): rows
- *       are bit-identical between them;
- *   generation 4, dim_in <= 256 and dim_out <= 208, ONLY through `tune`  csrc/layer_fused4.hip (round 4's experiment: all
- *       sixteen waves gather a stage of up to 320 columns of the concatenated K axis, then all sixteen multiply it; own
- *       packing, own k order: rows differ from generations 2 / 3 in the last bits; not faster, see LAB_NOTES.md).
+ *       are bit-identical between them.
  * Arguments as in (2) and (4), except that the weights are passed in MFMA fragment order: wp_dev = mgcn_pack_weights() of
  * the stacked [3*dim_in, dim_out] matrix (mgcn_packed_weights_bytes bytes, 16-byte aligned; re-pack whenever a weight
  * changes; the *_gen forms pack for a generation forced through `tune`; 0 = the shape's own, which generations 2 and 3 share for
- * dim_out > 128). Returns MGCN_EUNSUPPORTED (and does nothing) unless all operands are 16-byte aligned, ee_dev is given in
- * slot order, dim_in % 4 == 0, dim_in <= 1024, dim_out % 4 == 0 and dim_out <= 512 — callers then use (2) followed by (4).
+ * dim_out > 128; for any other `generation` than 0, 2 or 3 the size is 0 and packing returns MGCN_EINVAL). Returns
+ * MGCN_EUNSUPPORTED (and does nothing) unless all operands are 16-byte aligned, ee_dev is given in slot order, dim_in % 4 == 0, dim_in <= 1024, dim_out % 4 == 0 and dim_out <= 512 — callers then use (2) followed by (4).
  * NUMERIC CONTRACT. The dense step is not the exact-f32 MFMA of (4): every aggregate a and weight w is split EXACTLY
  * into three bf16 pieces (hi = bf16(v) rounded to nearest, mid = bf16(v - hi), lo = v - hi - mid; hi + mid + lo == v bit
  * for bit) and the six products hi.hi, hi.mid, mid.hi, hi.lo, lo.hi, mid.mid are accumulated in f32; the dropped terms
@@ -293,10 +290,10 @@ int mgcn_dense_bn_tanh_fwd(int64_t num_nodes, int32_t dim_in, int32_t dim_out, c
  * two tiles per CU takes generation 3 (dim_out > 128); generation 2 itself ignores them. The bounds are read by the launch, not
  * checked: offsets outside the range are the caller's error.
  * tune: 0 = automatic. For A/B runs only (never needed for correctness): bits 0-3 row tiles per tile (3..5); bits 4-7
- * generation 3: staging buffers (1..4), generation 4: slots per gather batch (2 / 4 / 8); bits 8-9 relation table in LDS
- * (1 = never); bits 10-11 force a generation (1 = generation 4, 2, 3; wp_dev must then come from mgcn_pack_weights_gen for
- * it); bits 12-13 generation 3: input columns per slot walk (0 or 1 = 128, 2 = 256), generation 4: phase groups of its
- * stagger (1 = none, 0 or 2 = two, 3 = four); bit 14 generations 2 and 3: the legacy column cut (below).
+ * generation 3: staging buffers (1..4); bits 8-9 relation table in LDS (1 = never); bits 10-11 force a generation (2 or 3;
+ * wp_dev must then come from mgcn_pack_weights_gen for it; 1 is reserved — it forced the removed generation 4 — and is refused
+ * with MGCN_EINVAL before anything is launched); bits 12-13 generation 3: input columns per slot walk (0 or 1 = 128, 2 = 256);
+ * bit 14 generations 2 and 3: the legacy column cut (below).
  * Column cut. Generations 2 and 3 (128-column walk) gather a mode's dim_in columns in chunks of at most 128, one slot walk per
  * chunk, every chunk starting on a k-block (32 columns). Rows of the layer input lie 4 * dim_in bytes apart, so the 128-byte
  * lines a chunk touches depend on where it starts. For 128 < dim_in <= 256 the boundary is the multiple of 32 columns (neither
@@ -310,13 +307,13 @@ int mgcn_dense_bn_tanh_fwd(int64_t num_nodes, int32_t dim_in, int32_t dim_out, c
  * status_dev (optional, one zero-initialised uint32 in device memory): generation 3 couples its roles through LDS counters
  * with BOUNDED spins; a spin that runs out (a wave parked for ~0.1 s by a debugger, a preemption, or a protocol error)
  * lets its wave go on, the rows of that tile are then garbage, and bit 0 of *status_dev is set: callers check the word at
- * their next synchronisation point (kgc-gcn_amd/_native.py check_fused_status). Generations 2 and 4 have no spins.
+ * their next synchronisation point (kgc-gcn_amd/_native.py check_fused_status). Generation 2 has no spins.
  * Live view. mgcn_layer_fwd_fused_live is the same launch with the main slot walk of generations 2 and 3 on the live view
  * of (1v): live_rowptr_dev / live_rec_dev take the place of rowptr_dev / rec_dev for the partition, the record chunks and
  * the runs, and a slot's per-edge row is its record's fourth word - ee_sub_{region}; rec_dev stays the CANONICAL record
  * array, which the hub pre-pass reads through chunks_dev as before (dead hub slots are still walked there). Same
- * dispatcher, same generation choice, same row bounds, ranges and shards (the row word is an absolute slot index);
- * generation 4 forced through `tune` is refused. CONTRACT: for finite inputs the rows are bit-identical to the
+ * dispatcher, same generation choice, same row bounds, ranges and shards (the row word is an absolute slot index).
+ * CONTRACT: for finite inputs the rows are bit-identical to the
  * canonical launch's (s + m * 0 == s, and a run of dead slots only is +0 either way). A non-finite value in an x row or
  * per-edge row that ONLY dead slots read no longer reaches the output: the canonical launch (and the reference) give
  * NaN for that destination, this launch gives the row of the finite terms. */
@@ -369,7 +366,7 @@ size_t mgcn_packed_weights_bytes_gen(int32_t generation, int32_t dim_in, int32_t
  * per element instead of 4, then a shift. Alignment: the vector paths want ee_dev 8-byte aligned (D % 4 == 0 makes every row
  * so); mgcn_aggregate_fwd_ee16 takes a table that is only 2-byte aligned on its element-wise path (as the f32 launch takes a
  * misaligned operand), the fused launches return MGCN_EUNSUPPORTED. Generations 2 and 3 read the bf16 table, on the
- * canonical layout and on the live view; generation 4 forced through `tune` returns MGCN_EUNSUPPORTED. The hub pre-pass
+ * canonical layout and on the live view. The hub pre-pass
  * reads the same table. There is no backward: (3) and (3s) take f32 tables only (a bf16 table is a deployment form of a
  * trained model). */
 int mgcn_aggregate_fwd_ee16(int64_t num_nodes, int64_t num_edges_half, int32_t dim, int32_t num_rel_rows,

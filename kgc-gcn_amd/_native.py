@@ -427,8 +427,8 @@ def dense_bn_tanh_fwd(a, w_cat, bias, bn_mean, bn_var, bn_gamma, bn_beta, eps, o
 
 
 # `tune` argument of mgcn_layer_fwd_fused (include/mgcn_hip.h): 0 = automatic. Read ONCE at import, for A/B tools only (see
-# INTEGRATION.md "Environment switches"): bits 0-3 row tiles per tile, 4-7 staging buffers / slots per batch, 8-9 relation
-# table in LDS, 10-11 a forced kernel generation (1 = 4, 2, 3), 12-13 columns per slot walk, 14 the legacy column cut.
+# INTEGRATION.md "Environment switches"): bits 0-3 row tiles per tile, 4-7 staging buffers, 8-9 relation
+# table in LDS, 10-11 a forced kernel generation (2 or 3; 1 is reserved), 12-13 columns per slot walk, 14 the legacy column cut.
 FUSED_TUNE = int(os.environ.get('MGCN_FUSED_TUNE', '0'), 0)
 # `tune` bit 14: the legacy column cut of the fused layer kernels (128-column chunks, idle lanes on the row's head) instead of
 # the one that follows the row stride (include/mgcn_hip.h (2b)); same rows either way. MGCN_FUSED_CUT=legacy, read ONCE at
@@ -448,9 +448,12 @@ def fused_cut(dim_in, legacy=False):
 
 
 def tune_generation(tune=None):
-    """Kernel generation a `tune` word forces (0 = the shape's own)."""
-    f = ((FUSED_TUNE if tune is None else int(tune)) >> 10) & 3
-    return 0 if f == 0 else (4 if f == 1 else f)
+    """Kernel generation a `tune` word forces: 2, 3, or 0 = the shape's own. Raises for the reserved field value 1."""
+    tune = FUSED_TUNE if tune is None else int(tune)
+    f = (tune >> 10) & 3
+    if f == 1:
+        raise NativeError('tune %#x: bits 10-11 = 1 is reserved (mgcn_layer_fwd_fused refuses it)' % tune)
+    return f
 
 
 _FUSED_STATUS = {}
@@ -495,12 +498,15 @@ def fused_supported(d_in, d_out):
 
 def pack_weights(w_cat, out=None, generation=None):
     """Stacked [3D, O] weights -> MFMA fragment order for layer_fwd_fused (re-pack whenever a weight changes).
-    `generation`: the kernel generation to pack for (None = what MGCN_FUSED_TUNE forces, else the shape's own)."""
+    `generation`: the kernel generation to pack for: 2, 3, or 0 = the shape's own (None = what MGCN_FUSED_TUNE forces, else the
+    shape's own); any other value raises NativeError."""
     D, O = w_cat.size(0) // 3, w_cat.size(1)
     if w_cat.dim() != 2 or w_cat.size(0) != 3 * D or not w_cat.is_contiguous():
         raise NativeError('pack_weights: w_cat must be contiguous (3D, O)')
     gen = tune_generation() if generation is None else int(generation)
     nbytes = lib().mgcn_packed_weights_bytes_gen(gen, D, O)
+    if nbytes == 0:
+        raise NativeError('pack_weights: there is no kernel generation %d (0, 2 or 3)' % gen)
     if out is None:
         out = torch.empty(nbytes // 4, dtype=torch.float32, device=w_cat.device)
     if out.numel() * 4 < nbytes:
@@ -559,13 +565,12 @@ def layer_fwd_fused(csr, x, rel, loop_rel, ee, ee_in_slot_order, loop_edge, w_pa
     from n0, strictly increasing from 0 to n1 - n0, at most 4096 runs, one workgroup each. No run may be longer than the cap the
     launch sizes its tiles by, from per = ceil(rows / runs): per rounded up to whole 16-row tiles while per <= 80, to whole 80-row
     tiles past that (the rule of GraphCSR.workgroup_bounds); anything else raises NativeError before a launch (the check reads
-    the tensor back: it synchronises). Read by generations 3 and 4 (bounds make a lockstep shape with O > 128 and fewer than two
+    the tensor back: it synchronises). Read by generation 3 (bounds make a lockstep shape with O > 128 and fewer than two
     tiles per CU take generation 3); generation 2 tiles the range itself. Results do not depend on the runs.
     `live`: walk the graph's live view (GraphCSR.live_rowptr / live_rec: zero-norm slots left out; bit-identical rows for
     finite inputs). None = whenever the graph has one and MGCN_LIVE_SLOTS is not 0; False = the canonical launch; True raises
     where there is no view to walk.
-    A bf16 `ee` takes the _ee16 entry points (generations 2 and 3): the rows of the f32 launch on ee.float(), bit for bit; a
-    forced generation 4 raises FusedUnsupported."""
+    A bf16 `ee` takes the _ee16 entry points (generations 2 and 3): the rows of the f32 launch on ee.float(), bit for bit."""
     N, E, D, O = csr.num_nodes, csr.num_edges_half, x.size(1), int(d_out)
     n0, n1 = (0, N) if node_range is None else (int(node_range[0]), int(node_range[1]))
     if not 0 <= n0 <= n1 <= N:
@@ -609,9 +614,9 @@ def layer_fwd_fused(csr, x, rel, loop_rel, ee, ee_in_slot_order, loop_edge, w_pa
     if row_bounds is not None:
         bounds = row_bounds
     # the graph's live view (zero-norm slots left out) whenever it has one: same rows for finite inputs, fewer row loads
-    has_view = getattr(csr, 'live_rowptr', None) is not None and tune_generation(tune) != 4
+    has_view = getattr(csr, 'live_rowptr', None) is not None
     if live and not has_view:
-        raise NativeError('layer_fwd_fused: live=True, but this graph has no live view (no dead slot) or tune forces generation 4')
+        raise NativeError('layer_fwd_fused: live=True, but this graph has no live view (no dead slot)')
     live = has_view and (LIVE_SLOTS if live is None else bool(live))
     ee16 = is_ee16(ee)
     if live:

@@ -1,4 +1,4 @@
-// What the fused layer kernels (layer_fused2.hip, layer_fused3.hip, layer_fused4.hip) have in common, ONE copy each: the kernel
+// What the fused layer kernels (layer_fused2.hip, layer_fused3.hip) have in common, ONE copy each: the kernel
 // arguments every generation reads, the exact bf16 split, the epilogue's arithmetic, the relation projection, the gather groups'
 // row bookkeeping and the weight packing. The project's promises rest on these being the same code: generations 2 and 3 give
 // bit-identical rows, every generation gives the relation projection the bits of the separate launch. Internal linkage throughout
@@ -27,7 +27,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// The leading kernel arguments of every generation (Args2 / Args3 / Args4 extend this: the offsets are part of no ABI, but the
+// The leading kernel arguments of every generation (Args2 / Args3 extend this: the offsets are part of no ABI, but the
 // order is kept so that the kernels' argument loads do not move)
 struct LayerArgs {
   const int32_t *rowptr;
@@ -186,7 +186,7 @@ __device__ __forceinline__ void epilogue_table_entry(const LayerArgs &p, float b
   epi[op + c] = in ? ((p.bias ? p.bias[c] : 0.f) - p.bn_mean[c]) * inv + p.bn_beta[c] : 0.f;
 }
 // The relation table [rel_rows - 1][D] into LDS (when it fits: a third of the gather's row loads), by waves 0 .. nwaves - 1
-// (generations 2 and 3: their MFMA waves; generation 4 copies it with all its threads beside its other one-time set-up)
+// (the kernel's MFMA waves)
 __device__ __forceinline__ void copy_rel_table(const LayerArgs &p, float *rel_lds, int wave, int lane, int nwaves) {
   const int n4 = ((p.rel_rows - 1) * p.d) >> 2;
   for (int i = wave * 64 + lane; i < n4; i += nwaves * 64)
@@ -215,7 +215,7 @@ __device__ __forceinline__ RowPtrs rp_load(const int32_t *rp, int row0, int h, i
 // bid of nblk.
 // One item = one relation row x 16 columns per wave: the four 16-lane groups run the four K quarters of small_matmul_kernel's
 // arithmetic (sequential fmaf chains), the partial sums are added in quarter order — values bit-identical to the separate
-// launch, one load round trip per 32 k. (Generation 4 carries the same text in its kernel, see there.)
+// launch, one load round trip per 32 k.
 __device__ __forceinline__ void rel_projection(const LayerArgs &p, int wave, int wave0, int nwaves, int lane, int bid, int nblk) {
   const int rows = p.rel_rows - 1, k = p.d, n = p.o;
   const int ncg = (n + 15) / 16, items = rows * ncg;

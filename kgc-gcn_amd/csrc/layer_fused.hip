@@ -1,6 +1,6 @@
 // Fused layer forward (eval) — C-ABI entry points: mgcn_pack_weights / mgcn_packed_weights_bytes /
 // mgcn_layer_fwd_fused (include/mgcn_hip.h (2)+(4)); replaces model.py:29-30, 99-107, 111-118 in one launch.
-// The kernels are layer_fused2.hip (D <= 256, O <= 208), layer_fused3.hip (the rest) and, through `tune` only, layer_fused4.hip.
+// The kernels are layer_fused2.hip (D <= 256, O <= 208) and layer_fused3.hip (the rest).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -9,31 +9,28 @@
 
 
 namespace {
-// Three kernels behind one entry point.
+// Two kernels behind one entry point.
 //   generation 2  layer_fused2.hip  D <= 256, O <= 208: gather / multiply roles in lockstep, one workgroup barrier per stage (every
 //                 workgroup walks the packed weights in step, which keeps them L2-resident while the step's alternating layers
 //                 stream 330 MB through the caches): the benchmark's layers;
 //   generation 3  layer_fused3.hip  the rest (D <= 1024, O <= 512), and generation 2's shapes when the caller brings work-balanced
 //                 runs for a launch that is short of two tiles per CU (FB15k-237): roles coupled by LDS counters. Generations 2
 //                 and 3 share the k order, the six products and (O > 128) the weight packing: their rows are bit-identical
-//                 (tests/test_gpu_round4.py holds them to it at the benchmark's sizes);
-//   generation 4  layer_fused4.hip  D <= 256, O <= 208, round 4's structural experiment (no role split: sixteen waves gather, then
-//                 sixteen multiply; K folded): correct, NOT faster (LAB_NOTES.md) — reachable through `tune` only, own packing.
+//                 (tests/test_gpu_round4.py holds them to it at the benchmark's sizes).
 bool lockstep_shape(int32_t dim_in, int32_t dim_out) { return dim_in <= 256 && mgcn::fused2_takes(dim_in, dim_out); }
 int pack_generation(int32_t dim_in, int32_t dim_out) { return lockstep_shape(dim_in, dim_out) ? 2 : 3; }
 bool generation_takes(int gen, int32_t dim_in, int32_t dim_out) {
-  if (gen == 4) return mgcn::fused4_takes(dim_in, dim_out);
   if (gen == 2) return lockstep_shape(dim_in, dim_out);
   return gen == 3 && mgcn::fused3_takes(dim_in, dim_out);
 }
 }  // namespace
 
-// generation: 0 = the shape's own; 2 / 3 / 4
+// generation: 0 = the shape's own; 2 / 3; any other value: 0 bytes
 extern "C" size_t mgcn_packed_weights_bytes_gen(int32_t generation, int32_t dim_in, int32_t dim_out) {
   const int gen = generation ? generation : pack_generation(dim_in, dim_out);
-  if (gen == 4) return mgcn::fused4_packed_bytes(dim_in, dim_out);
   if (gen == 2) return mgcn::fused2_packed_bytes(dim_in, dim_out);
-  return mgcn::fused3_packed_bytes(dim_in, dim_out);
+  if (gen == 3) return mgcn::fused3_packed_bytes(dim_in, dim_out);
+  return 0;
 }
 
 extern "C" size_t mgcn_packed_weights_bytes(int32_t dim_in, int32_t dim_out) {
@@ -44,11 +41,10 @@ extern "C" int mgcn_pack_weights_gen(int32_t generation, int32_t dim_in, int32_t
                                      size_t wp_bytes, void *stream) {
   MGCN_REQUIRE(dim_in > 0 && dim_out > 0 && w_dev && wp_dev, "pack_weights: bad arguments");
   const int gen = generation ? generation : pack_generation(dim_in, dim_out);
-  MGCN_REQUIRE(gen >= 2 && gen <= 4 && generation_takes(gen, dim_in, dim_out),
+  MGCN_REQUIRE(generation_takes(gen, dim_in, dim_out),
                "pack_weights: generation %d does not take D=%d O=%d", gen, dim_in, dim_out);
   MGCN_REQUIRE(wp_bytes >= mgcn_packed_weights_bytes_gen(gen, dim_in, dim_out) && mgcn::aligned16(wp_dev),
                "pack_weights: packed buffer too small or misaligned");
-  if (gen == 4) return mgcn::fused4_pack(dim_in, dim_out, w_dev, wp_dev, stream);
   if (gen == 2) return mgcn::fused2_pack(dim_in, dim_out, w_dev, wp_dev, stream);
   return mgcn::fused3_pack(dim_in, dim_out, w_dev, wp_dev, stream);
 }
@@ -125,15 +121,10 @@ int layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, i
   const bool want_rel = rel_out_dev != nullptr && num_rel_rows > 1;
   MGCN_REQUIRE(!want_rel || (rels_weight_dev && rel_dev), "layer_fwd_fused: the relation projection needs rels_weight and rel");
   if (node_end == node_begin && !want_rel) return MGCN_OK;
-  if (num_chunks > 0 && node_end > node_begin) {
-    if (int rc = mgcn::launch_hub_partials(num_nodes, dim_in, num_rel_rows, rec_dev, x_dev, ldx, rel_dev, loop_rel_dev,
-                                           ee_dev, ee_in_slot_order, ee_sub_hub, chunks_dev, chunk_begin, chunk_end,
-                                           partial_dev, stream, ee16))
-      return rc;
-  }
-  // tune bits 10-11: 0 = the launch's own kernel; 1 / 2 / 3 force generation 4 / 2 / 3 (A/B runs; wp_dev must be packed for it:
-  // mgcn_pack_weights_gen; generations 2 and 3 share one packing for O > 128)
-  const int forced = ((tune >> 10) & 3) == 1 ? 4 : ((tune >> 10) & 3);
+  // tune bits 10-11: 0 = the launch's own kernel; 2 / 3 force that generation (A/B runs; wp_dev must be packed for it:
+  // mgcn_pack_weights_gen; generations 2 and 3 share one packing for O > 128); 1 is reserved. Checked before anything is launched.
+  const int forced = (tune >> 10) & 3;
+  MGCN_REQUIRE(forced != 1, "layer_fwd_fused: tune %d: bits 10-11 = 1 is reserved (it forced the removed generation 4)", tune);
   const int gen = forced == 0 ? mgcn_fused_kernel_generation(dim_in, dim_out, node_end - node_begin, num_row_bounds > 0) : forced;
   MGCN_REQUIRE(forced != 3 || !lockstep_shape(dim_in, dim_out) || dim_out > 128,
                "layer_fwd_fused: tune %d: generation 3 reads another packing than generation 2 for O <= 128", tune);
@@ -141,17 +132,19 @@ int layer_fwd_fused(int64_t num_nodes, int64_t num_edges_half, int32_t dim_in, i
                dim_in, dim_out);
   MGCN_REQUIRE(num_row_bounds >= 0 && num_row_bounds <= 4096 && (num_row_bounds == 0 || row_bounds_dev),
                "layer_fwd_fused: bad row bounds");
-  if (ee16 && gen == 4)
-    return mgcn::fail(MGCN_EUNSUPPORTED, "layer_fwd_fused: tune %d: generation 4 does not read a bf16 per-edge table", tune);
+  if (num_chunks > 0 && node_end > node_begin) {
+    if (int rc = mgcn::launch_hub_partials(num_nodes, dim_in, num_rel_rows, rec_dev, x_dev, ldx, rel_dev, loop_rel_dev,
+                                           ee_dev, ee_in_slot_order, ee_sub_hub, chunks_dev, chunk_begin, chunk_end,
+                                           partial_dev, stream, ee16))
+      return rc;
+  }
   const bool live = live_rowptr_dev != nullptr;
-  MGCN_REQUIRE(!live || gen != 4, "layer_fwd_fused: tune %d: generation 4 does not walk a live view", tune);
   const mgcn::FusedLaunch a = {num_nodes, dim_in, dim_out, num_rel_rows, live ? live_rowptr_dev : rowptr_dev,
                                live ? live_rec_dev : rec_dev, x_dev, ldx, rel_dev, loop_rel_dev, ee_dev,
                                loop_edge_dev, wp_dev, bias_dev, bn_mean_dev, bn_var_dev, bn_gamma_dev, bn_beta_dev, bn_eps, out_dev, ldo,
                                node_begin, node_end, ee_sub_in, ee_sub_out, num_chunks > 0 ? hubinfo_dev : nullptr, chunk_begin,
                                partial_dev, want_rel ? rels_weight_dev : nullptr, want_rel ? rel_out_dev : nullptr, row_bounds_dev,
                                num_row_bounds, tune, status_dev, stream, live, ee16};
-  if (gen == 4) return mgcn::fused4_launch(a);
   if (gen == 2) return mgcn::fused2_launch(a);
   return mgcn::fused3_launch(a);
 }

@@ -58,7 +58,7 @@ struct FusedLaunch {
   const float *partial;
   const float *rels_weight;    // null, with rel_out, when the launch does not project the relations
   float *rel_out;
-  const int32_t *row_bounds;   // generations 3 and 4
+  const int32_t *row_bounds;   // generation 3
   int32_t num_row_bounds;
   int32_t tune;
   uint32_t *status;            // generation 3
@@ -80,13 +80,6 @@ bool fused3_takes(int32_t dim_in, int32_t dim_out);
 size_t fused3_packed_bytes(int32_t dim_in, int32_t dim_out);
 int fused3_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_dev, void *stream);
 int fused3_launch(const FusedLaunch &a);
-
-// fused layer, phase-alternating generation (layer_fused4.hip): D <= 256, O <= 208; all sixteen waves gather a stage of up to 320
-// columns of the concatenated K axis into one LDS image, then all sixteen multiply it
-bool fused4_takes(int32_t dim_in, int32_t dim_out);
-size_t fused4_packed_bytes(int32_t dim_in, int32_t dim_out);
-int fused4_pack(int32_t dim_in, int32_t dim_out, const float *w_dev, void *wp_dev, void *stream);
-int fused4_launch(const FusedLaunch &a);
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }

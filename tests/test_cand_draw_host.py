@@ -134,7 +134,7 @@ def test_exports_and_header(pkg):
     assert '(15) Counter-drawn candidate lists' in header
     assert lib.mgcn_abi_version() == 4 and pkg._native.ABI_VERSION == 4
     import __graft_entry__ as entry
-    assert 'dropout.hip' in entry.SOURCES and len(entry.SOURCES) == 15
+    assert 'dropout.hip' in entry.SOURCES and len(entry.SOURCES) == 14
 
 
 def test_argument_validation_without_a_gpu(pkg):

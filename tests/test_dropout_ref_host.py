@@ -103,7 +103,7 @@ def test_exports_and_header(pkg):
         assert n in pkg._native.EXPORTS and n + '(' in header
     assert pkg._native.lib().mgcn_abi_version() == 4
     import __graft_entry__ as entry
-    assert 'dropout.hip' in entry.SOURCES and len(entry.SOURCES) == 15
+    assert 'dropout.hip' in entry.SOURCES and len(entry.SOURCES) == 14
 
 
 def test_argument_validation_without_a_gpu(pkg):

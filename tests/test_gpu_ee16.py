@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 N, R = 300, 3
 B33, B129 = 100, 200                # the two hub destinations
-GEN4 = 0x400                        # `tune` bits 10-11 = 1: force generation 4
+GEN4 = 0x400                        # `tune` bits 10-11 = 1: the reserved value
 
 _cache = {}
 
@@ -326,11 +326,13 @@ def test_refusals(pkg, monkeypatch):
         nat.aggregate_bwd(csr, lay.x, rel_full, lay.t16, g)
     with pytest.raises(nat.NativeError, match='inference-only'):
         nat.aggregate_bwd_shard(csr, lay.x, rel_full, csr.edge_table_shard(lay.t16, 0, 64), g[:64], (0, 64))
-    # a forced generation 4 (its own packing) does not read a bf16 table; it still takes the f32 one
-    wp4 = nat.pack_weights(lay.conv.derived_weights()[0], generation=4)
-    with pytest.raises(nat.FusedUnsupported):
-        lay.launch(lay.t16, tune=GEN4, wpack=wp4)
-    assert torch.isfinite(lay.launch(lay.t32, tune=GEN4, wpack=wp4)).all()
+    # the reserved `tune` value is refused for either table, and nothing packs for the generation it once forced
+    with pytest.raises(nat.NativeError):
+        nat.pack_weights(lay.conv.derived_weights()[0], generation=4)
+    with pytest.raises(nat.NativeError):
+        lay.launch(lay.t32, tune=GEN4)
+    with pytest.raises(nat.NativeError):
+        lay.launch(lay.t16, tune=GEN4)
     assert torch.equal(lay.launch(lay.t16), lay.launch(lay.t32))           # the refused launch left the hub buffers usable
     graph, E = _model_graph(pkg)
     m16 = _model(pkg, E, 0, edge_table_dtype='bf16').to(DEV)

@@ -621,7 +621,7 @@ def test_fused_kernel_generation_rule(pkg):
     """mgcn_fused_kernel_generation (no device work): wide shapes take the elastic kernel (generation 3); a lockstep shape
     takes it too when the caller brings work-balanced runs, its lockstep tiling has fewer than two tiles per CU and O > 128
     (FB15k-237: 182 tiles of 80 rows), and stays on the lockstep kernel (generation 2) otherwise (WN18RR: 512 tiles).
-    Generation 4 (round 4's experiment) is never dispatched: `tune` only. Packing sizes per generation."""
+    Packing sizes per generation; a generation that does not exist has none (0 bytes)."""
     gen = pkg._native.lib().mgcn_fused_kernel_generation
     assert gen(100, 200, 40943, 1) == 2 and gen(200, 200, 40943, 0) == 2
     assert gen(100, 200, 14541, 1) == 3 and gen(100, 200, 14541, 0) == 2
@@ -629,7 +629,7 @@ def test_fused_kernel_generation_rule(pkg):
     assert gen(512, 512, 250000, 0) == 3 and gen(512, 200, 250000, 1) == 3 and gen(200, 256, 40943, 0) == 3
     nb = pkg._native.lib().mgcn_packed_weights_bytes_gen
     assert nb(0, 100, 200) == nb(2, 100, 200) == nb(3, 100, 200) == 12 * 13 * 3 * 64 * 16    # generations 2 and 3: one packing
-    assert nb(4, 100, 200) == 10 * 13 * 3 * 64 * 16 and nb(4, 200, 200) == 19 * 13 * 3 * 64 * 16   # K = 3 D padded ONCE
+    assert nb(4, 100, 200) == 0 == nb(5, 100, 200) == nb(1, 100, 200)
     assert nb(0, 512, 512) == nb(3, 512, 512)
 
 
