@@ -1182,6 +1182,61 @@ int mgcn_edge_drop_records_host(int64_t num_nodes, int64_t num_edges_half, const
 int mgcn_edge_flags_from_queries(int32_t batch, const int64_t *qkey_dev, int64_t num_edges_half, const int64_t *ekeys_dev,
                                  const int32_t *eund_dev, uint8_t *forced_dev, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (20) Softmax cross-entropy over the full entity table (csrc/dense.hip) — additive, MGCN_ABI_VERSION stays 4.
+ * The listwise loss of (16) with "list position" replaced by "entity": the 1-vs-all softmax next to the BCE of (6). Every entity
+ * is live. The forward is logits -> merge over tiles (mgcn_cand_ce_merge of (16), unchanged) -> finish; the backward is (6)'s three
+ * products on the g this block leaves. No [B, N] label block, ONE [n_local, batch] block (z, overwritten by g), no float atomics,
+ * every sum has a fixed order: the same inputs give the same bits. No host read.
+ *
+ * The loss. For query b and entity n of the GLOBAL table of N = num_entities entities: z[b, n] = x[b,:] . ent[n,:] + bias[n].
+ * Per row b over ALL shards: M = max z, S = sum exp(z - M), n_pos = the number of set mask bits (the known tails of the query).
+ *   q[b, n] = (1 - eps) y[b, n] / n_pos + eps / N      (eps = lbl_smooth; y = the mask bit; the smoothing mass is eps / N over
+ *             the table, not (6)'s + 1 / N; eps / N is formed once on the host as float(eps) / float(N))
+ *   lp = (z - M) - log S,  p = exp(lp),  g = (p - q) inv_batch,  the element's term is -(q lp);
+ *   loss = inv_batch * the sum of all terms (inv_batch = 1 / B for the mean over queries).
+ * A row with n_pos == 0 has g = 0 everywhere and no term; it still counts in the divisor B: the convention of (14) and (16).
+ * With the GLOBAL statistics of a row in every shard's finish the shards' losses add up to the loss, the shards' g blocks are
+ * disjoint, d ent / d bias are local and complete, d x is a sum of partial sums.
+ *
+ * A STATISTIC is (16)'s record (m, s, n_live, n_pos). z, like (6)'s grad_logit, is entity-major: element (n, b) at z[n * ldz + b].
+ * mgcn_score_ce_tiles(n_local) = ceil(n_local / 32): the row tiles of a launch. mgcn_score_ce_partials(batch, n_local) =
+ *   ceil(n_local / 32) * ceil(batch / 64): the length of loss_partial of mgcn_score_ce_finish.
+ * mgcn_score_ce_logits: ONE launch of (6)'s tile kernel with another epilogue: same operands, same acceptance rule (16-byte
+ *   aligned x / ent / z, ldx, lde, ldz, dim and batch multiples of 4, else MGCN_EUNSUPPORTED), ALWAYS the exact-f32 family,
+ *   never the six-product split. z[n * ldz + b] has the bits of the logit mgcn_score_bce_fwd feeds its sigmoid, which are the
+ *   bits of (16)'s z for the list that names entity n. Record t * lds + b of stat_dev (lds >= batch, in records; stat_dev 16-byte
+ *   aligned, ceil(n_local / 32) * lds records) is the statistic of (row tile t of 32 entities, query b): m = the maximum of the
+ *   tile's rows below n_local, s = the sum from 0 of exp(z - m) over those rows in row order (one thread per query: no lane or
+ *   wave order enters), n_live = their number, n_pos = the popcount of the query's mask word t below n_live. A record is a
+ *   function of its own tile and query and of nothing else in the launch. mgcn_cand_ce_merge(batch, parts = tiles, in = stat_dev,
+ *   row_stride = 1, part_stride = lds) folds them tile by tile into the rows' [batch] records with coalesced reads; the same
+ *   entry point folds the all-gathered [W, batch] blocks of the ranks (a rank without rows passes the empty statistic on).
+ *   That fold is one thread per query walking every tile: with many tiles fold in two levels through the same strides (as
+ *   _native.score_ce_fold does beyond 64 tiles): with G groups of P tiles, lds = batch and the records past `tiles` preset to the
+ *   empty statistic, mgcn_cand_ce_merge(batch * G, parts = P, row_stride = 1, part_stride = G * batch) folds tiles g, g + G, ...
+ *   into record g * batch + b, and mgcn_cand_ce_merge(batch, parts = G, row_stride = 1, part_stride = batch) folds the groups.
+ * mgcn_score_ce_finish: element-wise and IN PLACE over z [n_local, batch], any batch and alignment, every access guarded: from z,
+ *   the mask, the rows' GLOBAL statistics stat_dev [batch] (of which m, s and n_pos are read), lbl_smooth, inv_batch and
+ *   num_entities it overwrites z with g and writes loss_partial[t * ceil(batch / 64) + qg] = the sum of the terms of (row tile t,
+ *   queries 64 qg .. 64 qg + 63): a lane adds its query's eight rows in row order from 0, the 64 lanes fold by xor tree, the four
+ *   waves follow in wave order. The loss is inv_batch times the sum of the partials.
+ * All checks precede the first launch; a refusal writes nothing. MGCN_EINVAL: a null pointer, a negative size, dim < 1, batch /
+ * n_local at or above 2^31 - 64, ldx / lde < dim, ldz / lds < batch, ldm < ceil(n_local / 32), lds at or above 2^40, a stat_dev of
+ * mgcn_score_ce_logits that is not 16-byte aligned, lbl_smooth outside [0, 1], num_entities < max(n_local, 1). batch == 0 or
+ * n_local == 0 return MGCN_OK without a launch and write nothing.
+ * Domain: finite logits. NOT MEASURED: the kernels' own times (DESIGN §4.19 and profiles/bench_table_ce.json have the stage's time
+ * around device events, Python's enqueueing included).
+ */
+int64_t mgcn_score_ce_tiles(int64_t n_local);
+int64_t mgcn_score_ce_partials(int32_t batch, int64_t n_local);
+int mgcn_score_ce_logits(int32_t batch, int64_t n_local, int32_t dim, const float *x_dev, int64_t ldx, const float *ent_dev,
+                         int64_t lde, const float *bias_dev, const uint32_t *mask_dev, int64_t ldm, float *z_dev, int64_t ldz,
+                         float *stat_dev, int64_t lds, void *stream);
+int mgcn_score_ce_finish(int32_t batch, int64_t n_local, float *z_dev, int64_t ldz, const uint32_t *mask_dev, int64_t ldm,
+                         const float *stat_dev, float lbl_smooth, float inv_batch, int64_t num_entities, float *loss_partial_dev,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1520,6 +1520,101 @@ def score_bce_fwd(x, ent, bias, mask, hot, cold, num_entities=None):
     return parts.sum() * inv, g
 
 
+# ------------------------------------------------------------------------------------------------
+# (20) Softmax cross-entropy over the full entity table: (16)'s loss with every entity a live position. Statistics are (16)'s
+# records; z and g are entity-major [n, B] like score_bce_fwd's G.
+def _table_mask(mask, B, n, what):
+    if mask.dim() != 2 or mask.size(0) != B or mask.size(1) < (n + 31) // 32 or not mask.is_contiguous():
+        raise NativeError('%s: mask must be contiguous (%d, >= %d)' % (what, B, (n + 31) // 32))
+
+
+def score_ce_supported(x, ent):
+    """Whether mgcn_score_ce_logits takes the batch: score_bce_fwd's rule."""
+    return score_bce_supported(x, ent)
+
+
+def score_ce_fold_shape(n):
+    """(tiles, G, P) of a table of n rows: its tiles of 32 entities fold in one level (G = 1, P = tiles) up to 64 tiles, beyond in
+    two: G = ceil(sqrt(tiles)) groups of P = ceil(tiles / G) tiles, group g holding the tiles g, g + G, g + 2 G, ... A function
+    of n alone, so the order of every sum is fixed."""
+    tiles = (int(n) + 31) // 32
+    G = 1 if tiles <= 64 else math.isqrt(tiles - 1) + 1
+    return tiles, G, (tiles + G - 1) // G if tiles else 0
+
+
+def score_ce_logits(x, ent, bias, mask):
+    """(20) One launch: (z [n, B] f32 entity-major, stat [G P, B, 4]): the logits ent[n] . x[b] + bias[n] and per (tile of 32
+    entities, query) the statistic (max, sum of exp(z - max), rows of the tile, set mask bits of the tile); (tiles, G, P) =
+    score_ce_fold_shape(n), the records past `tiles` hold the empty statistic. Fold the tiles with score_ce_fold(stat, n). See
+    mgcn_score_ce_logits; raises for a batch score_ce_supported refuses."""
+    B, n, O = _score_args(x, ent, bias)
+    _table_mask(mask, B, n, 'score_ce_logits')
+    _same_device(x, ent, bias, mask)
+    tiles, G, P = score_ce_fold_shape(n)
+    z = torch.empty((n, B), dtype=torch.float32, device=x.device)
+    stat = torch.empty((G * P, B, 4), dtype=torch.float32, device=x.device)
+    if G * P > tiles:
+        stat[tiles:] = cand_ce_empty_stat(1, x.device)
+    if B and n:
+        _check(lib().mgcn_score_ce_logits(B, n, O, _dev(x, torch.float32, 'x'), _ld(x), _dev(ent, torch.float32, 'ent'), _ld(ent),
+                                          _dev(bias, torch.float32, 'bias'), _dev(mask, torch.int32, 'mask'), mask.size(1),
+                                          _dev(z, torch.float32, 'z'), B, _dev(stat, torch.float32, 'stat'), B, _stream(x)),
+               'mgcn_score_ce_logits')
+    return z, stat
+
+
+def score_ce_fold(stat, n):
+    """(20) [B, 4]: the rows' statistics from the tile records stat [G P, B, 4] of score_ce_logits for a table of n rows, by
+    mgcn_cand_ce_merge through its strides. Up to 64 tiles: ONE sequential fold in tile order. Beyond, one thread per query
+    walking every tile would be the stage's longest launch (62 500 dependent steps at n = 2 000 000), so two folds: (group g,
+    query b) folds its tiles g, g + G, ... in that order (B G rows, P parts, part_stride = G B records), then query b folds its
+    G groups in group order. Empty records are skipped by the merge."""
+    tiles, G, P = score_ce_fold_shape(n)
+    if stat.dim() != 3 or stat.size(0) != G * P or stat.size(2) != 4 or not stat.is_contiguous():
+        raise NativeError('score_ce_fold: stat %s must be contiguous (%d, B, 4) for %d rows' % (tuple(stat.shape), G * P, n))
+    B = stat.size(1)
+    if G <= 1:
+        return cand_ce_merge(stat, part_dim=0)
+    return cand_ce_merge(cand_ce_merge(stat.view(P, G * B, 4), part_dim=0).view(G, B, 4), part_dim=0)
+
+
+def score_ce_finish(z, mask, stat, lbl_smooth, num_entities, inv_batch=None):
+    """(20) One launch, IN PLACE: z [n, B] (contiguous f32, the logits) becomes g = d loss / d logit; returns (loss [] f32, g = z,
+    loss_partial). stat [B, 4]: the rows' statistics over the WHOLE table (merged over tiles and, sharded, over ranks);
+    num_entities: the global entity count the smoothing mass lbl_smooth is spread over; inv_batch: the weight of a query, default
+    1 / B. Any batch and alignment. See mgcn_score_ce_finish."""
+    if z.dim() != 2 or z.dtype != torch.float32 or not z.is_contiguous():
+        raise NativeError('score_ce_finish: z must be contiguous f32 [n, B]')
+    n, B = z.shape
+    _table_mask(mask, B, n, 'score_ce_finish')
+    _same_device(z, mask, stat)
+    if tuple(stat.shape) != (B, 4) or stat.dtype != torch.float32 or not stat.is_contiguous():
+        raise NativeError('score_ce_finish: stat %s must be contiguous f32 (%d, 4)' % (tuple(stat.shape), B))
+    inv = (1.0 / float(B) if B else 0.0) if inv_batch is None else float(inv_batch)
+    parts = torch.empty(int(lib().mgcn_score_ce_partials(B, n)), dtype=torch.float32, device=z.device)
+    if B and n:
+        _check(lib().mgcn_score_ce_finish(B, n, _dev(z, torch.float32, 'z'), B, _dev(mask, torch.int32, 'mask'), mask.size(1),
+                                          _dev(stat, torch.float32, 'stat'), float(lbl_smooth), inv, int(num_entities),
+                                          _dev(parts, torch.float32, 'loss_partial'), _stream(z)), 'mgcn_score_ce_finish')
+    return parts.sum() * inv, z, parts
+
+
+def mask_popcount(mask, n=None):
+    """[B] int32: the set bits of each row of a bit-packed mask [B, words] int32 (integer ops on the device, no host read). `n`:
+    only the bits of entities below n count, as in the EPI_CE epilogue (mgcn_filter_mask sets none past them; this does not rely
+    on it)."""
+    v = mask.to(torch.int64) & 0xffffffff
+    if n is not None:
+        words = (int(n) + 31) // 32
+        v = v[:, :words]
+        if int(n) % 32:
+            v = torch.cat([v[:, :-1], v[:, -1:] & ((1 << (int(n) % 32)) - 1)], 1)
+    v = v - ((v >> 1) & 0x55555555)
+    v = (v & 0x33333333) + ((v >> 2) & 0x33333333)
+    v = (v + (v >> 4)) & 0x0f0f0f0f
+    return (((v * 0x01010101) >> 24) & 0xff).sum(1).to(torch.int32)
+
+
 def label_rows(qkey, keys, ptr, tails, n_local, lbl_smooth=0.0, num_entities=None, ent_row0=0, out=None):
     """Dense training targets [B, n_local] f32 for queries with keys `qkey` (see mgcn_label_rows): 1 at the known
     tails, 0 elsewhere, then (1 - eps) * y + 1/N when eps != 0 (data_loader.py:41-43, evaluated in f32 as numpy does)."""

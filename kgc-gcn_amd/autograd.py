@@ -275,6 +275,54 @@ class _ScoreBCEFn(torch.autograd.Function):
                 g.sum(1) * gl if ctx.needs_input_grad[2] else None, None, None, None, None)
 
 
+class _ScoreCEFn(torch.autograd.Function):
+    """softmax cross-entropy over the full entity table (include/mgcn_hip.h (20)): _CandCEFn's loss with every entity a list
+    position. One launch of the tile kernel leaves the logits z [n, B] and a statistic per (tile of 32 entities, query); the
+    tiles are merged per row by the kernel that merges the list chunks (_native.score_ce_fold: in two levels beyond 64 tiles); the finish overwrites z with d loss / d logit. The
+    backward is _ScoreBCEFn's, on that g. No [B, N] labels, one [n, B] block, no float atomics. `eps` is spread over the
+    `num_entities` entities of the GLOBAL table (default: the rows of `ent`).
+    `ex`: `ent` / `bias` / `mask` are this rank's entity rows. With an exchange of more than one rank the [B, 4] row statistics
+    make ONE all-gather (ex.gather_stats) and are merged over the ranks in rank order; the finish takes the global statistics.
+    The rank's loss is the sum of its own entities' terms, so the ranks' losses and d x add up to the one-rank step's; d ent and
+    d bias are the rank's rows, complete. A rank without rows passes the empty statistic on and joins the all-gather.
+    A batch the logits launch refuses (B % 4 != 0, a misaligned x) forms z on the matmul kernel and the [B, 4] record with
+    torch ops on the device (the counts through an int32 view) and goes through the same exchange, merge and finish; this second
+    form holds a second [n, B] block while it forms the statistic (the launch path holds one).
+    The incoming scalar gradient is handled as in _ScoreBCEFn."""
+
+    @staticmethod
+    def forward(ctx, x, ent, bias, mask, eps, num_entities=None, ex=None):
+        B, n = x.size(0), ent.size(0)
+        total = n if num_entities is None else int(num_entities)
+        if n == 0 or B == 0:
+            z = torch.empty((n, B), dtype=torch.float32, device=x.device)
+            stat = _native.cand_ce_empty_stat(B, x.device)
+        elif _native.score_ce_supported(x, ent):
+            z, stat = _native.score_ce_logits(x, ent, bias, mask)
+            stat = _native.score_ce_fold(stat, n)
+        else:
+            x, ent = x.contiguous(), ent.contiguous()
+            z = _native.matmul(ent, x.t().contiguous()).add_(bias.view(-1, 1))
+            m = z.max(0).values
+            stat = torch.empty((B, 4), dtype=torch.float32, device=x.device)
+            stat[:, 0], stat[:, 1] = m, z.sub(m).exp_().sum(0)      # (one [n, B] temporary next to z, freed before the finish)
+            counts = stat.view(torch.int32)
+            counts[:, 2], counts[:, 3] = n, _native.mask_popcount(mask, n)
+        if ex is not None and ex.world > 1:
+            stat = _native.cand_ce_merge(ex.gather_stats(stat), part_dim=0)
+        loss, g, _ = _native.score_ce_finish(z, mask, stat, eps, max(total, 1))
+        ctx.save_for_backward(x, ent, g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        x, ent, g = ctx.saved_tensors
+        if ent.size(0) == 0 or x.size(0) == 0:          # a rank without rows: nothing to multiply
+            return (torch.zeros_like(x) if ctx.needs_input_grad[0] else None, torch.zeros_like(ent) if ctx.needs_input_grad[1] else None,
+                    g.new_zeros(ent.size(0)) if ctx.needs_input_grad[2] else None, None, None, None, None)
+        return _ScoreBCEFn.backward(ctx, gl)
+
+
 def _save_plan(ctx, x, ent, cand, g, row0, run_split):
     """What the list backward of _CandBCEFn / _CandCEFn needs, saved on ctx: the plan of the rank's rows, and with a run_split
     its sorted keys too. No host read of the live count: the whole plan is handed over, its dead tail is skipped entry by entry."""

@@ -46,7 +46,7 @@ _RING = 8      # pinned staging slots: the host may run this many replays ahead 
 
 
 class CapturedTrainStep(object):
-    """step = CapturedTrainStep(model, graph, index, optimizer, lbl_smooth=0.0, clip=None, warmup=2); loss = step(src, rel).
+    """step = CapturedTrainStep(model, graph, index, optimizer, lbl_smooth=0.0, clip=None, warmup=2, loss='bce'); loss = step(src, rel).
 
     `loss` is a 0-dim device tensor; no call waits for the device, and the next call overwrites it (clone it to keep it). The
     first `warmup` (>= 1) calls are ordinary eager steps on the real batches (they create the optimizer state whose addresses
@@ -55,7 +55,7 @@ class CapturedTrainStep(object):
     when something the captured launches hold by value or by address changed: the graph's CSR, the address of a parameter, a
     buffer, an optimizer state tensor or an index tensor, the set of parameters that take a gradient, a dispatch switch or
     its environment variable, a dropout probability, a BatchNorm momentum or eps, betas / eps / weight_decay of a group,
-    `lbl_smooth` or `clip` (both plain attributes). optimizer.load_state_dict replaces the state tensors and so re-captures;
+    `lbl_smooth`, `clip` or `loss` (MGCN.forward_loss's 'bce' / 'softmax'; all plain attributes). optimizer.load_state_dict replaces the state tensors and so re-captures;
     model.load_state_dict copies in place and does not.
 
     Raises NativeError, before anything is captured, for: a model on the CPU, in eval mode (the step is a training step: call
@@ -67,8 +67,9 @@ class CapturedTrainStep(object):
     parameters, buffers and optimizer state tensors, the switches): O(number of parameters), no device work, no wait. It is part
     of every wall time tools/bench_train_captured.py reports."""
 
-    def __init__(self, model, graph, index, optimizer, lbl_smooth=0.0, clip=None, warmup=2):
+    def __init__(self, model, graph, index, optimizer, lbl_smooth=0.0, clip=None, warmup=2, loss='bce'):
         self.model, self.graph, self.index, self.optimizer = model, graph, index, optimizer
+        self.loss = loss
         self.lbl_smooth, self.clip, self.warmup = float(lbl_smooth), clip, max(1, int(warmup))
         self.captures = self.replays = self.eager_steps = 0
         self.disabled = False
@@ -80,7 +81,8 @@ class CapturedTrainStep(object):
     def _body(self, src, rel):
         opt = self.optimizer
         opt.zero_grad(set_to_none=True)
-        loss = self.model.forward_loss(src, rel, self.graph, self.index, lbl_smooth=self.lbl_smooth)
+        extra = {} if self.loss == 'bce' else {'loss': self.loss}           # the default is the call as it was
+        loss = self.model.forward_loss(src, rel, self.graph, self.index, lbl_smooth=self.lbl_smooth, **extra)
         loss.backward()
         opt.clip_and_step(self.clip)
         return loss.detach()
@@ -102,6 +104,8 @@ class CapturedTrainStep(object):
     def _refuse(self, src):
         """The reasons not to capture at all: raised (NativeError) before anything is captured."""
         m, opt = self.model, self.optimizer
+        if self.loss not in ('bce', 'softmax'):
+            raise _native.NativeError("%s: loss must be 'bce' or 'softmax', got %r" % (type(self).__name__, self.loss))
         if _native.is_ee16(m.edge_embeddings):
             raise _native.NativeError('CapturedTrainStep: this model holds its per-edge tables in bf16 (params.edge_table_dtype), '
                                       'which is inference-only')
@@ -147,7 +151,7 @@ class CapturedTrainStep(object):
         # runs no Python of the step, so it happens here, in place, ahead of the replay
         csr, ent_identity, edge_identity = m._layout_for(g)
         key = [id(csr), ent_identity, edge_identity, g.edge_index.data_ptr(), g.edge_attr.data_ptr(), ix.keys.data_ptr(), ix.ptr.data_ptr(), ix.tails.data_ptr(),
-               ix.num_rel_ids, self.lbl_smooth, self.clip, self._dropout_ps(), int(getattr(m.params, 'gcn_layers', 1))]
+               ix.num_rel_ids, self.lbl_smooth, self.clip, self.loss, self._dropout_ps(), int(getattr(m.params, 'gcn_layers', 1))]
         key += [os.environ.get(name) for name in _ENV_SWITCHES] + [getattr(m.params, name, None) for name in _PARAM_SWITCHES]
         key += [(p.data_ptr(), p.requires_grad) for p in m.parameters()] + [b.data_ptr() for b in m.buffers()]
         key += [(bn.momentum, bn.eps) for bn in m.modules() if isinstance(bn, torch.nn.modules.batchnorm._BatchNorm)]

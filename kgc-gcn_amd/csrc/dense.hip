@@ -6,6 +6,7 @@
 //   EPI_TARGET    target[b]   = score[b, obj[b]]  (same tile arithmetic, gathered rows, diagonal)
 //   EPI_RANK      filtered counts gt / ties_lower / ties per query, scores never stored (main.py:122-126)
 //   EPI_BCE       training: BCE(sigmoid(score), target) partial sums + d loss / d logit [M, ncols] (main.py:61-66, N3)
+//   EPI_CE        training: the logits [M, ncols] and one softmax statistic per (row tile, query) (include/mgcn_hip.h (20))
 // and, for aligned scoring shapes with K <= 352, score_split_kernel<SIGMOID / TARGET / RANK>: the same three results on
 // the bf16 MFMA from exactly split operands (below); and cand_split_kernel / cand_tile_kernel: score[b, cand[b, j]] for per-query
 // candidate lists, the same two arithmetics over gathered rows (include/mgcn_hip.h (13)); cand_bce_kernel and
@@ -31,7 +32,7 @@
 
 namespace {
 
-enum { EPI_NONE = 0, EPI_BN_TANH = 1, EPI_SIGMOID = 2, EPI_TARGET = 3, EPI_RANK = 4, EPI_BCE = 5 };
+enum { EPI_NONE = 0, EPI_BN_TANH = 1, EPI_SIGMOID = 2, EPI_TARGET = 3, EPI_RANK = 4, EPI_BCE = 5, EPI_CE = 6 };
 
 
 struct TileArgs {
@@ -52,6 +53,8 @@ struct TileArgs {
   int32_t k, ncols, tiles_m;
   int32_t a_vec, b_vec;  // 16-byte loads allowed (alignment + leading dimension checked on the host)
   float bn_eps;
+  float *stat;           // CE: [tiles_m, ldstat] records of four words (appended: the fields above keep their offsets)
+  int64_t ldstat;
 };
 
 constexpr int WAVES = 4, BM = 32, KS = 16, THREADS = 64 * WAVES;
@@ -264,6 +267,7 @@ __global__ __launch_bounds__(THREADS, min_waves(EPI, NT)) void tile_kernel(TileA
   // target makes hipcc drain vmcnt before every ds_read (cdna_hip_programming.md, M = 256 GEMM item 4a).
   __shared__ __attribute__((aligned(16))) float Bs[2 * SLAB_F + (EPI == EPI_RANK ? BNC * 3 : (EPI == EPI_BCE ? 4 : 0))];
   static_assert(2 * KS == BM, "the output staging tile [BM][LDB] reuses the two slab buffers");
+  static_assert(EPI != EPI_CE || (FAST && B_NT && BM == 32), "EPI_CE: aligned scoring shapes only, a row tile is one mask word");
   unsigned int *cnt = reinterpret_cast<unsigned int *>(Bs + 2 * SLAB_F);
 
   const int tid = threadIdx.x;
@@ -360,7 +364,7 @@ __global__ __launch_bounds__(THREADS, min_waves(EPI, NT)) void tile_kernel(TileA
     // Row-major outputs (NONE, BN_TANH) are staged through the (now idle) slab buffers so that every lane
     // stores 16 contiguous bytes of one output row: a dword-per-lane store of the accumulator layout touches
     // 64-byte pieces of four rows per instruction and made the store tail the longest phase of the kernel.
-    constexpr bool STAGED = FAST && (EPI == EPI_NONE || EPI == EPI_BN_TANH || EPI == EPI_BCE);
+    constexpr bool STAGED = FAST && (EPI == EPI_NONE || EPI == EPI_BN_TANH || EPI == EPI_BCE || EPI == EPI_CE);
     float *os = Bs;  // [BM][LDB]; 2*KS*LDB == BM*LDB floats
 #pragma unroll
     for (int t = 0; t < NTW; ++t) {
@@ -386,6 +390,7 @@ __global__ __launch_bounds__(THREADS, min_waves(EPI, NT)) void tile_kernel(TileA
         const int64_t row = r0 + lrow;
         if (row >= p.m) continue;
         const float v = acc[t][j];
+        if constexpr (EPI == EPI_CE) os[lrow * LDB + lcol] = v + p.bias[row];   // the logit EPI_BCE feeds its sigmoid
         if (EPI == EPI_NONE) {
           if (STAGED) os[lrow * LDB + lcol] = v; else p.c[row * p.ldc + col] = v;
         } else if (EPI == EPI_BN_TANH) {
@@ -429,6 +434,22 @@ __global__ __launch_bounds__(THREADS, min_waves(EPI, NT)) void tile_kernel(TileA
     }
     if (STAGED) {
       __syncthreads();
+      if constexpr (EPI == EPI_CE) {
+        // The tile's statistic of each query: one thread per column walks the staged tile's live rows in row order, the
+        // maximum first, then s = sum exp(z - m) from 0: a function of this (row tile, query) alone. The tile is mask word tm.
+        const int ncl = (p.ncols - c0) < BNC ? (p.ncols - c0) : BNC;
+        const int nlive = (p.m - r0) < BM ? int(p.m - r0) : BM;
+        for (int lc = tid; lc < ncl; lc += THREADS) {
+          float m = os[lc];
+          for (int r = 1; r < nlive; ++r) m = fmaxf(m, os[r * LDB + lc]);
+          float s = 0.f;
+          for (int r = 0; r < nlive; ++r) s = s + expf(os[r * LDB + lc] - m);
+          uint32_t w = p.mask[int64_t(c0 + lc) * p.ldl + tm];
+          if (nlive < 32) w &= (1u << nlive) - 1u;
+          *reinterpret_cast<float4 *>(p.stat + 4 * (int64_t(tm) * p.ldstat + c0 + lc)) =
+              make_float4(m, s, __int_as_float(nlive), __int_as_float(__popc(w)));
+        }
+      }
       const int c4n = (((p.ncols - c0) < BNC ? (p.ncols - c0) : BNC) + 3) / 4;  // float4 pieces per row (ncols % 4 == 0)
       const bool vec_out = (p.ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.c) & 15u) == 0);
       for (int s4 = tid; s4 < BM * c4n; s4 += THREADS) {
@@ -1643,5 +1664,135 @@ extern "C" int mgcn_cand_ce_finish(int32_t batch, int64_t n_cand, int64_t n_loca
   const unsigned gx = unsigned(groups < (int64_t(1) << 22) ? groups : (int64_t(1) << 22));   // beyond: grid-stride
   hipLaunchKernelGGL(cand_ce_finish_kernel, dim3(gx), dim3(CD_THREADS), 0, static_cast<hipStream_t>(stream), a);
   MGCN_CHECK_LAUNCH("cand_ce_finish_kernel");
+  return MGCN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Softmax cross-entropy over the full entity table (include/mgcn_hip.h (20)): (16)'s loss with "list position" replaced by
+// "entity". mgcn_score_ce_logits is tile_kernel<EPI_CE>, mgcn_score_bce_fwd's launch with another epilogue; the tiles' records
+// are folded by cand_ce_merge_kernel; score_ce_finish_kernel below turns z [n_local, batch] into g in place.
+namespace {
+
+constexpr int SF_Q = 64, SF_ROWS = BM / WAVES;   // a unit = (row tile of BM entities, 64 queries); a wave takes 8 rows of it
+
+struct ScoreCeFinishArgs {
+  float *z;              // [n_local, ldz] in: logits, out: g
+  const uint32_t *mask;  // [batch, ldm]
+  const float *stat;     // [batch] records: the rows' GLOBAL statistics
+  float *loss_partial;   // [tiles_m * qgroups]
+  int64_t ldz, ldm, n_local, units;
+  int32_t batch, qgroups;
+  float eps, inv_batch, smooth;   // smooth = eps / N, formed once on the host in f32
+};
+
+// Lane l of every wave owns query qg * 64 + l, wave w the rows 8 w .. 8 w + 7 of the tile: a wave instruction touches 256
+// contiguous bytes of one entity row. A lane adds its eight terms in row order from 0, the lanes fold by xor tree, the four waves
+// follow in wave order: the unit's partial is a function of its tile, its queries and their statistics alone. Every access is a
+// guarded scalar one: any batch, any alignment.
+__global__ __launch_bounds__(THREADS) void score_ce_finish_kernel(ScoreCeFinishArgs a) {
+  __shared__ float wsum[WAVES];
+  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  for (int64_t u = blockIdx.x; u < a.units; u += gridDim.x) {
+    const int64_t tm = u / a.qgroups;
+    const int b = int(u - tm * a.qgroups) * SF_Q + lane;
+    float term = 0.f;
+    if (b < a.batch) {
+      const float *st = a.stat + 4 * int64_t(b);
+      const float m = st[0], ls = logf(st[1]);
+      const int np = reinterpret_cast<const int *>(st)[3];
+      const uint32_t w = a.mask[int64_t(b) * a.ldm + tm];
+      const float hot = np > 0 ? (1.0f - a.eps) / float(np) + a.smooth : 0.f;
+#pragma unroll
+      for (int i = 0; i < SF_ROWS; ++i) {
+        const int lrow = wave * SF_ROWS + i;
+        const int64_t row = tm * BM + lrow;
+        if (row < a.n_local) {
+          float *zp = a.z + row * a.ldz + b;
+          float gz = 0.f;
+          if (np > 0) {
+            const float lp = (*zp - m) - ls;
+            const float pz = expf(lp);
+            const float q = ((w >> lrow) & 1u) ? hot : a.smooth;
+            gz = (pz - q) * a.inv_batch;
+            term = term + (-(q * lp));
+          }
+          *zp = gz;
+        }
+      }
+    }
+    float v = term;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+    __syncthreads();   // the previous unit's reader is done with wsum
+    if (lane == 0) wsum[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) a.loss_partial[u] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t mgcn_score_ce_tiles(int64_t n_local) { return n_local <= 0 ? 0 : (n_local + BM - 1) / BM; }
+
+extern "C" int64_t mgcn_score_ce_partials(int32_t batch, int64_t n_local) {
+  if (batch <= 0 || n_local <= 0) return 0;
+  return ((n_local + BM - 1) / BM) * ((int64_t(batch) + SF_Q - 1) / SF_Q);
+}
+
+extern "C" int mgcn_score_ce_logits(int32_t batch, int64_t n_local, int32_t dim, const float *x_dev, int64_t ldx,
+                                    const float *ent_dev, int64_t lde, const float *bias_dev, const uint32_t *mask_dev,
+                                    int64_t ldm, float *z_dev, int64_t ldz, float *stat_dev, int64_t lds, void *stream) {
+  if (int rc = check_common("score_ce_logits", n_local, dim, batch)) return rc;
+  MGCN_REQUIRE(x_dev && ent_dev && bias_dev && mask_dev && z_dev && stat_dev, "score_ce_logits: null pointer");
+  MGCN_REQUIRE(ldx >= dim && lde >= dim && ldz >= batch && lds >= batch && ldm >= (n_local + 31) / 32,
+               "score_ce_logits: leading dimension too small");
+  MGCN_REQUIRE(lds < (int64_t(1) << 40), "score_ce_logits: stride too large");
+  MGCN_REQUIRE(mgcn::aligned16(stat_dev), "score_ce_logits: stat_dev must be 16-byte aligned");
+  if (batch == 0 || n_local == 0) return MGCN_OK;
+  TileArgs p = {};
+  p.a = ent_dev; p.lda = lde;
+  p.b = x_dev; p.ldb = ldx;
+  p.c = z_dev; p.ldc = ldz;
+  p.bias = bias_dev; p.mask = mask_dev; p.ldl = ldm;
+  p.stat = stat_dev; p.ldstat = lds;
+  p.m = n_local; p.k = dim; p.ncols = batch;
+  // mgcn_score_bce_fwd's acceptance rule: the aligned (FAST) tiling only, so the record layout is the one handed to the caller
+  if (!(mgcn::aligned16(ent_dev) && mgcn::aligned16(x_dev) && mgcn::aligned16(z_dev) && lde % 4 == 0 && ldx % 4 == 0 &&
+        ldz % 4 == 0 && dim % 4 == 0 && batch % 4 == 0))
+    return mgcn::fail(MGCN_EUNSUPPORTED, "score_ce_logits: needs 16-byte aligned operands, dim %% 4 == 0 and batch %% 4 == 0");
+  set_vec_flags(&p);
+  p.tiles_m = int32_t((p.m + BM - 1) / BM);
+  const int nt = pick_nt(p.ncols);
+  const dim3 grid(unsigned(p.tiles_m), unsigned((p.ncols + nt * 16 - 1) / (nt * 16)));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (nt) {   // launch<>'s aligned half: EPI_CE has no element-wise instantiation
+    case 2: hipLaunchKernelGGL((tile_kernel<EPI_CE, true, 2, true>), grid, dim3(THREADS), 0, s, p); break;
+    case 4: hipLaunchKernelGGL((tile_kernel<EPI_CE, true, 4, true>), grid, dim3(THREADS), 0, s, p); break;
+    case 8: hipLaunchKernelGGL((tile_kernel<EPI_CE, true, 8, true>), grid, dim3(THREADS), 0, s, p); break;
+    default: hipLaunchKernelGGL((tile_kernel<EPI_CE, true, 13, true>), grid, dim3(THREADS), 0, s, p); break;
+  }
+  MGCN_CHECK_LAUNCH("tile_kernel<CE>");
+  return MGCN_OK;
+}
+
+extern "C" int mgcn_score_ce_finish(int32_t batch, int64_t n_local, float *z_dev, int64_t ldz, const uint32_t *mask_dev,
+                                    int64_t ldm, const float *stat_dev, float lbl_smooth, float inv_batch, int64_t num_entities,
+                                    float *loss_partial_dev, void *stream) {
+  MGCN_REQUIRE(batch >= 0 && n_local >= 0, "score_ce_finish: bad sizes");
+  MGCN_REQUIRE(batch < (int64_t(1) << 31) - 64 && n_local < (int64_t(1) << 31) - 64, "score_ce_finish: sizes exceed int32");
+  MGCN_REQUIRE(num_entities >= n_local && num_entities >= 1, "score_ce_finish: num_entities below n_local or below 1");
+  MGCN_REQUIRE(lbl_smooth >= 0.0f && lbl_smooth <= 1.0f, "score_ce_finish: lbl_smooth outside [0, 1]");
+  MGCN_REQUIRE(ldz >= batch && ldm >= (n_local + 31) / 32, "score_ce_finish: leading dimension too small");
+  if (batch == 0 || n_local == 0) return MGCN_OK;
+  MGCN_REQUIRE(z_dev && mask_dev && stat_dev && loss_partial_dev, "score_ce_finish: null pointer");
+  ScoreCeFinishArgs a = {};
+  a.z = z_dev; a.mask = mask_dev; a.stat = stat_dev; a.loss_partial = loss_partial_dev;
+  a.ldz = ldz; a.ldm = ldm; a.n_local = n_local;
+  a.batch = batch; a.qgroups = int32_t((int64_t(batch) + SF_Q - 1) / SF_Q);
+  a.units = ((n_local + BM - 1) / BM) * a.qgroups;
+  a.eps = lbl_smooth; a.inv_batch = inv_batch; a.smooth = lbl_smooth / float(num_entities);
+  const unsigned gx = unsigned(a.units < (int64_t(1) << 22) ? a.units : (int64_t(1) << 22));   // beyond: grid-stride
+  hipLaunchKernelGGL(score_ce_finish_kernel, dim3(gx), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
+  MGCN_CHECK_LAUNCH("score_ce_finish_kernel");
   return MGCN_OK;
 }

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from . import _native
 from .autograd import _AggregateFn, _LayerTrainFn
-from .model import _drawn_dropout, counter_dropout, list_loss_stage, query_rows, refuse_list_step, step_csr, table_bce_stage
+from .model import _drawn_dropout, counter_dropout, list_loss_stage, query_rows, refuse_list_step, refuse_table_loss, step_csr, table_bce_stage, table_ce_stage
 
 
 def shard_bounds(n, world):
@@ -705,7 +705,7 @@ def _shard_sq_reducer(model, group):
     return reduce
 
 
-def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0, clip=None, group=None, generator=None):
+def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0, clip=None, group=None, generator=None, loss='bce'):
     """One training step (main.py:59-70: forward, BCE against the train index's targets, backward, clipping, optimizer) of the
     destination-partitioned model: rank r owns destinations [n0, n1) = graph.csr(...).balanced_bounds(W)[r:r + 2], the table
     shards of `dist.shard_model_tables` for that range (a whole-table model only at W = 1) and entity rows [n0, n1) of the
@@ -727,11 +727,18 @@ def train_step_sharded(model, graph, src, rel, index, optimizer, lbl_smooth=0.0,
     depend on the partition. The call uses the current step for all its sites and then increments it, as one training-mode
     MGCN.encode does; every rank must hold the same (dropout_seed, dropout_step). With one rank the step then equals
     forward_loss + backward + clip_grad_norm_ + step bit for bit AT ANY DROPOUT.
+    loss = 'softmax': the softmax cross-entropy over the whole table instead (forward_loss(loss='softmax')): each
+    rank scores its own rows, the ranks' [B, 4] row statistics make one all-gather and are merged in rank order (_ScoreCEFn with
+    the exchange), lbl_smooth is spread over the global table; the ranks' losses and d x add up, d ent and d bias are local.
     Returns the global loss (0-dim tensor, detached)."""
+    refuse_table_loss('train_step_sharded', loss)
     ex, ent, xt = _sharded_trunk(model, graph, src, rel, optimizer, group, generator, 'train_step_sharded')
     keys = index.query_keys(src, rel)
-    loss = table_bce_stage(model, xt, ent, _own_bias(model, ex), keys, index, lbl_smooth, ex.total, ex.n0, ex.world)
-    return _sharded_finish(model, ex, loss, optimizer, clip, group)
+    if loss == 'softmax':
+        out = table_ce_stage(xt, ent, _own_bias(model, ex), keys, index, lbl_smooth, ex.total, ex.n0, ex)
+    else:
+        out = table_bce_stage(model, xt, ent, _own_bias(model, ex), keys, index, lbl_smooth, ex.total, ex.n0, ex.world)
+    return _sharded_finish(model, ex, out, optimizer, clip, group)
 
 
 def _own_bias(model, ex):
@@ -809,14 +816,16 @@ def _sharded_finish(model, ex, loss, optimizer, clip, group):
     return ex.all_reduce(loss)
 
 
-def train_epoch_sharded(model, queries, index, graph, optimizer, params, batch_size, generator=None, group=None):
+def train_epoch_sharded(model, queries, index, graph, optimizer, params, batch_size, generator=None, group=None, loss='bce'):
     """One epoch of train_step_sharded, as harness.train_device_labels: `queries` [Q, 2] int64 (DataLoader.train_queries()),
     `index` = DataLoader.train_index() on the device, shuffled with `generator` — which must be seeded identically on every rank
     so that every rank takes the same batches. Without one every call draws a new order: at W = 1 from torch's default
     generator (as harness.train_device_labels, which one epoch then equals bit for bit at dropout 0), at W > 1 from a fresh seed
-    that rank 0 draws and broadcasts. Clips at params.clip_grad, smooths with params.lbl_smooth. Returns the mean of the steps'
+    that rank 0 draws and broadcasts. Clips at params.clip_grad, smooths with params.lbl_smooth. `loss` is train_step_sharded's;
+    under 'softmax' the epoch's last batch, whatever its size, takes _ScoreCEFn's second form. Returns the mean of the steps'
     global losses."""
     from .utils import RunningAverage
+    refuse_table_loss('train_epoch_sharded', loss)
     world, _ = _world_rank(group)
     dev = model.entity_embedding.device
     if generator is None and world > 1:
@@ -826,11 +835,12 @@ def train_epoch_sharded(model, queries, index, graph, optimizer, params, batch_s
     loss_avg = RunningAverage()
     queries = queries.to(dev)
     order = torch.randperm(queries.size(0), generator=generator).to(dev)
+    extra = {} if loss == 'bce' else {'loss': loss}           # the default is the call as it was
     for i in range(0, queries.size(0), batch_size):
         q = queries.index_select(0, order[i:i + batch_size])
-        loss = train_step_sharded(model, graph, q[:, 0], q[:, 1], index, optimizer, lbl_smooth=params.lbl_smooth,
-                                  clip=params.clip_grad, group=group)
-        loss_avg.update(loss.item())
+        step_loss = train_step_sharded(model, graph, q[:, 0], q[:, 1], index, optimizer, lbl_smooth=params.lbl_smooth,
+                                  clip=params.clip_grad, group=group, **extra)
+        loss_avg.update(step_loss.item())
     return loss_avg()
 
 

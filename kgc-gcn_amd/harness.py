@@ -36,7 +36,8 @@ def train(model, data_iter, graph, optimizer, params):
     return loss_avg()
 
 
-def train_device_labels(model, queries, index, graph, optimizer, params, batch_size, generator=None, fused_loss=True, captured=None):
+def train_device_labels(model, queries, index, graph, optimizer, params, batch_size, generator=None, fused_loss=True, captured=None,
+                        loss='bce'):
     """One epoch like `train`, but the label rows never exist on the host: `queries` [Q, 2] int64
     (DataLoader.train_queries()), `index` = DataLoader.train_index() on the device; per step only B keys are indexed
     and mgcn_label_rows writes the smoothed [B, N] targets next to the scores. Shuffles like the reference's loader
@@ -44,8 +45,14 @@ def train_device_labels(model, queries, index, graph, optimizer, params, batch_s
     `captured`: a captured.CapturedTrainStep built for this model, graph, index and optimizer (or True: one is built with
     params.lbl_smooth / params.clip_grad and kept on the model for the following epochs). Every step is then one call of it (a
     replay of the captured step once it is warm), the per-step losses stay on the device, and the epoch reads them ONCE at its
-    end into the same RunningAverage; needs fused_loss=True. None (the default): the loop below, unchanged."""
+    end into the same RunningAverage; needs fused_loss=True. None (the default): the loop below, unchanged.
+    `loss`: 'bce' (the above) or 'softmax', MGCN.forward_loss's; 'softmax' needs fused_loss=True (there is no
+    label-row form of it). captured=True builds its step with this `loss`; a step handed in keeps its own."""
     from . import _native
+    from .model import refuse_table_loss
+    refuse_table_loss('train_device_labels', loss)
+    if loss == 'softmax' and not fused_loss:
+        raise _native.NativeError("train_device_labels: loss='softmax' is the fused_loss=True step")
     model.train()
     loss_avg = RunningAverage()
     dev = params.device
@@ -55,7 +62,10 @@ def train_device_labels(model, queries, index, graph, optimizer, params, batch_s
     if captured is not None and captured is not False:
         if not fused_loss:
             raise _native.NativeError('train_device_labels: a captured step is the fused_loss=True step')
-        step = _captured_step(model, graph, index, optimizer, params) if captured is True else captured
+        step = captured
+        if captured is True:
+            step = _captured_step(model, graph, index, optimizer, params)
+            step.loss = loss
         starts = range(0, queries.size(0), batch_size)
         losses = torch.empty(len(starts), dtype=torch.float32, device=dev)
         for k, i in enumerate(starts):
@@ -68,18 +78,21 @@ def train_device_labels(model, queries, index, graph, optimizer, params, batch_s
         q = queries.index_select(0, order[i:i + batch_size])
         optimizer.zero_grad()
         if fused_loss:                                   # scores, targets and loss in one launch
-            loss = model.forward_loss(q[:, 0], q[:, 1], graph, index, lbl_smooth=params.lbl_smooth)
+            if loss == 'bce':
+                step_loss = model.forward_loss(q[:, 0], q[:, 1], graph, index, lbl_smooth=params.lbl_smooth)
+            else:
+                step_loss = model.forward_loss(q[:, 0], q[:, 1], graph, index, lbl_smooth=params.lbl_smooth, loss=loss)
         else:
             labels = _native.label_rows(index.query_keys(q[:, 0], q[:, 1]), index.keys, index.ptr, index.tails, n_ent,
                                         lbl_smooth=params.lbl_smooth)
-            loss = model.loss(model(q[:, 0], q[:, 1], graph), labels)
-        loss.backward()
+            step_loss = model.loss(model(q[:, 0], q[:, 1], graph), labels)
+        step_loss.backward()
         if hasattr(optimizer, 'clip_and_step'):          # optim.ClipAdam: norm, clipping and update on the HIP kernels
             optimizer.clip_and_step(params.clip_grad)
         else:
             nn.utils.clip_grad_norm_(parameters=model.parameters(), max_norm=params.clip_grad)
             optimizer.step()
-        loss_avg.update(loss.item())
+        loss_avg.update(step_loss.item())
     return loss_avg()
 
 

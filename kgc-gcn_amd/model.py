@@ -30,7 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native
-from .autograd import (_AggregateFn, _CandBCEFn, _CandCEFn, _CounterDropoutFn, _LayerTrainFn, _QueryRowsFn, _ScoreBCEFn, _ScoreFn,
+from .autograd import (_AggregateFn, _CandBCEFn, _CandCEFn, _CounterDropoutFn, _LayerTrainFn, _QueryRowsFn, _ScoreBCEFn, _ScoreCEFn, _ScoreFn,
                        _TrunkTailFn, _TrunkTrainFn)
 from .graph import csr_for_tensors
 from .utils import get_param
@@ -174,6 +174,23 @@ def table_bce_stage(model, x, ent, bias, keys, index, lbl_smooth, num_entities, 
     if world == 1:
         return model.loss_fn(scores, labels)
     return F.binary_cross_entropy(scores, labels, reduction='sum') * (1.0 / (x.size(0) * num_entities))
+
+
+def refuse_table_loss(what, loss):
+    """The refusal that the full-table steps share, raised before any launch or collective of the step."""
+    if loss not in ('bce', 'softmax'):
+        raise _native.NativeError("%s: loss must be 'bce' or 'softmax', got %r" % (what, loss))
+
+
+def table_ce_stage(x, ent, bias, keys, index, lbl_smooth, num_entities, row0=0, ex=None):
+    """The full-table softmax cross-entropy of MGCN.forward_loss(loss='softmax') and dist.train_step_sharded(loss='softmax') from
+    the trunk output x [B, O] (include/mgcn_hip.h (20)): `ent` / `bias` are this rank's entity rows [row0, row0 + ent.size(0)) of
+    `num_entities`, `keys` the queries' keys in `index`, `ex` the sharded step's exchange. The bit-packed positives of the rank's
+    rows, then _ScoreCEFn: lbl_smooth is spread over the GLOBAL table. A rank without rows passes the empty statistic on, so it
+    joins the all-gather; a batch the logits launch refuses takes the Function's own second form, never an error."""
+    x = x if x.stride(-1) == 1 else x.contiguous()
+    mask = _native.filter_mask(keys, index.keys, index.ptr, index.tails, ent.size(0), ent_row0=row0)
+    return _ScoreCEFn.apply(x, ent, bias, mask, float(lbl_smooth), int(num_entities), ex)
 
 
 def refuse_list_step(what, model, num_queries, cand, labels, loss, logq, run_split=None):
@@ -867,15 +884,23 @@ class MGCN(nn.Module):
     def loss(self, pred, label):
         return self.loss_fn(pred, label)
 
-    def forward_loss(self, src, rel, data, index, lbl_smooth=0.0):
+    def forward_loss(self, src, rel, data, index, lbl_smooth=0.0, loss='bce'):
         """loss(forward(src, rel, data), labels) of main.py:61-62 without the [B, N] scores and labels (SURVEY N2 + N3):
         `index` is DataLoader.train_index() on the device; the targets are 1 at the known tails of (src, rel), 0
         elsewhere, smoothed as data_loader.py:41-43. Falls back to the two-step form for batch sizes the fused launch
-        does not take (B % 4 != 0)."""
+        does not take (B % 4 != 0).
+        loss: 'bce' (the above, unchanged) or 'softmax': the softmax cross-entropy over the whole entity table (1-vs-all,
+        include/mgcn_hip.h (20)), forward_loss_candidates(loss='softmax') with every entity a list position: the
+        target mass (1 - lbl_smooth) is shared by the query's known tails, lbl_smooth is spread over the N entities (eps / N, not
+        the BCE's + 1 / N), the mean runs over the B queries; a query without a known tail adds nothing and counts in B. The
+        [B, N] labels never exist and one [N, B] block holds the logits, then d loss / d logit."""
+        refuse_table_loss('MGCN.forward_loss', loss)
         self._refuse_training_ee16('MGCN.forward_loss')
         all_ent, all_rel = self._encode_for(data, src, rel)
         x = self.conv2.trunk(query_rows(self, all_ent, src), query_rows(self, all_rel, rel))
         keys = index.query_keys(src, rel)
+        if loss == 'softmax':
+            return table_ce_stage(x, all_ent.contiguous(), self.conv2.bias, keys, index, lbl_smooth, all_ent.size(0))
         return table_bce_stage(self, x, all_ent.contiguous(), self.conv2.bias, keys, index, lbl_smooth, all_ent.size(0))
 
     def forward_loss_candidates(self, src, rel, cand, data, index=None, labels=None, lbl_smooth=0.0, loss='bce', logq=None,
